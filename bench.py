@@ -10,9 +10,16 @@ BasePolicy.forward + DAgger loss + backward (+ gradient all-reduce over RCCL for
 `value` = policy steps (rows) per second over all ranks = T*N*world*K / t.  Inputs are
 device-resident before the timed region.  Prints ONE JSON line on rank 0.
 
-The line carries `roofline` for the dominant kernel (live HIP-event timing of the conv-engine
-launches inside the timed region) and `cpu_baseline` (the oracle — a PyTorch-CPU port of the
-reference's update step — timed on this box's host cores on a bounded sample, N=1 only).
+A plain run does only what `value` / `ms_per_step` need: set up, warm up, time --steps updates,
+print the line.  --full adds everything else the line can carry: `roofline` / `kernels` for the
+dominant kernel families (live HIP-event timing of the conv-engine launches inside the timed
+region), the float32 / bf16+f32grad / feeder-layout legs, the other BASELINE configs
+(bench_legs.py) and `cpu_baseline` (the oracle — a PyTorch-CPU port of the reference's update
+step — timed on the host cores on a bounded sample, N=1 only).
+
+--dump-outputs DIR writes what the last timed update computed (loss, action logits, aux loss,
+a fixed sample of the gradients and of the updated parameters) as DIR/<name>.npy; the inputs,
+the initial weights and the number of updates before it are the same from run to run.
 """
 import argparse
 import json
@@ -206,8 +213,44 @@ def cpu_baseline(state, T_full, N, budget_s=90.0):
                        + (f", control-group quota {quota:g} CPUs" if quota is not None else "") + f"){scaled}")
 
 
-def measure(args, dtype, steps, warmup, rank, world, local, dev):
-    """Build the policy in `dtype` mode and time `steps` updates; returns (dt, prof, loss, state_cpu)."""
+DUMP_SAMPLE = 1 << 16     # --dump-outputs: elements kept per gradient / parameter tensor (a fixed, seeded sample of larger ones)
+
+
+def dump_outputs(out_dir, policy, last):
+    """What the last timed update handed its caller, as float32 / float64 .npy files: the loss, the action logits and the aux loss,
+    and the gradients and updated values of every parameter that received a gradient (concatenated in named_parameters() order;
+    tensors above DUMP_SAMPLE elements by a sample whose indices depend only on the tensor sizes)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(20240613)
+    grads, params = [], []
+    with torch.no_grad():
+        for _, p in policy.named_parameters():
+            if p.grad is None:
+                continue
+            g, v, n = p.grad.detach().reshape(-1), p.detach().reshape(-1), p.numel()
+            if n > DUMP_SAMPLE:
+                idx = torch.from_numpy(np.sort(rng.choice(n, DUMP_SAMPLE, replace=False))).to(p.device)
+                g, v = g[idx], v[idx]
+            grads.append(g.float().cpu())
+            params.append(v.float().cpu())
+    arrays = {
+        "loss": np.asarray([float(last["loss"])], dtype=np.float64),
+        "aux_loss": np.asarray([float(last["aux"])], dtype=np.float64),
+        "action_logits": last["pred"].float().cpu().numpy(),
+        "param_grads_sample": torch.cat(grads).numpy(),
+        "updated_params_sample": torch.cat(params).numpy(),
+    }
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, f"--dump-outputs: {total} bytes, over the 64 MB bound"
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def measure(args, dtype, steps, warmup, rank, world, local, dev, full=True, dump_dir=None):
+    """Build the policy in `dtype` mode and time `steps` updates; returns (dt, prof, loss, state_cpu).
+    full=False: no kernel timing (prof is empty) and no host copy of the initial state (state_cpu is None).
+    dump_dir: write the last timed update's outputs there (dump_outputs)."""
     from wsmgmap import ops
     from wsmgmap.common.aux_losses import AuxLosses
     from wsmgmap.config import default_model_config
@@ -217,7 +260,7 @@ def measure(args, dtype, steps, warmup, rank, world, local, dev):
     torch.manual_seed(0)
     policy = BasePolicy(None, _Box(), default_model_config(num_proc=1, gpu_id=local, compute_dtype=dtype))
     policy.net.instruction_encoder.embedding_layer.weight.requires_grad_(False)  # reference default: frozen embeddings
-    state_cpu = {k: v.detach().clone() for k, v in policy.state_dict().items()} if rank == 0 else None
+    state_cpu = {k: v.detach().clone() for k, v in policy.state_dict().items()} if rank == 0 and full else None
     policy = policy.to(dev)
     policy.train()
     policy.net.depth_encoder.eval()
@@ -247,6 +290,7 @@ def measure(args, dtype, steps, warmup, rank, world, local, dev):
     # the previous update to finish on the GPU (wsmgmap/ops/core.py, "input readiness")
     ops.mark_inputs_ready(obs["instruction"])
     AuxLosses.activate()
+    last = {}       # the latest update's outputs, detached (what --dump-outputs writes after the timed region)
 
     def update():
         opt.zero_grad(set_to_none=True)
@@ -259,7 +303,34 @@ def measure(args, dtype, steps, warmup, rank, world, local, dev):
         if reducer:
             reducer.finish()
         opt.step()
+        last.update(pred=pred.detach(), aux=aux.detach() if torch.is_tensor(aux) else aux, loss=loss.detach())
         return loss
+
+    def snapshot():
+        """What an update changes: the parameters the optimizer steps, the buffers of train-mode modules (running statistics) and the
+        optimizer's per-parameter state.  Nothing else, and nothing unchanged, is copied back: an in-place copy advances a tensor's
+        version counter, which the caches of derived operands (the frozen encoders' folded weights among them) compare."""
+        ts = list(opt.state.keys())
+        for m in policy.modules():
+            if m.training:
+                ts += [b for b in m.buffers(recurse=False) if b is not None]
+        return ([(t, t.detach().clone()) for t in ts],
+                {p: {k: (v.clone() if torch.is_tensor(v) else v) for k, v in st.items()} for p, st in opt.state.items()})
+
+    def restore(snap):
+        with torch.no_grad():
+            for t, s in snap[0]:
+                if not torch.equal(t, s):
+                    t.copy_(s)
+            for p in [p for p in opt.state if p not in snap[1]]:
+                del opt.state[p]
+            for p, saved in snap[1].items():
+                st = opt.state[p]
+                for k, v in saved.items():
+                    if torch.is_tensor(v) and torch.is_tensor(st.get(k)):
+                        st[k].copy_(v)
+                    else:
+                        st[k] = v.clone() if torch.is_tensor(v) else v
 
     # ---- round 6: a persistent-kernel timeout must not cost the run its line (VERDICT r05 item 4) --------------------------------
     # The two recurrences and the instruction LSTM are persistent kernels whose workgroups wait for each other with BOUNDED spins;
@@ -329,12 +400,13 @@ def measure(args, dtype, steps, warmup, rank, world, local, dev):
         # which conv-engine kernel family dominates is learned on the warm-up updates (all six entry points timed); inside
         # the timed region only that family is bracketed with HIP events — every timed launch costs two event records on a
         # host that is within 10 % of being the bottleneck, and `value` should not pay for the other five
+        # (a plain run times no kernel family: the events only feed the --full line's roofline / kernels)
         warm_prof = {}
         for i in range(warmup):
-            if i == warmup - 1:
+            if i == warmup - 1 and full:
                 ops.profile_begin()      # the last warm-up update: first-launch effects are over
             update()
-        if warmup > 0:
+        if warmup > 0 and full:
             warm_prof = ops.profile_end()
         dom_entry = None
         if warm_prof:
@@ -365,6 +437,9 @@ def measure(args, dtype, steps, warmup, rank, world, local, dev):
         measure.prewarm = None
         prewarm_s = args.prewarm_s if dtype == args.dtype else min(args.prewarm_s, 0.5)   # the extra float32 leg: a short one
         if prewarm_s > 0:
+            # how many updates fit the prewarm depends on the build and the box: the state from before it is put back afterwards, so
+            # that the timed updates (and what --dump-outputs writes) follow the same number of updates on every run
+            snap = snapshot()
             tp = time.perf_counter()
             n_pw = 0
             while True:
@@ -380,6 +455,8 @@ def measure(args, dtype, steps, warmup, rank, world, local, dev):
                 if go == 0.0:
                     break
             measure.prewarm = dict(seconds=round(time.perf_counter() - tp, 3), updates=n_pw)
+            restore(snap)
+            del snap
         if args.dp:
             dist.barrier()
         torch.cuda.synchronize()
@@ -402,7 +479,7 @@ def measure(args, dtype, steps, warmup, rank, world, local, dev):
         # event, one box, interleaved: profiles/r05_bench_line_cost.txt) — BOTH families are now timed on every 4th update of the timed
         # region only (10.38); WSMG_BENCH_PROF_EVERY=1 restores the largest family on every update
         prof_every = int(os.environ.get("WSMG_BENCH_PROF_EVERY", "4"))
-        if os.environ.get("WSMG_BENCH_NOPROF") != "1":
+        if full and os.environ.get("WSMG_BENCH_NOPROF") != "1":
             ops.profile_begin(only=[dom_entry] if dom_entry else None)
         # an event every WIN updates (no synchronisation): `sustained` for --steps >= 200 (50-update windows), and `windows` for every
         # run (a quarter of the run each), so that a transient stall inside the timed region — one run in ~40 on this pool came out at
@@ -501,6 +578,8 @@ def measure(args, dtype, steps, warmup, rank, world, local, dev):
     dt, prof, loss, warm_prof = guarded(phases)
     measure.fallback = fbk.report()
     final_loss = float(loss.detach())
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, policy, last)
     # The same update captured into ONE HIP graph and replayed (wsmgmap.graph.GraphedUpdate): reported beside the eager figure,
     # never as `value` — the roofline object is measured with HIP events around eager launches inside the timed region, which
     # a graph replay has none of.  One process only; opt-in (WSMG_BENCH_GRAPH=1): at the bench size the replay takes the same
@@ -569,13 +648,23 @@ def main():
                          "bf16+f32grad = bf16 with the three first-of-chain weight gradients from a 16-bit-mantissa dY (opt-in, round 6)")
     ap.add_argument("--prewarm-s", type=float, default=float(os.environ.get("WSMG_BENCH_PREWARM_S", "1.5")),
                     help="seconds of untimed updates between the warm-up and the timed region (clock ramp / allocator steady state); 0 = none")
-    ap.add_argument("--no-f32", action="store_true", help="skip the extra float32 parity-mode measurement")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: per-kernel timing and roofline, the float32 / bf16+f32grad / feeder-layout "
+                         "legs, the other BASELINE configs and the CPU baseline (the --no-* options below trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed update's outputs (loss, action logits, aux loss, sampled gradients and updated parameters) "
+                         "as DIR/<name>.npy")
+    ap.add_argument("--no-f32", action="store_true", help="--full: skip the extra float32 parity-mode measurement")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the cfg1 / cfg4 / cfg5 legs (BASELINE configs[0], [3], [4]; bench_legs.py, ~2 s after the cfg2 leg)")
+                    help="--full: skip the cfg1 / cfg4 / cfg5 legs (BASELINE configs[0], [3], [4]; bench_legs.py, ~2 s after the cfg2 leg)")
     ap.add_argument("--cpu-budget", type=float, default=90.0,
                     help="seconds the host may spend on the TWO timed CPU-baseline updates: T=64 if they fit, else T=32 / 16")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py --steps must be at least 1")
+    if not args.full:
+        args.no_f32 = args.no_cpu_baseline = args.no_other_configs = True
 
     share = os.environ.get("WSMG_BENCH_SHARE_GPU") == "1"
     if "WORLD_SIZE" not in os.environ:
@@ -632,7 +721,8 @@ def main():
             dist.init_process_group(backend)
 
     T, N = args.T, args.N
-    dt, prof, final_loss, state_cpu = measure(args, args.dtype, args.steps, args.warmup, rank, world, local, dev)
+    dt, prof, final_loss, state_cpu = measure(args, args.dtype, args.steps, args.warmup, rank, world, local, dev, full=args.full,
+                                              dump_dir=args.dump_outputs)
     measure.host_ms_main = getattr(measure, "host_ms", None)
     dp_info = measure.dp_info
     fallback = getattr(measure, "fallback", None)
@@ -756,6 +846,7 @@ def main():
             "scaling": "weak",
             "vs_baseline": None,
             "dtype": args.dtype,
+            "full": args.full,
             "data": "synthetic",
             "config": {"workload": f"teacher-forcing update fwd+bwd+Adam, T={T} x N={N} rows/GPU (B={T * N}), E=100 C=64 "
                                    f"80-token instructions, cached rgb/depth/ego-map features (BASELINE configs[1])",

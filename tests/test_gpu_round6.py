@@ -61,6 +61,31 @@ def test_bench_line_names_the_default_core_without_a_timeout():
     assert line["recurrent_core"]["fallback_level"] == 0 and line["recurrent_core"]["recurrent_core"].startswith("chained"), line["recurrent_core"]
 
 
+def test_bench_dump_outputs_do_not_depend_on_the_prewarm(tmp_path):
+    """bench.py --dump-outputs: the last timed update's outputs as float .npy files within 64 MB, the same whether or not a
+    (time-bounded, so variable-length) prewarm ran before the timed region — the state from before it is restored."""
+    a, b = tmp_path / "a", tmp_path / "b"
+    la, _ = _bench_line({}, "--dump-outputs", str(a))
+    lb, _ = _bench_line({}, "--prewarm-s", "1", "--dump-outputs", str(b))
+    assert la["prewarm_updates"] == 0 and lb["prewarm_updates"] > 0 and la["full"] is False
+    names = sorted(p.name for p in a.iterdir())
+    assert names == ["action_logits.npy", "aux_loss.npy", "loss.npy", "param_grads_sample.npy", "updated_params_sample.npy"]
+    assert names == sorted(p.name for p in b.iterdir())
+    assert sum((a / n).stat().st_size for n in names) <= 64 << 20
+    da = {n: np.load(a / n) for n in names}
+    db = {n: np.load(b / n) for n in names}
+    for n in names:
+        assert da[n].dtype in (np.float32, np.float64) and da[n].shape == db[n].shape and np.isfinite(da[n]).all(), n
+    assert da["action_logits.npy"].shape == (512, 2)
+    assert abs(float(da["loss.npy"][0]) - la["loss"]) <= 1e-5 and abs(float(db["loss.npy"][0]) - lb["loss"]) <= 1e-5
+    # the same number of updates from the same initial state: equal up to the run-to-run order of floating-point sums
+    assert abs(float(da["loss.npy"][0]) - float(db["loss.npy"][0])) <= 1e-3 * abs(float(da["loss.npy"][0]))
+    pa, pb = da["updated_params_sample.npy"], db["updated_params_sample.npy"]
+    assert float(np.abs(pa - pb).mean()) <= 1e-5, float(np.abs(pa - pb).mean())
+    ga, gb = da["param_grads_sample.npy"], db["param_grads_sample.npy"]
+    assert float(np.abs(ga - gb).mean()) <= 1e-2 * float(np.abs(ga).mean()), (float(np.abs(ga - gb).mean()), float(np.abs(ga).mean()))
+
+
 # ----------------------------------------------------------------------------- the concatenation in front of map_cated_linear, in place
 def _update_grads(monkeypatch, T, N, seed=91, **switches):
     import bench

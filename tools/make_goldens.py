@@ -288,7 +288,10 @@ def g5f():
     L = k.shape[2]
     mask = np.arange(L)[None, :] >= c["lengths"][inv][:, None]
     o, a = pol.net._attn(T(c["q"]), T(k), T(v), T(mask))
-    np.savez_compressed(os.path.join(OUT, "g5f_attn_fp8.npz"), out=o.detach().numpy(), attn=a.detach().numpy())
+    # and in float64: float32 results depend on the host's CPU kernels at the tests' tolerances, float64 ones do not
+    o64, a64 = pol.net._attn(T(c["q"]).double(), T(k).double(), T(v).double(), T(mask))
+    np.savez_compressed(os.path.join(OUT, "g5f_attn_fp8.npz"), out=o.detach().numpy(), attn=a.detach().numpy(),
+                        out_f64=o64.detach().numpy(), attn_f64=a64.detach().numpy())
     print("g5f out", o.detach().numpy().ravel()[:4], "attn row sums", a.detach().numpy().sum(1)[:3])
 
 
@@ -303,8 +306,14 @@ def g9():
         feat = enc.visual_encoder({"depth": T(obs_np["depth"])})
         out = enc({"depth": T(obs_np["depth"])})
     assert tuple(feat.shape) == (2, 128, 4, 4) and tuple(out.shape) == (2, 192, 4, 4)
-    np.savez_compressed(os.path.join(OUT, "g9_depth.npz"), feat=feat.numpy(), out_sample=out.numpy()[:, ::7, :, :],
-                        n_params=np.int64(sum(p.numel() for p in enc.visual_encoder.parameters())))
+    n_params = np.int64(sum(p.numel() for p in enc.visual_encoder.parameters()))
+    # and in float64 (the float32 backbone's result moves by ~1e-4 with the host's CPU kernels and thread count; float64 does not)
+    enc.double()
+    with torch.no_grad():
+        feat64 = enc.visual_encoder({"depth": T(obs_np["depth"]).double()})
+        out64 = enc({"depth": T(obs_np["depth"]).double()})
+    np.savez_compressed(os.path.join(OUT, "g9_depth.npz"), feat=feat.numpy(), out_sample=out.numpy()[:, ::7, :, :], n_params=n_params,
+                        feat_f64=feat64.numpy(), out_sample_f64=out64.numpy()[:, ::7, :, :])
     print("g9 feat", feat.numpy().ravel()[:4], "params", sum(p.numel() for p in enc.visual_encoder.parameters()))
 
 

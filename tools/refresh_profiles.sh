@@ -4,7 +4,7 @@ TAG=${1:-r02}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/refresh_$TAG
 mkdir -p $O && rm -rf $O/*
-timeout 600 python bench.py > $O/bench.json 2> $O/bench.err; echo bench rc=$?
+timeout 600 python bench.py --full > $O/bench.json 2> $O/bench.err; echo bench rc=$?
 timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-f32 --no-other-configs --prewarm-s 0 > $O/stats.log 2>&1; echo stats rc=$?
 # the counter passes serialise the kernels of a process: the chained recurrent core's device-side waits (a kernel spinning until a kernel
 # on another stream has produced its chunk) would spin out their bound there — these passes run the chunk-launch route (same conv kernels)
