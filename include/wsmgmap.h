@@ -543,6 +543,26 @@ int wsmg_gru_bwd_owned(const float* dy, const float* dhT, const float* w_hh, con
                        const float* y, const float* save_r, const float* save_z, const float* save_n, const float* save_ghn,
                        int T, int N, int hidden, float* dgi, float* dgh, float* dh0, void* sync_ws, wsmg_stream_t stream);
 
+/* ============================ persistent masked-LSTM state encoders ============================ */
+/* habitat-lab RNNStateEncoder with rnn_type "LSTM" (hidden 512), the reference's MODEL.STATE_ENCODER.rnn_type option at
+ * mg_map_policy.py:118-123,147-152: h_{t-1} AND c_{t-1} are multiplied by masks[t] before every step, gate order i,f,g,o.
+ * As wsmg_gru_fwd: one launch of 32 cooperating workgroups for all T <= 1023 steps, W_hh [4H][H] in registers, h crossing
+ * workgroups as {value, tag} words; c stays in the thread that owns its (unit, batch) slot.  gi = x W_ih^T + b_ih [T][N][4H]
+ * is computed by the caller; N <= 8.  sync_ws: wsmg_lstm_state_workspace_bytes(T) bytes of 128-B-aligned device scratch,
+ * cleared by the call.  Writes y [T][N][H] (h_T = y[T-1]), c_T [N][H], save_gates [T][N][4H] (post-activation i,f,g,o)
+ * and save_c [T][N][H] (c_t), the last two consumed by wsmg_lstm_state_bwd. */
+int64_t wsmg_lstm_state_workspace_bytes(int T);
+int wsmg_lstm_state_fwd(const float* gi, const float* w_hh, const float* b_hh, const float* h0, const float* c0,
+                        const float* masks, int T, int N, int hidden, float* y, float* c_T, float* save_gates,
+                        float* save_c, void* sync_ws, wsmg_stream_t stream);
+/* backward through time (gru_bwd's partial-sum exchange of dh_{t-1}; the dc recursion stays in the owning thread): dy [T][N][H]
+ * (gradient of every h_t), dhT, dcT [N][H] or NULL; writes dgates [T][N][4H] (gradient of the gate pre-activations: of gi and
+ * of W_hh h + b_hh alike), dh0 and dc0 [N][H].  The caller forms dW_hh = dgates^T (mask * h_prev), db_hh = db_ih = sum dgates,
+ * and back-propagates dgates through its input GEMM. */
+int wsmg_lstm_state_bwd(const float* dy, const float* dhT, const float* dcT, const float* w_hh, const float* c0,
+                        const float* masks, const float* save_gates, const float* save_c, int T, int N, int hidden,
+                        float* dgates, float* dh0, float* dc0, void* sync_ws, wsmg_stream_t stream);
+
 /* ============================ persistent packed bidirectional LSTM ============================ */
 /* nn.LSTM(50 -> 128, bidirectional) over packed instructions (instruction_encoder.py:80-92): row b is
  * active at token t iff t < lengths[b]; inactive positions emit 0.  Both directions run concurrently
@@ -577,6 +597,7 @@ int wsmg_group_norm_nhwc_bf16(const void* x, int x_f32, const void* residual, co
  * cannot time out; mg_map_policy.py:220-227,242-249, instruction_encoder.py:80-92 are the replaced call sites).
  * wsmg_rnn_debug_spin_limit(n): bound every spin by n polls (0 = default, 2^20) — test hook to force a timeout.
  * Bit 16 (round 6): the grid barrier of wsmg_attn_fp8_mfma_fused timed out (its outputs are NaN).
+ * Bits 32 and 64: wsmg_lstm_state_fwd / wsmg_lstm_state_bwd timed out (y, c_T / dgates, dh0, dc0 are NaN).
  * wsmg_rnn_debug_inject(bits): OR `bits` into the word as a timed-out kernel would — test hook for the callers' error paths
  * (bench.py's in-process fallback, GradAllReducer's cross-rank agreement); returns the word after the OR. */
 int wsmg_rnn_status(int clear);

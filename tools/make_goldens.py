@@ -7,7 +7,7 @@ feeds them the seeded inputs of oracle/cases.py with weights from oracle/detfill
 writes small .npz fixtures (data only: inputs are re-derivable, outputs are digests /
 small tensors) to tests/golden/.
 
-    python tools/make_goldens.py [g1 g2 g3 g4 g5]
+    python tools/make_goldens.py [g1 g2 g3 g4 g5 ... g10]
 """
 import hashlib
 import os
@@ -57,14 +57,14 @@ class _TorchProxy:
         return torch.device("cpu")
 
 
-def model_config(E=100, C=64, G=240, num_proc=2):
+def model_config(E=100, C=64, G=240, num_proc=2, rnn_type="GRU"):
     return Config(
         INSTRUCTION_ENCODER=Config(vocab_size=2504, embedding_size=50, use_pretrained_embeddings=False,
                                    hidden_size=128, rnn_type="LSTM", final_state_only=False, bidirectional=True),
         RGB_ENCODER=Config(output_size=256, pretrain_model="__synthetic__"),
         DEPTH_ENCODER=Config(output_size=128, ddppo_checkpoint="NONE", backbone="resnet50"),
         MAP_ENCODER=Config(ego_map_size=E, output_size=256),
-        STATE_ENCODER=Config(hidden_size=512, rnn_type="GRU", input_type=["rgb", "depth", "map"]),
+        STATE_ENCODER=Config(hidden_size=512, rnn_type=rnn_type, input_type=["rgb", "depth", "map"]),
         PROGRESS_MONITOR=Config(use=True, alpha=1.0),
         CONTRASTIVE_MONITOR=Config(use=True, alpha=1.0, target_tau=0.07),
         PREDICTION_MONITOR=Config(use=True, alpha=0.1),
@@ -73,7 +73,7 @@ def model_config(E=100, C=64, G=240, num_proc=2):
     )
 
 
-def build_policy(num_proc=2):
+def build_policy(num_proc=2, rnn_type="GRU"):
     import vlnce_baselines.common.rgb_mapping as rm
     rm.torch = _TorchProxy()
     import vlnce_baselines.models.encoders.unet_encoder as ue
@@ -89,7 +89,7 @@ def build_policy(num_proc=2):
     torch.load = fake_load
     try:
         obs_space = sp.Dict({"depth": sp.Box(shape=(256, 256, 1)), "rgb": sp.Box(shape=(224, 224, 3))})
-        pol = BasePolicy(obs_space, sp.Box(shape=(2,)), model_config(num_proc=num_proc))
+        pol = BasePolicy(obs_space, sp.Box(shape=(2,)), model_config(num_proc=num_proc, rnn_type=rnn_type))
     finally:
         torch.load = real_load
     sd = pol.state_dict()
@@ -165,13 +165,24 @@ def g2():
 
 # ============================================================================= G3
 def g3():
+    out = _update_golden()
+    print("g3 pred", out["pred"].ravel()[:4], "aux", float(out["aux_loss"]), "loss", float(out["loss"]),
+          "params with grad", len(out["grad.names"]), "trainable without grad", len(out["grad.none"]))
+    np.savez_compressed(os.path.join(OUT, "g3_update.npz"), **out)
+
+
+def _update_golden(rnn_type="GRU", restarts=()):
+    """One teacher-forcing update of the reference policy (T = 4, N = 2) on cases.update_inputs; `restarts`: extra (t, n)
+    episode starts set to 0 in the masks."""
     from vlnce_baselines.common.aux_losses import AuxLosses
-    pol = build_policy()
+    pol = build_policy(rnn_type=rnn_type)
     pol.train()
     pol.net.depth_encoder.eval()
     pol.net.rgb_encoder.eval()
     T_, N = 4, 2
     obs_np, prev, masks, weights = cases.update_inputs(T_, N)
+    for t, n in restarts:
+        masks[t * N + n] = 0.0
     obs = {k: T(v) for k, v in obs_np.items()}
     AuxLosses.activate()
     AuxLosses.clear()
@@ -222,15 +233,29 @@ def g3():
     # pred_sem_map is returned by the net, not kept: re-run the net for its digest (BN stats move again; fine)
     with torch.no_grad():
         AuxLosses.clear()
-        h1 = torch.zeros(2, N, 512)
+        nl = pol.net.num_recurrent_layers
+        h1 = torch.zeros(nl, N, 512)
         pol.eval()
         _, _, sem = pol.net(obs, h1, T(prev), T(masks))
         flat_summary("eval.pred_sem_map", sem, out)
-        out["eval.pred"] = pol.action_distribution(pol.net(obs, torch.zeros(2, N, 512), T(prev), T(masks))[0]).mean.numpy()
+        out["eval.pred"] = pol.action_distribution(pol.net(obs, torch.zeros(nl, N, 512), T(prev), T(masks))[0]).mean.numpy()
     AuxLosses.deactivate()
-    print("g3 pred", out["pred"].ravel()[:4], "aux", float(out["aux_loss"]), "loss", float(out["loss"]),
-          "params with grad", len(names), "trainable without grad", len(nograd))
-    np.savez_compressed(os.path.join(OUT, "g3_update.npz"), **out)
+    if rnn_type != "GRU":
+        out["masks"] = np.asarray(masks, np.float32)
+        for k, v in pol.state_dict().items():
+            if "state_encoder.rnn." in k:
+                out["shape." + k] = np.array(v.shape, np.int64)
+    return out
+
+
+# ============================================================================= G10
+def g10():
+    """g3 with MODEL.STATE_ENCODER.rnn_type = "LSTM" (habitat's packed [h; c] state: 4 recurrent layers) and one more episode
+    restart in the middle of the sequence (t = 2, column 1); the masks and the reference's rnn.* shapes are stored too."""
+    out = _update_golden("LSTM", restarts=((2, 1),))
+    print("g10 pred", out["pred"].ravel()[:4], "aux", float(out["aux_loss"]), "loss", float(out["loss"]),
+          "h_out", out["h_out"].shape)
+    np.savez_compressed(os.path.join(OUT, "g10_lstm_update.npz"), **out)
 
 
 # ============================================================================= G4
@@ -390,6 +415,6 @@ def g8():
 
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["shapes", "g1", "g2", "g3", "g4", "g5", "g5f", "g8", "g9"]
+    which = sys.argv[1:] or ["shapes", "g1", "g2", "g3", "g4", "g5", "g5f", "g8", "g9", "g10"]
     for w in which:
         globals()[w]()

@@ -8,7 +8,7 @@ What is stubbed:
     boundaries — the reference has no tests that pin them):
       - torch_scatter 2.0.6 `scatter_max`   (call site rgb_mapping.py:220-225)
       - torchvision `resnet18`              (call sites map_encoder.py:75, unet_encoder.py:34)
-      - habitat-lab v0.1.5 `RNNStateEncoder`, `Net`, `CriticHead`, `Flatten`,
+      - habitat-lab v0.1.5 `RNNStateEncoder` (GRU and LSTM branches), `Net`, `CriticHead`, `Flatten`,
         `ResNetEncoder` + `resnet.resnet50` (the GroupNorm DD-PPO depth backbone)
 """
 import sys
@@ -129,23 +129,42 @@ class Flatten(nn.Module):
 class RNNStateEncoder(nn.Module):
     """habitat-lab v0.1.5 rl/models/rnn_state_encoder.py restated: hidden state is
     multiplied by `masks` before the step (single step) or at each segment start
-    (sequence split wherever any mask is 0)."""
+    (sequence split wherever any mask is 0).  rnn_type "GRU" or "LSTM" (getattr(nn, rnn_type));
+    an LSTM's (h, c) travel packed as one [2 * num_layers, N, H] tensor (_pack_hidden /
+    _unpack_hidden) and both are masked.  Third-party semantics, parity UNPINNED."""
 
     def __init__(self, input_size, hidden_size, num_layers=1, rnn_type="GRU"):
         super().__init__()
-        assert rnn_type == "GRU"
-        self._num_recurrent_layers = num_layers
-        self.rnn = nn.GRU(input_size=input_size, hidden_size=hidden_size, num_layers=num_layers)
+        assert rnn_type in ("GRU", "LSTM")
+        self._num_recurrent_layers = num_layers * (2 if "LSTM" in rnn_type else 1)
+        self._rnn_type = rnn_type
+        self.rnn = getattr(nn, rnn_type)(input_size=input_size, hidden_size=hidden_size, num_layers=num_layers)
 
     @property
     def num_recurrent_layers(self):
         return self._num_recurrent_layers
 
+    def _pack_hidden(self, hidden_states):
+        if "LSTM" in self._rnn_type:
+            hidden_states = torch.cat([hidden_states[0], hidden_states[1]], dim=0)
+        return hidden_states
+
+    def _unpack_hidden(self, hidden_states):
+        if "LSTM" in self._rnn_type:
+            hidden_states = (hidden_states[0:self.rnn.num_layers], hidden_states[self.rnn.num_layers:])
+        return hidden_states
+
+    def _mask_hidden(self, hidden_states, masks):
+        if isinstance(hidden_states, tuple):
+            return tuple(v * masks for v in hidden_states)
+        return masks * hidden_states
+
     def forward(self, x, hidden_states, masks):
         n = hidden_states.size(1)
+        hidden_states = self._unpack_hidden(hidden_states)
         if x.size(0) == n:
-            y, h = self.rnn(x.unsqueeze(0), hidden_states * masks.unsqueeze(0))
-            return y.squeeze(0), h
+            y, h = self.rnn(x.unsqueeze(0), self._mask_hidden(hidden_states, masks.unsqueeze(0)))
+            return y.squeeze(0), self._pack_hidden(h)
         t = x.size(0) // n
         x = x.view(t, n, x.size(1))
         masks = masks.view(t, n)
@@ -154,9 +173,9 @@ class RNNStateEncoder(nn.Module):
         outs = []
         h = hidden_states
         for s, e in zip(bounds[:-1], bounds[1:]):
-            y, h = self.rnn(x[s:e], h * masks[s].view(1, -1, 1))
+            y, h = self.rnn(x[s:e], self._mask_hidden(h, masks[s].view(1, -1, 1)))
             outs.append(y)
-        return torch.cat(outs, 0).view(t * n, -1), h
+        return torch.cat(outs, 0).view(t * n, -1), self._pack_hidden(h)
 
 
 # habitat-lab v0.1.5 rl/ddppo/policy/resnet.py + resnet_policy.py restated (third-party, not under /root/reference:

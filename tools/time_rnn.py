@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""GPU-box tool: per-kernel time of the persistent GRU / LSTM launches (HIP events, no other load)."""
+"""GPU-box tool: per-kernel time of the persistent GRU / LSTM-state / bi-LSTM launches, and of the LSTM state encoder's stock
+route for contrast (HIP events, no other load)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "ws-mgmap_amd"))
@@ -27,6 +28,28 @@ def timeit(f, reps=20):
     return a.elapsed_time(b) / reps * 1e3
 tf, tb = timeit(fwd), timeit(bwd)
 print(f"GRU T={T} N={N}: fwd {tf:.1f} us ({tf / T:.2f} us/step)  bwd {tb:.1f} us ({tb / T:.2f} us/step)")
+# LSTM state encoder (STATE_ENCODER.rnn_type = "LSTM"): the persistent kernel pair on the same sequence, then the stock route
+sgi = torch.randn(T, N, 4 * H, device="cuda"); swhh = torch.randn(4 * H, H, device="cuda") * 0.04
+sbhh = torch.randn(4 * H, device="cuda") * 0.1; c0 = torch.randn(N, H, device="cuda")
+sy = torch.empty(T, N, H, device="cuda"); scT = torch.empty(N, H, device="cuda")
+ssg = torch.empty(T, N, 4 * H, device="cuda"); ssc = torch.empty(T, N, H, device="cuda")
+sdg = torch.empty(T, N, 4 * H, device="cuda"); sdh0 = torch.empty(N, H, device="cuda"); sdc0 = torch.empty(N, H, device="cuda")
+sws = ops._rnn_workspace(L.wsmg_lstm_state_workspace_bytes(T), gi.device)
+def sfwd(): _abi.call("wsmg_lstm_state_fwd", P(sgi), P(swhh), P(sbhh), P(h0), P(c0), P(masks), T, N, H, P(sy), P(scT), P(ssg), P(ssc), P(sws), st())
+def sbwd(): _abi.call("wsmg_lstm_state_bwd", P(gy), None, None, P(swhh), P(c0), P(masks), P(ssg), P(ssc), T, N, H, P(sdg), P(sdh0), P(sdc0), P(sws), st())
+tsf, tsb = timeit(sfwd), timeit(sbwd)
+print(f"LSTM state T={T} N={N}: fwd {tsf:.1f} us ({tsf / T:.2f} us/step)  bwd {tsb:.1f} us ({tsb / T:.2f} us/step)")
+from wsmgmap.models.rnn_state_encoder import RNNStateEncoder
+enc = RNNStateEncoder(640, H, rnn_type="LSTM").cuda()
+sx = torch.randn(T * N, 640, device="cuda", requires_grad=True); shc = torch.randn(2, N, H, device="cuda")
+smk = masks.reshape(-1, 1); sgy = gy.reshape(T * N, H)
+def kf(): enc(sx, shc, smk)
+def kfb(): (enc(sx, shc, smk)[0] * sgy).sum().backward()
+def stf(): enc.forward_stock(sx, shc, smk)
+def stfb(): (enc.forward_stock(sx, shc, smk)[0] * sgy).sum().backward()
+tkf, tkfb, tstf, tstfb = timeit(kf), timeit(kfb), timeit(stf), timeit(stfb)
+print(f"LSTM state module T={T} N={N} (in 640): kernel route fwd {tkf:.1f} us  fwd+bwd {tkfb:.1f} us | "
+      f"stock nn.LSTM route (forward_stock) fwd {tstf:.1f} us  fwd+bwd {tstfb:.1f} us")
 U, Lt = 8, int(os.environ.get("L", "80"))
 lgi = torch.randn(U, Lt, 2, 512, device="cuda", requires_grad=True); lw = torch.randn(2, 512, 128, device="cuda") * 0.08
 lb = torch.randn(2, 512, device="cuda") * 0.1; lens = torch.full((U,), Lt, device="cuda", dtype=torch.int32)

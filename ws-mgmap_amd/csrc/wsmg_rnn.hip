@@ -711,6 +711,350 @@ extern "C" int wsmg_gru_chain_workgroups(void) { return NWG; }
 __attribute__((visibility("hidden"))) unsigned* wsmgi_rnn_status_dev() { return rnn_status_dev(); }
 
 // =================================================================================================
+// Persistent masked-LSTM state encoder (habitat-lab RNNStateEncoder with rnn_type = "LSTM", hidden 512,
+// N <= 8): the reference's MODEL.STATE_ENCODER.rnn_type option.  The two kernels are the 8-wave GRU pair
+// above with FOUR gate rows per unit (i, f, g, o: PyTorch nn.LSTM order) instead of three:
+//   * forward: 64 W_hh weights per lane in registers, the same {value, tag} exchange of h (one memory round
+//     trip per step); c_t never leaves the lane that owns its (unit, batch) slot, so it needs no exchange.
+//     Both h_{t-1} and c_{t-1} are multiplied by masks[t] before step t.
+//   * backward: the producer multiplies its 64 resident gate rows with its own gate gradients and publishes the
+//     partial sums of dh_{t-1} (gru_bwd8's ring); the dc recursion dc_{t-1} = dc_t f_t mask_t stays in the owning
+//     thread.  For an LSTM the gradients of gi and of W_hh h + b_hh are the same tensor: one output, dgates.
+// Status bits 32 (forward) and 64 (backward).
+namespace {
+
+struct LstmStateFwdArgs {
+  const float* gi;     // [T][N][4H]  x W_ih^T + b_ih
+  const float* whh;    // [4H][H]
+  const float* bhh;    // [4H]
+  const float* h0;     // [N][H]
+  const float* c0;     // [N][H]
+  const float* masks;  // [T][N]
+  float* y;            // [T][N][H]   h_t
+  float* cT;           // [N][H]      c_{T-1}
+  float* sg;           // [T][N][4H]  post-activation gates i, f, g, o
+  float* sc;           // [T][N][H]   c_t
+  unsigned* sync;      // [1] error word (zeroed by the launcher)
+  unsigned long long* xh;  // exchange [T][NWG][NB][UNITS_WG] of {value, tag} words, each written once per launch
+  int T, N;
+  unsigned tagbase;
+  unsigned* status;
+  unsigned spin;
+};
+
+__device__ __forceinline__ void lstm_state_fwd_fail(const LstmStateFwdArgs& a) {
+  rnn_fail(a.status, 32u);
+  rnn_poison(a.y, (size_t)a.T * a.N, H, blockIdx.x * UNITS_WG, UNITS_WG);
+  rnn_poison(a.cT, (size_t)a.N, H, blockIdx.x * UNITS_WG, UNITS_WG);
+}
+
+// Layout as gru_fwd8_kernel: waves w and w + 4 share the 4 units of wave w and split K; after the halving butterfly the even lane
+// of a (unit, batch) pair holds the i and f sums, the odd lane g and o.
+__global__ __launch_bounds__(512) void lstm_state_fwd8_kernel(LstmStateFwdArgs a) {
+  __shared__ __attribute__((aligned(16))) float hs[2][NB][H];   // masked h_{t-1}, double-buffered by step parity
+  __shared__ float part[WAVES][64][2];                          // the upper K half's two sums per lane
+  const int tid = threadIdx.x, lane = tid & 63, wave8 = tid >> 6;
+  const int wave = wave8 & 3, q = wave8 >> 2;
+  const int grp = lane >> 4, kl = lane & 15;
+  const int my_unit = blockIdx.x * UNITS_WG + wave * UNITS_WAVE + grp;
+  float w[4][16];
+#pragma unroll
+  for (int g = 0; g < 4; ++g)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      f32x4 v = *reinterpret_cast<const f32x4*>(a.whh + (size_t)(g * H + my_unit) * H + 64 * (4 * q + j) + 4 * kl);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) w[g][4 * j + e] = v[e];
+    }
+  const int my_b = kl >> 1;
+  const bool worker = (q == 0) && ((kl & 1) == 0) && (my_b < a.N);
+  const float bi = a.bhh[my_unit], bf = a.bhh[H + my_unit], bg = a.bhh[2 * H + my_unit], bo = a.bhh[3 * H + my_unit];
+  float c = worker ? a.c0[(size_t)my_b * H + my_unit] : 0.f;
+  const int sw = tid >> 4, sb = (tid >> 1) & 7, sh = tid & 1;
+  const int xw = (blockIdx.x * NB + my_b) * UNITS_WG + wave * UNITS_WAVE + grp;
+  for (int t = 0; t < a.T; ++t) {
+    float (*hcur)[H] = hs[t & 1];
+    float xi = 0.f, xf = 0.f, xg = 0.f, xo = 0.f, mk = 0.f;
+    const size_t orow = (size_t)t * a.N + my_b;
+    if (worker) {
+      const float* g = a.gi + orow * 4 * H;
+      xi = g[my_unit]; xf = g[H + my_unit]; xg = g[2 * H + my_unit]; xo = g[3 * H + my_unit];
+      mk = a.masks[t * a.N + my_b];
+    }
+    {
+      float row[8];
+      bool good = true;
+      if (sb >= a.N) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) row[i] = 0.f;
+      } else if (t == 0) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          f32x4 v = *reinterpret_cast<const f32x4*>(a.h0 + (size_t)sb * H + sw * UNITS_WG + 8 * sh + 4 * i);
+          row[4 * i] = v[0]; row[4 * i + 1] = v[1]; row[4 * i + 2] = v[2]; row[4 * i + 3] = v[3];
+        }
+      } else {
+        const unsigned long long* src = a.xh + ((size_t)(t - 1) * NWG + sw) * NB * UNITS_WG + sb * UNITS_WG + 8 * sh;
+        good = poll_row8(src, a.tagbase | (unsigned)t, a.sync, row, a.spin);
+      }
+      const float sm = sb < a.N ? a.masks[t * a.N + sb] : 0.f;
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        f32x4 v = {row[4 * i] * sm, row[4 * i + 1] * sm, row[4 * i + 2] * sm, row[4 * i + 3] * sm};
+        *reinterpret_cast<f32x4*>(&hcur[sb][sw * UNITS_WG + 8 * sh + 4 * i]) = v;
+      }
+      if (__syncthreads_or(good ? 0 : 1)) {   // timeout or error elsewhere: every thread leaves
+        lstm_state_fwd_fail(a);
+        return;
+      }
+    }
+    float acc[32];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+      float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+      if (b < a.N) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const f32x4 hv = *reinterpret_cast<const f32x4*>(&hcur[b][64 * (4 * q + j) + 4 * kl]);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            s0 = fmaf(w[0][4 * j + e], hv[e], s0);
+            s1 = fmaf(w[1][4 * j + e], hv[e], s1);
+            s2 = fmaf(w[2][4 * j + e], hv[e], s2);
+            s3 = fmaf(w[3][4 * j + e], hv[e], s3);
+          }
+        }
+      }
+      acc[4 * b] = s0; acc[4 * b + 1] = s1; acc[4 * b + 2] = s2; acc[4 * b + 3] = s3;
+    }
+    halve_row<32, 8>(acc, lane);
+    halve_row<16, 4>(acc, lane);
+    halve_row<8, 2>(acc, lane);
+    halve_row<4, 1>(acc, lane);
+    if (q == 1) { part[wave][lane][0] = acc[0]; part[wave][lane][1] = acc[1]; }
+    __syncthreads();
+    if (q == 0) { acc[0] += part[wave][lane][0]; acc[1] += part[wave][lane][1]; }
+    const float gsum = row_xor<1>(acc[0]), osum = row_xor<1>(acc[1]);   // the odd lane's sums: g and o gates of the same batch
+    if (worker) {
+      const float ig = sigmoidf_(xi + (acc[0] + bi));
+      const float fg = sigmoidf_(xf + (acc[1] + bf));
+      const float gg = tanhf(xg + (gsum + bg));
+      const float og = sigmoidf_(xo + (osum + bo));
+      c = fg * (c * mk) + ig * gg;
+      const float h = og * tanhf(c);
+      if (t + 1 < a.T)
+        __hip_atomic_store(a.xh + (size_t)t * NWG * NB * UNITS_WG + xw,
+                           ((unsigned long long)(a.tagbase | (unsigned)(t + 1)) << 32) | __float_as_uint(h),
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      a.y[orow * H + my_unit] = h;
+      float* sg = a.sg + orow * 4 * H + my_unit;
+      sg[0] = ig; sg[H] = fg; sg[2 * H] = gg; sg[3 * H] = og;
+      a.sc[orow * H + my_unit] = c;
+      if (t + 1 == a.T) a.cT[(size_t)my_b * H + my_unit] = c;
+    }
+  }
+}
+
+struct LstmStateBwdArgs {
+  const float* dy;     // [T][N][H]   gradient w.r.t. every h_t
+  const float* dhT;    // [N][H] gradient w.r.t. the final h, or null
+  const float* dcT;    // [N][H] gradient w.r.t. the final c, or null
+  const float* whh;    // [4H][H]
+  const float* c0;     // [N][H]
+  const float* masks;  // [T][N]
+  const float* sg;     // [T][N][4H]
+  const float* sc;     // [T][N][H]
+  float* dg;           // [T][N][4H]  gradient of the gate pre-activations (= d gi = d (W_hh h + b_hh))
+  float* dh0;          // [N][H]
+  float* dc0;          // [N][H]
+  unsigned* sync;
+  unsigned long long* xp;  // exchange ring as gru_bwd8_kernel's
+  int T, N;
+  unsigned tagbase;
+  unsigned* status;
+  unsigned spin;
+};
+
+__device__ __forceinline__ void lstm_state_bwd_fail(const LstmStateBwdArgs& a) {
+  rnn_fail(a.status, 64u);
+  for (int g = 0; g < 4; ++g) rnn_poison(a.dg, (size_t)a.T * a.N, 4 * H, g * H + blockIdx.x * UNITS_WG, UNITS_WG);
+  rnn_poison(a.dh0, (size_t)a.N, H, blockIdx.x * UNITS_WG, UNITS_WG);
+  rnn_poison(a.dc0, (size_t)a.N, H, blockIdx.x * UNITS_WG, UNITS_WG);
+}
+
+// Layout as gru_bwd8_kernel: thread pair (tid, tid + 256) owns columns k = 2 c, 2 c + 1 and splits the 64 gate rows of the
+// workgroup's 16 units: half q multiplies rows 32 q .. 32 q + 31 (i, f of the 16 units for q = 0; g, o for q = 1).
+__global__ __launch_bounds__(512) void lstm_state_bwd8_kernel(LstmStateBwdArgs a) {
+  __shared__ __attribute__((aligned(16))) float part[NWG][NB][UNITS_WG];   // the 32 producers' partial sums for my units
+  __shared__ __attribute__((aligned(16))) float dgs[4 * UNITS_WG][NB];     // my gate gradients of this step: rows i, f, g, o
+  __shared__ __attribute__((aligned(16))) float swp[2][256][8];            // swp[q][c]: what half q hands to the other half
+  const int tid = threadIdx.x;
+  const int c = tid & 255, q = tid >> 8;
+  f32x2 w[32];
+#pragma unroll
+  for (int i = 0; i < 32; ++i) {
+    const int rw = 32 * q + i, g = rw / UNITS_WG, u = rw - g * UNITS_WG;
+    w[i] = *reinterpret_cast<const f32x2*>(a.whh + (size_t)(g * H + blockIdx.x * UNITS_WG + u) * H + 2 * c);
+  }
+  const int wu = tid & 15, wb = tid >> 4;
+  const bool worker = tid < 128 && wb < a.N;
+  const int my_unit = blockIdx.x * UNITS_WG + wu;
+  const int pq = tid >> 4, pb = (tid >> 1) & 7, ph = tid & 1;
+  const size_t pub = ((size_t)(c >> 3) * NWG + blockIdx.x) * NB * UNITS_WG + ((2 * c) & 15);
+
+  float mk_next = 0.f, dc_carry = 0.f;   // dc_carry: gradient reaching c_t from step t + 1 (already times f_{t+1} mask_{t+1})
+  if (worker && a.dcT) dc_carry = a.dcT[(size_t)wb * H + my_unit];
+  for (int t = a.T - 1; t >= -1; --t) {
+    float dyv = 0.f, ig = 0.f, fg = 0.f, gg = 0.f, og = 0.f, ct = 0.f, cprev = 0.f, mk = 0.f;
+    size_t row = 0;
+    if (worker && t >= 0) {
+      row = (size_t)t * a.N + wb;
+      const size_t o = row * H + my_unit;
+      mk = a.masks[t * a.N + wb];
+      const float* csrc = (t == 0) ? a.c0 : a.sc + (size_t)(t - 1) * a.N * H;
+      cprev = csrc[(size_t)wb * H + my_unit] * mk;
+      dyv = a.dy[o];
+      const float* sg = a.sg + row * 4 * H + my_unit;
+      ig = sg[0]; fg = sg[H]; gg = sg[2 * H]; og = sg[3 * H];
+      ct = a.sc[o];
+    }
+    float carry = 0.f;
+    if (t == a.T - 1) {
+      if (worker && a.dhT) carry = a.dhT[(size_t)wb * H + my_unit];
+    } else {
+      bool good = true;
+      if (pb < a.N) {
+        float rowv[8];
+        const unsigned long long* src = a.xp + (size_t)((t + 1) % BWD_RING) * XP_SLOT + (size_t)blockIdx.x * XP_CONSUMER +
+                                        ((size_t)pq * NB + pb) * UNITS_WG + 8 * ph;
+        good = poll_row8(src, a.tagbase | (unsigned)(t + 2), a.sync, rowv, a.spin);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          f32x4 v = {rowv[4 * i], rowv[4 * i + 1], rowv[4 * i + 2], rowv[4 * i + 3]};
+          *reinterpret_cast<f32x4*>(&part[pq][pb][8 * ph + 4 * i]) = v;
+        }
+      }
+      if (__syncthreads_or(good ? 0 : 1)) {   // timeout or error elsewhere: every thread leaves
+        lstm_state_bwd_fail(a);
+        return;
+      }
+      if (worker) {
+        float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+        for (int p2 = 0; p2 < NWG; p2 += 2) { s0 += part[p2][wb][wu]; s1 += part[p2 + 1][wb][wu]; }
+        carry = (s0 + s1) * mk_next;
+      }
+    }
+    if (t < 0) {
+      if (worker) {
+        a.dh0[(size_t)wb * H + my_unit] = carry;
+        a.dc0[(size_t)wb * H + my_unit] = dc_carry;
+      }
+      break;
+    }
+    if (tid < 128) {
+      float di = 0.f, df = 0.f, dgg = 0.f, dout = 0.f;
+      if (worker) {
+        const float dh = dyv + carry;
+        const float tc = tanhf(ct);
+        dout = dh * tc * og * (1.0f - og);
+        const float dc = dh * og * (1.0f - tc * tc) + dc_carry;
+        di = dc * gg * ig * (1.0f - ig);
+        df = dc * cprev * fg * (1.0f - fg);
+        dgg = dc * ig * (1.0f - gg * gg);
+        float* dgp = a.dg + row * 4 * H + my_unit;
+        dgp[0] = di; dgp[H] = df; dgp[2 * H] = dgg; dgp[3 * H] = dout;
+        dc_carry = dc * fg * mk;
+        mk_next = mk;
+      }
+      dgs[wu][wb] = di; dgs[UNITS_WG + wu][wb] = df; dgs[2 * UNITS_WG + wu][wb] = dgg; dgs[3 * UNITS_WG + wu][wb] = dout;   // zeros for unused slots
+    }
+    __syncthreads();   // dgs complete; also: every read of part[] / swp[] of the previous step is done
+    float acc0[NB], acc1[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) { acc0[b] = 0.f; acc1[b] = 0.f; }
+    const unsigned dgs_addr = (unsigned)(size_t)&dgs[0][0] + (unsigned)(32 * q * NB * 4);     // this half's 32 rows
+#pragma unroll
+    for (int c8 = 0; c8 < 32; c8 += 8) {
+      f32x4 d[16];
+      asm volatile("" :: "v"(acc0[0]), "v"(acc0[1]), "v"(acc0[2]), "v"(acc0[3]), "v"(acc0[4]), "v"(acc0[5]), "v"(acc0[6]), "v"(acc0[7]),
+                         "v"(acc1[0]), "v"(acc1[1]), "v"(acc1[2]), "v"(acc1[3]), "v"(acc1[4]), "v"(acc1[5]), "v"(acc1[6]), "v"(acc1[7]));
+#pragma unroll
+      for (int i = 0; i < 16; ++i)
+        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d[i]) : "v"(dgs_addr), "n"((c8 * NB + 4 * i) * 4) : "memory");
+      asm volatile("s_waitcnt lgkmcnt(0)"
+                   : "+v"(d[0]), "+v"(d[1]), "+v"(d[2]), "+v"(d[3]), "+v"(d[4]), "+v"(d[5]), "+v"(d[6]), "+v"(d[7]),
+                     "+v"(d[8]), "+v"(d[9]), "+v"(d[10]), "+v"(d[11]), "+v"(d[12]), "+v"(d[13]), "+v"(d[14]), "+v"(d[15]));
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int rw = c8 + i;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          acc0[b] = fmaf(w[rw][0], d[2 * i][b], acc0[b]);             acc1[b] = fmaf(w[rw][1], d[2 * i][b], acc1[b]);
+          acc0[4 + b] = fmaf(w[rw][0], d[2 * i + 1][b], acc0[4 + b]); acc1[4 + b] = fmaf(w[rw][1], d[2 * i + 1][b], acc1[4 + b]);
+        }
+      }
+    }
+    {
+      const int give = 4 * (1 - q);
+      f32x4 g0 = {acc0[give], acc0[give + 1], acc0[give + 2], acc0[give + 3]};
+      f32x4 g1 = {acc1[give], acc1[give + 1], acc1[give + 2], acc1[give + 3]};
+      *reinterpret_cast<f32x4*>(&swp[q][c][0]) = g0;
+      *reinterpret_cast<f32x4*>(&swp[q][c][4]) = g1;
+    }
+    __syncthreads();
+    const f32x4 o0 = *reinterpret_cast<const f32x4*>(&swp[1 - q][c][0]), o1 = *reinterpret_cast<const f32x4*>(&swp[1 - q][c][4]);
+    unsigned long long* dst = a.xp + (size_t)(t % BWD_RING) * XP_SLOT + pub;
+    const unsigned long long tag = (unsigned long long)(a.tagbase | (unsigned)(t + 1)) << 32;
+#pragma unroll
+    for (int bb = 0; bb < 4; ++bb) {
+      const int b = 4 * q + bb;
+      if (b < a.N) {
+        const float v0 = q == 0 ? acc0[b] + o0[bb] : o0[bb] + acc0[b];
+        const float v1 = q == 0 ? acc1[b] + o1[bb] : o1[bb] + acc1[b];
+        __hip_atomic_store(dst + b * UNITS_WG, tag | __float_as_uint(v0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(dst + b * UNITS_WG + 1, tag | __float_as_uint(v1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+  }
+}
+
+}  // namespace
+
+// same exchange image / ring as the GRU kernels: the h values crossing workgroups per step are the same 4096 words
+extern "C" int64_t wsmg_lstm_state_workspace_bytes(int T) { return wsmg_gru_workspace_bytes(T); }
+
+extern "C" int wsmg_lstm_state_fwd(const float* gi, const float* w_hh, const float* b_hh, const float* h0, const float* c0,
+                                   const float* masks, int T, int N, int hidden, float* y, float* c_T, float* save_gates,
+                                   float* save_c, void* sync_ws, wsmg_stream_t stream) {
+  if (hidden != H || T <= 0 || N <= 0 || N > NB) return WSMG_EINVAL;
+  if (((uintptr_t)sync_ws & 127) != 0) return WSMG_EINVAL;
+  if (T > 1023) return WSMG_EINVAL;
+  hipStream_t s = wsmg_s(stream);
+  hipError_t e = hipMemsetAsync(sync_ws, 0, 256 + (size_t)T * NWG * NB * UNITS_WG * 8, s);   // as wsmg_gru_fwd
+  if (e != hipSuccess) return (int)e;
+  LstmStateFwdArgs a{gi, w_hh, b_hh, h0, c0, masks, y, c_T, save_gates, save_c, (unsigned*)sync_ws,
+                     (unsigned long long*)((char*)sync_ws + 256), T, N, next_tagbase(), rnn_status_dev(), g_spin};
+  hipLaunchKernelGGL(lstm_state_fwd8_kernel, dim3(NWG), dim3(512), 0, s, a);
+  WSMG_RETURN_LAUNCH();
+}
+
+extern "C" int wsmg_lstm_state_bwd(const float* dy, const float* dhT, const float* dcT, const float* w_hh, const float* c0,
+                                   const float* masks, const float* save_gates, const float* save_c, int T, int N, int hidden,
+                                   float* dgates, float* dh0, float* dc0, void* sync_ws, wsmg_stream_t stream) {
+  if (hidden != H || T <= 0 || N <= 0 || N > NB) return WSMG_EINVAL;
+  if (((uintptr_t)sync_ws & 127) != 0) return WSMG_EINVAL;
+  if (T > 1023) return WSMG_EINVAL;
+  hipStream_t s = wsmg_s(stream);
+  hipError_t e = hipMemsetAsync(sync_ws, 0, 256 + (size_t)BWD_RING * XP_SLOT * 8, s);   // as wsmg_gru_bwd
+  if (e != hipSuccess) return (int)e;
+  LstmStateBwdArgs a{dy, dhT, dcT, w_hh, c0, masks, save_gates, save_c, dgates, dh0, dc0, (unsigned*)sync_ws,
+                     (unsigned long long*)((char*)sync_ws + 256), T, N, next_tagbase(), rnn_status_dev(), g_spin};
+  hipLaunchKernelGGL(lstm_state_bwd8_kernel, dim3(NWG), dim3(512), 0, s, a);
+  WSMG_RETURN_LAUNCH();
+}
+
+// =================================================================================================
 // Persistent packed bidirectional LSTM (instruction encoder, hidden 128 per direction, U <= 8 unique
 // instructions per launch).  Replaces the cuDNN/MIOpen packed-sequence LSTM behind nn.LSTM at
 // instruction_encoder.py:80-92 (about 10 tiny launches per token step and direction in MIOpen).

@@ -487,6 +487,8 @@ class MGMapNet(nn.Module):
         n1 = self.state_encoder.num_recurrent_layers
         ops.mark("state_in", state_in)
         n_env = rnn_hidden_states.size(1)
+        # The pipelined / chained recurrent core is GRU-only: `n1 == 1` and the 2-layer state exclude an LSTM state encoder
+        # (habitat's [h; c] layout: n1 == 2, 4 layers), which takes the staged route below whatever recurrent_chunks says.
         if (self.recurrent_chunks > 0 and not ops.ranks_share_gpu() and torch.is_grad_enabled() and not rows and "map" in self._inputs and n1 == 1
                 and rnn_hidden_states.size(0) == 2 and recurrent.usable(state_in, map_tokens, n_env, text)):
             # GRU 1 -> text attention -> map attention -> compress -> GRU 2 as one autograd node, pipelined over time chunks on three

@@ -4,7 +4,7 @@ operator family (round 4: the 1 981-line ops.py, split) —
     core       argument checks, pointers / streams, live kernel timing, section marks, per-pass state, stream joins
     conv       the map stack's convolutions (operator 2)            norm    BatchNorm / GroupNorm / channel sums
     nhwc       ReLU, pools, upsampling, layout changes, concatenation   attention   operator 3 (+ e4m3 forms)
-    heads      fused losses and heads                                rnn     persistent GRU / bi-LSTM
+    heads      fused losses and heads                                rnn     persistent GRU / LSTM / bi-LSTM
     bev        operator 1
 
 PyTorch is used only for device memory, streams and the autograd tape; every FLOP of the three named operators runs in the

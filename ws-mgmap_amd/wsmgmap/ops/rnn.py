@@ -1,4 +1,4 @@
-"""wsmgmap.ops.rnn — the persistent masked-GRU and packed bi-LSTM sequence kernels.
+"""wsmgmap.ops.rnn — the persistent masked-GRU / masked-LSTM state-encoder and packed bi-LSTM sequence kernels.
 """
 import ctypes
 
@@ -67,6 +67,55 @@ class _MaskedGRU(torch.autograd.Function):
 def masked_gru(gi, w_hh, b_hh, h0, masks):
     """Whole-sequence masked GRU in one persistent launch.  Returns y [T,N,H]; final state = y[-1]."""
     return _MaskedGRU.apply(gi.contiguous(), w_hh.contiguous(), b_hh.contiguous(), h0.contiguous(), masks.contiguous())
+
+
+class _MaskedLSTM(torch.autograd.Function):
+    """gi [T,N,4H] (input projections), w_hh [4H,H], b_hh [4H], h0, c0 [N,H], masks [T,N] -> y [T,N,H], c_T [N,H]."""
+
+    @staticmethod
+    def forward(ctx, gi, w_hh, b_hh, h0, c0, masks):
+        _req(gi, w_hh, b_hh, h0, c0, masks)
+        _f32(gi, w_hh, b_hh, h0, c0, masks)
+        T, N, H4 = gi.shape
+        H = H4 // 4
+        dev = gi.device
+        y = torch.empty(T, N, H, device=dev, dtype=torch.float32)
+        c_t = torch.empty(N, H, device=dev, dtype=torch.float32)
+        sg = torch.empty(T, N, 4 * H, device=dev, dtype=torch.float32)
+        sc = torch.empty(T, N, H, device=dev, dtype=torch.float32)
+        sync = _rnn_workspace(_abi.lib().wsmg_lstm_state_workspace_bytes(T), dev)
+        _abi.call("wsmg_lstm_state_fwd", _p(gi), _p(w_hh), _p(b_hh), _p(h0), _p(c0), _p(masks), T, N, H, _p(y), _p(c_t),
+                  _p(sg), _p(sc), _p(sync), _stream())
+        _rnn_launched()
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(w_hh, h0, c0, masks, y, sg, sc)
+        return y, c_t
+
+    @staticmethod
+    def backward(ctx, dy, dc_t):
+        w_hh, h0, c0, masks, y, sg, sc = ctx.saved_tensors
+        T, N, H = y.shape
+        dev = y.device
+        dy = torch.zeros_like(y) if dy is None else dy.contiguous()
+        dgates = torch.empty(T, N, 4 * H, device=dev, dtype=torch.float32)
+        dh0 = torch.empty(N, H, device=dev, dtype=torch.float32)
+        dc0 = torch.empty(N, H, device=dev, dtype=torch.float32)
+        sync = _rnn_workspace(_abi.lib().wsmg_lstm_state_workspace_bytes(T), dev)
+        _abi.call("wsmg_lstm_state_bwd", _p(dy), None, None if dc_t is None else _p(dc_t.contiguous()), _p(w_hh), _p(c0),
+                  _p(masks), _p(sg), _p(sc), T, N, H, _p(dgates), _p(dh0), _p(dc0), _p(sync), _stream())
+        _rnn_launched()
+        hprev = torch.cat([h0.unsqueeze(0), y[:-1]], dim=0) * masks.unsqueeze(-1)
+        g2 = dgates.view(T * N, 4 * H)
+        dw_hh = g2.t() @ hprev.view(T * N, H)
+        db_hh = g2.sum(dim=0)
+        return dgates, dw_hh, db_hh, dh0, dc0, None
+
+
+def masked_lstm(gi, w_hh, b_hh, h0, c0, masks):
+    """Whole-sequence masked LSTM (habitat RNNStateEncoder semantics: h and c times masks[t] before step t) in one persistent
+    launch.  Returns (y [T,N,H], c_T [N,H]); the final h = y[-1]."""
+    return _MaskedLSTM.apply(gi.contiguous(), w_hh.contiguous(), b_hh.contiguous(), h0.contiguous(), c0.contiguous(),
+                             masks.contiguous())
 
 
 # ----------------------------------------------------------------------------- persistent packed bi-LSTM
