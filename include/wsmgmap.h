@@ -580,6 +580,27 @@ int wsmg_lstm_bwd(const float* dout, const float* w_hh, const int32_t* lengths, 
                   const float* save_c, int U, int L, int hidden, float* dgates, void* state_ws,
                   wsmg_stream_t stream);
 
+/* The other instruction encoders the policy admits (output width 256; instruction_encoder.py:80-93 with
+ * MODEL.INSTRUCTION_ENCODER.rnn_type / .bidirectional / .hidden_size): cell WSMG_CELL_LSTM or WSMG_CELL_GRU (gate order
+ * r, z, n; n = tanh(gi_n + r (W_hn h + b_hn))) at (hidden 128, dirs 2) or (hidden 256, dirs 1); any other combination,
+ * U > 8 or L <= 0 returns WSMG_EINVAL before anything is enqueued.  Semantics and layouts as wsmg_lstm_fwd / _bwd with G = 4
+ * (LSTM) or 3 (GRU) gate rows per unit: gi [U][L][dirs][G H]; w_hh [dirs][G H][H]; b_hh [dirs][G H]; out [U][L][dirs H];
+ * save_gates [dirs][U][L][4][H] (LSTM i, f, g, o; GRU r, z, n, W_hn h + b_hn); save_c [dirs][U][L][H] (LSTM only, may be
+ * NULL for the GRU).  (LSTM, 128, 2) runs wsmg_lstm_fwd / _bwd.  state_ws: wsmg_instr_rnn_workspace_bytes(cell, hidden,
+ * dirs, L) bytes of 128-B-aligned device scratch (0 for an unsupported combination). */
+#define WSMG_CELL_LSTM 0
+#define WSMG_CELL_GRU 1
+int64_t wsmg_instr_rnn_workspace_bytes(int cell, int hidden, int dirs, int L);
+int wsmg_instr_rnn_fwd(int cell, const float* gi, const float* w_hh, const float* b_hh, const int32_t* lengths, int U, int L,
+                       int hidden, int dirs, float* out, float* save_gates, float* save_c, void* state_ws,
+                       wsmg_stream_t stream);
+/* backward through time: dout [U][L][dirs H] and the forward's out / save_gates / save_c -> dgi [U][L][dirs][G H] (gradient
+ * of gi) and, for the GRU, dgh (gradient of W_hh h + b_hh: its n rows are r times dgi's); the LSTM's dgh equals dgi and may
+ * be NULL.  out is read by the GRU only (the state before each step). */
+int wsmg_instr_rnn_bwd(int cell, const float* dout, const float* w_hh, const int32_t* lengths, const float* out,
+                       const float* save_gates, const float* save_c, int U, int L, int hidden, int dirs, float* dgi,
+                       float* dgh, void* state_ws, wsmg_stream_t stream);
+
 /* ============================ GroupNorm (frozen DD-PPO depth backbone, rollout path) ============================ */
 /* nn.GroupNorm(G, C) [+ residual] [+ ReLU] on NHWC activations, inference only: x [B][HW][C] float32 (x_f32 = 1: the
  * convolution's float32 accumulators, stored unrounded) or bf16; y, residual [B][HW][C] bf16; gamma, beta [C]; statistics
@@ -598,6 +619,8 @@ int wsmg_group_norm_nhwc_bf16(const void* x, int x_f32, const void* residual, co
  * wsmg_rnn_debug_spin_limit(n): bound every spin by n polls (0 = default, 2^20) — test hook to force a timeout.
  * Bit 16 (round 6): the grid barrier of wsmg_attn_fp8_mfma_fused timed out (its outputs are NaN).
  * Bits 32 and 64: wsmg_lstm_state_fwd / wsmg_lstm_state_bwd timed out (y, c_T / dgates, dh0, dc0 are NaN).
+ * Bits 128 and 256: wsmg_instr_rnn_fwd / wsmg_instr_rnn_bwd timed out in their GRU / hidden-256 kernels (out / dgi, dgh
+ * are NaN; the default bidirectional LSTM reports bits 4 and 8).
  * wsmg_rnn_debug_inject(bits): OR `bits` into the word as a timed-out kernel would — test hook for the callers' error paths
  * (bench.py's in-process fallback, GradAllReducer's cross-rank agreement); returns the word after the OR. */
 int wsmg_rnn_status(int clear);

@@ -7,7 +7,7 @@ feeds them the seeded inputs of oracle/cases.py with weights from oracle/detfill
 writes small .npz fixtures (data only: inputs are re-derivable, outputs are digests /
 small tensors) to tests/golden/.
 
-    python tools/make_goldens.py [g1 g2 g3 g4 g5 ... g10]
+    python tools/make_goldens.py [g1 g2 g3 g4 g5 ... g12]
 """
 import hashlib
 import os
@@ -57,10 +57,11 @@ class _TorchProxy:
         return torch.device("cpu")
 
 
-def model_config(E=100, C=64, G=240, num_proc=2, rnn_type="GRU"):
+def model_config(E=100, C=64, G=240, num_proc=2, rnn_type="GRU", instr_rnn="LSTM", instr_bidir=True, instr_hidden=128):
     return Config(
         INSTRUCTION_ENCODER=Config(vocab_size=2504, embedding_size=50, use_pretrained_embeddings=False,
-                                   hidden_size=128, rnn_type="LSTM", final_state_only=False, bidirectional=True),
+                                   hidden_size=instr_hidden, rnn_type=instr_rnn, final_state_only=False,
+                                   bidirectional=instr_bidir),
         RGB_ENCODER=Config(output_size=256, pretrain_model="__synthetic__"),
         DEPTH_ENCODER=Config(output_size=128, ddppo_checkpoint="NONE", backbone="resnet50"),
         MAP_ENCODER=Config(ego_map_size=E, output_size=256),
@@ -73,7 +74,8 @@ def model_config(E=100, C=64, G=240, num_proc=2, rnn_type="GRU"):
     )
 
 
-def build_policy(num_proc=2, rnn_type="GRU"):
+def build_policy(num_proc=2, rnn_type="GRU", **instr):
+    """instr: the instruction encoder's instr_rnn / instr_bidir / instr_hidden (model_config)."""
     import vlnce_baselines.common.rgb_mapping as rm
     rm.torch = _TorchProxy()
     import vlnce_baselines.models.encoders.unet_encoder as ue
@@ -89,7 +91,7 @@ def build_policy(num_proc=2, rnn_type="GRU"):
     torch.load = fake_load
     try:
         obs_space = sp.Dict({"depth": sp.Box(shape=(256, 256, 1)), "rgb": sp.Box(shape=(224, 224, 3))})
-        pol = BasePolicy(obs_space, sp.Box(shape=(2,)), model_config(num_proc=num_proc, rnn_type=rnn_type))
+        pol = BasePolicy(obs_space, sp.Box(shape=(2,)), model_config(num_proc=num_proc, rnn_type=rnn_type, **instr))
     finally:
         torch.load = real_load
     sd = pol.state_dict()
@@ -171,11 +173,11 @@ def g3():
     np.savez_compressed(os.path.join(OUT, "g3_update.npz"), **out)
 
 
-def _update_golden(rnn_type="GRU", restarts=()):
+def _update_golden(rnn_type="GRU", restarts=(), **instr):
     """One teacher-forcing update of the reference policy (T = 4, N = 2) on cases.update_inputs; `restarts`: extra (t, n)
-    episode starts set to 0 in the masks."""
+    episode starts set to 0 in the masks; `instr`: the instruction encoder's settings (model_config)."""
     from vlnce_baselines.common.aux_losses import AuxLosses
-    pol = build_policy(rnn_type=rnn_type)
+    pol = build_policy(rnn_type=rnn_type, **instr)
     pol.train()
     pol.net.depth_encoder.eval()
     pol.net.rgb_encoder.eval()
@@ -245,6 +247,10 @@ def _update_golden(rnn_type="GRU", restarts=()):
         for k, v in pol.state_dict().items():
             if "state_encoder.rnn." in k:
                 out["shape." + k] = np.array(v.shape, np.int64)
+    if instr:
+        for k, v in pol.state_dict().items():
+            if "instruction_encoder.encoder_rnn." in k:
+                out["shape." + k] = np.array(v.shape, np.int64)
     return out
 
 
@@ -256,6 +262,22 @@ def g10():
     print("g10 pred", out["pred"].ravel()[:4], "aux", float(out["aux_loss"]), "loss", float(out["loss"]),
           "h_out", out["h_out"].shape)
     np.savez_compressed(os.path.join(OUT, "g10_lstm_update.npz"), **out)
+
+
+# ============================================================================= G11 / G12
+def g11():
+    """g3 with a bidirectional GRU instruction encoder (MODEL.INSTRUCTION_ENCODER.rnn_type = "GRU", hidden 128); the
+    reference's encoder_rnn.* shapes are stored too."""
+    out = _update_golden(instr_rnn="GRU", instr_bidir=True, instr_hidden=128)
+    print("g11 pred", out["pred"].ravel()[:4], "aux", float(out["aux_loss"]), "loss", float(out["loss"]))
+    np.savez_compressed(os.path.join(OUT, "g11_gru_instr_update.npz"), **out)
+
+
+def g12():
+    """g3 with a unidirectional LSTM instruction encoder (bidirectional = False, hidden 256: the same output width)."""
+    out = _update_golden(instr_rnn="LSTM", instr_bidir=False, instr_hidden=256)
+    print("g12 pred", out["pred"].ravel()[:4], "aux", float(out["aux_loss"]), "loss", float(out["loss"]))
+    np.savez_compressed(os.path.join(OUT, "g12_unilstm_instr_update.npz"), **out)
 
 
 # ============================================================================= G4
@@ -415,6 +437,6 @@ def g8():
 
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["shapes", "g1", "g2", "g3", "g4", "g5", "g5f", "g8", "g9", "g10"]
+    which = sys.argv[1:] or ["shapes", "g1", "g2", "g3", "g4", "g5", "g5f", "g8", "g9", "g10", "g11", "g12"]
     for w in which:
         globals()[w]()

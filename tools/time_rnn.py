@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""GPU-box tool: per-kernel time of the persistent GRU / LSTM-state / bi-LSTM launches, and of the LSTM state encoder's stock
-route for contrast (HIP events, no other load)."""
+"""GPU-box tool: per-kernel time of the persistent GRU / LSTM-state / bi-LSTM / instruction GRU-LSTM launches, and of the
+stock routes of the LSTM state encoder and of the instruction encoders for contrast (HIP events, no other load)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "ws-mgmap_amd"))
@@ -61,3 +61,29 @@ def lfb():
     o = ops.bilstm(lgi, lw, lb, lens); (o * lgy).sum().backward()
 tlfb = timeit(lfb)
 print(f"LSTM L={Lt} U={U}: fwd (op) {tlf:.1f} us  fwd+bwd (op) {tlfb:.1f} us")
+# instruction encoders (INSTRUCTION_ENCODER.rnn_type / .bidirectional / .hidden_size): per row and U in (1, 8), the kernel pair
+# alone (wsmg_instr_rnn_fwd / _bwd; the default bi-LSTM through the same entry points) and the stock packed MIOpen route
+from wsmgmap.models.encoders.instruction_encoder import InstructionEncoder
+from wsmgmap.config import default_model_config
+for cell, D, Hh in (("LSTM", 2, 128), ("GRU", 2, 128), ("LSTM", 1, 256), ("GRU", 1, 256)):
+    G, code = (4 if cell == "LSTM" else 3), ops.CELLS[cell]
+    for U in (1, 8):
+        igi = torch.randn(U, Lt, D, G * Hh, device="cuda"); iw = torch.randn(D, G * Hh, Hh, device="cuda") * Hh ** -0.5
+        ib = torch.randn(D, G * Hh, device="cuda") * 0.1; ilen = torch.full((U,), Lt, device="cuda", dtype=torch.int32)
+        iout = torch.empty(U, Lt, D * Hh, device="cuda"); isg = torch.empty(D, U, Lt, 4, Hh, device="cuda")
+        isc = torch.empty(D, U, Lt, Hh, device="cuda"); idgi = torch.empty_like(igi); idgh = torch.empty_like(igi)
+        iws = ops._rnn_workspace(L.wsmg_instr_rnn_workspace_bytes(code, Hh, D, Lt), igi.device)
+        def ifwd(): _abi.call("wsmg_instr_rnn_fwd", code, P(igi), P(iw), P(ib), P(ilen), U, Lt, Hh, D, P(iout), P(isg), P(isc), P(iws), st())
+        def ibwd(): _abi.call("wsmg_instr_rnn_bwd", code, P(iout), P(iw), P(ilen), P(iout), P(isg), P(isc), U, Lt, Hh, D, P(idgi), P(idgh), P(iws), st())
+        tif, tib = timeit(ifwd), timeit(ibwd)
+        cfg = default_model_config().INSTRUCTION_ENCODER
+        cfg.rnn_type, cfg.bidirectional, cfg.hidden_size = cell, D == 2, Hh
+        enc = InstructionEncoder(cfg).cuda()
+        tok = torch.randint(1, 2504, (U, Lt), device="cuda")
+        dd = enc.dedup(tok, reuse=False)
+        egy = torch.randn(U, Lt, 256, device="cuda")
+        def kr(): (enc.encode_unique(tok, dedup=dd)[0] * egy).sum().backward()
+        def sr(): (enc.encode_unique(tok, stock=True, dedup=dd)[0] * egy).sum().backward()
+        tk, ts = timeit(kr), timeit(sr)
+        print(f"instr {cell} dirs={D} H={Hh} U={U} L={Lt}: kernel fwd {tif:.1f} us ({tif / Lt:.2f} us/step)  bwd {tib:.1f} us "
+              f"({tib / Lt:.2f} us/step) | encoder fwd+bwd: kernel route {tk:.1f} us, stock packed route {ts:.1f} us")

@@ -580,7 +580,7 @@ __global__ __launch_bounds__(512) void gru_bwd8_kernel(GruBwdArgs a) {
 // ownership").  (The claim itself, and its two attribute calls per launch, were removed in round 4.)
 // launch-unique tag bits for the flag-in-data exchange (22-bit epoch above the 10-bit step number)
 // Process-wide status word of the persistent kernels in host-mapped pinned memory: bit 0 gru_fwd, 1 gru_bwd, 2 lstm_fwd,
-// 3 lstm_bwd timed out.  The host polls it without synchronising (wsmg_rnn_status).
+// 3 lstm_bwd timed out (bit 4 wsmg_attn_fp8_mfma_fused, 5 lstm_state_fwd, 6 lstm_state_bwd, 7 instr_rnn_fwd, 8 instr_rnn_bwd).  The host polls it without synchronising (wsmg_rnn_status).
 static unsigned* g_status_host = nullptr;
 static unsigned* g_status_dev = nullptr;
 static unsigned g_spin = SPIN_LIMIT;
@@ -1310,5 +1310,353 @@ extern "C" int wsmg_lstm_bwd(const float* dout, const float* w_hh, const int32_t
   if (e != hipSuccess) return (int)e;
   LstmBwdArgs a{dout, w_hh, lengths, save_gates, save_c, dgates, (unsigned*)state_ws, (float*)((char*)state_ws + 256), U, L, rnn_status_dev(), g_spin};
   hipLaunchKernelGGL(lstm_bwd_kernel, dim3(2 * L_NWG), dim3(256), 0, s, a);
+  WSMG_RETURN_LAUNCH();
+}
+
+// =================================================================================================
+// Persistent packed instruction recurrences for the other three MODEL.INSTRUCTION_ENCODER settings the policy admits
+// (output width 256): GRU bidirectional hidden 128, LSTM unidirectional hidden 256, GRU unidirectional hidden 256.
+// The default bidirectional LSTM keeps lstm_fwd_kernel / lstm_bwd_kernel above, untouched.  Same structure: 256 hidden
+// units in flight per launch (DIRS x HID), 16 workgroups x 4 waves, 4 units per wave; the K = HID reduction is split
+// over the 64 lanes (HID / 64 per lane); one bounded grid barrier per token step and direction.  Packed-sequence
+// semantics as above.  GRU: PyTorch's r, z, n with n = tanh(gi_n + r * (W_hn h + b_hn)), h' = (1 - z) n + z h; its 12
+// gate rows per wave are padded to 16 in the reduction so that the lane layout of the LSTM carries over (lanes 48-63
+// hold the empty fourth gate).  Saved for the backward: LSTM i, f, g, o and c; GRU r, z, n and W_hn h + b_hn.
+namespace {
+
+template <int CELL, int HID>
+struct IrnnShape {
+  static constexpr int G = CELL == WSMG_CELL_LSTM ? 4 : 3;   // gate rows per unit
+  static constexpr int DIRS = 256 / HID;
+  static constexpr int NWG_D = HID / UNITS_WG;               // workgroups per direction
+  static constexpr int KL = HID / 64;                        // forward: K elements per lane
+  static constexpr int E = (G * HID / 64) % 4 == 0 ? 4 : 2;  // backward: consecutive W_hh rows per lane and chunk
+  static constexpr int Q = G * HID / (64 * E);               // backward: chunks
+};
+
+struct IrnnFwdArgs {
+  const float* gi;     // [U][L][DIRS][G*HID]
+  const float* whh;    // [DIRS][G*HID][HID]
+  const float* bhh;    // [DIRS][G*HID]
+  const int* len;      // [U]
+  float* out;          // [U][L][DIRS*HID]
+  float* hs;           // exchange [DIRS][L][NWG_D][NB][UNITS_WG]
+  float* sg;           // [DIRS][U][L][4][HID]  LSTM i,f,g,o / GRU r,z,n,ghn
+  float* sc;           // [DIRS][U][L][HID]     LSTM c_t (unused for the GRU)
+  unsigned* sync;      // per direction 16 words: [0] counter, [1] error
+  int U, L;
+  unsigned* status;
+  unsigned spin;
+};
+
+template <int CELL, int HID>
+__global__ __launch_bounds__(256) void irnn_fwd_kernel(IrnnFwdArgs a) {
+  using S = IrnnShape<CELL, HID>;
+  constexpr int G = S::G, DIRS = S::DIRS, NWG_D = S::NWG_D, KL = S::KL;
+  __shared__ int ok_lds;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int dir = blockIdx.x / NWG_D;
+  const int wgi = blockIdx.x % NWG_D;
+  const int u0 = wgi * UNITS_WG + wave * UNITS_WAVE;
+  const float* whh = a.whh + (size_t)dir * G * HID * HID;
+  const float* bhh = a.bhh + dir * G * HID;
+  unsigned* sync = a.sync + dir * 16;
+  // rows r = gate*4 + unit (r >= 4G: padding, never loaded); k = KL*lane + e
+  float w[4 * G][KL];
+#pragma unroll
+  for (int r = 0; r < 4 * G; ++r) {
+    const int row = (r >> 2) * HID + u0 + (r & 3);
+#pragma unroll
+    for (int e = 0; e < KL; ++e) w[r][e] = whh[(size_t)row * HID + KL * lane + e];
+  }
+  const int my_unit = u0 + ((lane >> 2) & 3);
+  const int my_b0 = 2 * (lane & 3);
+  float bias[G];
+#pragma unroll
+  for (int g = 0; g < G; ++g) bias[g] = lane < 16 ? bhh[g * HID + my_unit] : 0.f;
+  int mylen[2] = {0, 0};
+  if (lane < 16) {
+    if (my_b0 < a.U) mylen[0] = a.len[my_b0];
+    if (my_b0 + 1 < a.U) mylen[1] = a.len[my_b0 + 1];
+  }
+  float c[2] = {0.f, 0.f};
+  float* hs = a.hs + (size_t)dir * a.L * NB * HID;      // step-indexed image [L][NWG_D][NB][UNITS_WG]
+  const int k0 = KL * lane;
+  const int xk = (k0 >> 4) * NB * UNITS_WG + (k0 & 15);                          // + b*16
+  const int xw = wgi * NB * UNITS_WG + wave * UNITS_WAVE + ((lane >> 2) & 3);    // + b*16
+
+  for (int s = 0; s < a.L; ++s) {
+    const int t = dir == 0 ? s : a.L - 1 - s;
+    const float* hprev = hs + (size_t)(s > 0 ? s - 1 : 0) * NB * HID;   // slot written in step s-1
+    float* hnext = hs + (size_t)s * NB * HID;
+    float hp[NB][KL];
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+      for (int e = 0; e < KL; ++e) hp[b][e] = s > 0 ? hprev[xk + b * UNITS_WG + e] : 0.f;   // initial state is zero
+    float acc[128];
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        float v = 0.f;
+        if (r < 4 * G) {
+          v = w[r][0] * hp[b][0];
+#pragma unroll
+          for (int e = 1; e < KL; ++e) v = fmaf(w[r][e], hp[b][e], v);
+        }
+        acc[r * 8 + b] = v;
+      }
+    halve<128, 32>(acc, lane);
+    halve<64, 16>(acc, lane);
+    halve<32, 8>(acc, lane);
+    halve<16, 4>(acc, lane);
+    halve<8, 2>(acc, lane);
+    halve<4, 1>(acc, lane);
+    float gh[G][2];
+    gh[0][0] = acc[0];
+    gh[0][1] = acc[1];
+#pragma unroll
+    for (int g = 1; g < G; ++g) {
+      gh[g][0] = __shfl(acc[0], lane + 16 * g, 64);
+      gh[g][1] = __shfl(acc[1], lane + 16 * g, 64);
+    }
+    if (lane < 16) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int b = my_b0 + i;
+        if (b < a.U) {
+          const float hold = s > 0 ? hprev[xw + b * UNITS_WG] : 0.f;
+          const bool active = t < mylen[i];
+          float hnew = hold;
+          float outv = 0.f;
+          if (active) {
+            const float* g = a.gi + (((size_t)b * a.L + t) * DIRS + dir) * G * HID + my_unit;
+            float* sgp = a.sg + ((((size_t)dir * a.U + b) * a.L + t) * 4) * HID + my_unit;
+            if constexpr (CELL == WSMG_CELL_LSTM) {
+              float gi_ = sigmoidf_(g[0] + gh[0][i] + bias[0]);
+              float gf_ = sigmoidf_(g[HID] + gh[1][i] + bias[1]);
+              float gg_ = tanhf(g[2 * HID] + gh[2][i] + bias[2]);
+              float go_ = sigmoidf_(g[3 * HID] + gh[3][i] + bias[3]);
+              c[i] = gf_ * c[i] + gi_ * gg_;
+              hnew = go_ * tanhf(c[i]);
+              sgp[0] = gi_; sgp[HID] = gf_; sgp[2 * HID] = gg_; sgp[3 * HID] = go_;
+              a.sc[(((size_t)dir * a.U + b) * a.L + t) * HID + my_unit] = c[i];
+            } else {
+              float r_ = sigmoidf_(g[0] + gh[0][i] + bias[0]);
+              float z_ = sigmoidf_(g[HID] + gh[1][i] + bias[1]);
+              float ghn = gh[2][i] + bias[2];
+              float n_ = tanhf(g[2 * HID] + r_ * ghn);
+              hnew = (1.0f - z_) * n_ + z_ * hold;
+              sgp[0] = r_; sgp[HID] = z_; sgp[2 * HID] = n_; sgp[3 * HID] = ghn;
+            }
+            outv = hnew;
+          }
+          hnext[xw + b * UNITS_WG] = hnew;
+          a.out[((size_t)b * a.L + t) * DIRS * HID + dir * HID + my_unit] = outv;
+        }
+      }
+    }
+    if (s + 1 < a.L) {
+      if (!grid_barrier(sync, (unsigned)NWG_D * (unsigned)(s + 1), tid, &ok_lds, a.spin)) {
+        rnn_fail(a.status, 128u);
+        rnn_poison(a.out, (size_t)a.U * a.L, DIRS * HID, dir * HID + wgi * UNITS_WG, UNITS_WG);
+        return;
+      }
+    }
+  }
+}
+
+struct IrnnBwdArgs {
+  const float* dout;   // [U][L][DIRS*HID]
+  const float* whh;    // [DIRS][G*HID][HID]
+  const int* len;      // [U]
+  const float* out;    // [U][L][DIRS*HID]  forward outputs (GRU: the state before each step)
+  const float* sg;     // [DIRS][U][L][4][HID]
+  const float* sc;     // [DIRS][U][L][HID] (LSTM)
+  float* dgi;          // [U][L][DIRS][G*HID]  gradient of gi
+  float* dgh;          // [U][L][DIRS][G*HID]  gradient of W_hh h + b_hh (GRU; the LSTM's equals dgi)
+  unsigned* sync;
+  float* xg;           // exchange [DIRS][L][NWG_D][NB][G][UNITS_WG]: each line written once
+  int U, L;
+  unsigned* status;
+  unsigned spin;
+};
+
+template <int E>
+__device__ __forceinline__ void ld_vec(const float* p, float (&v)[E]) {
+  if constexpr (E == 4) {
+    f32x4 x = *reinterpret_cast<const f32x4*>(p);
+    v[0] = x[0]; v[1] = x[1]; v[2] = x[2]; v[3] = x[3];
+  } else {
+    f32x2 x = *reinterpret_cast<const f32x2*>(p);
+    v[0] = x[0]; v[1] = x[1];
+  }
+}
+
+template <int CELL, int HID>
+__global__ __launch_bounds__(256) void irnn_bwd_kernel(IrnnBwdArgs a) {
+  using S = IrnnShape<CELL, HID>;
+  constexpr int G = S::G, DIRS = S::DIRS, NWG_D = S::NWG_D, E = S::E, Q = S::Q;
+  __shared__ int ok_lds;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int dir = blockIdx.x / NWG_D;
+  const int wgi = blockIdx.x % NWG_D;
+  const int u0 = wgi * UNITS_WG + wave * UNITS_WAVE;
+  const float* whh = a.whh + (size_t)dir * G * HID * HID;
+  unsigned* sync = a.sync + dir * 16;
+  // columns u0..u0+3 of W_hh over the G*HID gate rows: row = 64*E*q + E*lane + e
+  float wt[4][Q * E];
+#pragma unroll
+  for (int q = 0; q < Q; ++q)
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      const int row = 64 * E * q + E * lane + e;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) wt[u][q * E + e] = whh[(size_t)row * HID + u0 + u];
+    }
+  const int my_unit = u0 + (lane >> 4);
+  const int my_b = (lane >> 1) & 7;
+  const bool worker = ((lane & 1) == 0) && (my_b < a.U);
+  const int mylen = worker ? a.len[my_b] : 0;
+  float carry_h = 0.f, carry_c = 0.f;
+  constexpr int LXG_WG = NB * G * UNITS_WG;
+  const int xgw = wgi * LXG_WG + my_b * G * UNITS_WG + wave * UNITS_WAVE + (lane >> 4);   // + gate*16
+
+  for (int s = a.L - 1; s >= 0; --s) {
+    const int t = dir == 0 ? s : a.L - 1 - s;
+    float* xcur = a.xg + ((size_t)dir * a.L + s) * NWG_D * LXG_WG;
+    float dh_direct = 0.f;
+    if (worker) {
+      const size_t gofs = (((size_t)my_b * a.L + t) * DIRS + dir) * G * HID + my_unit;
+      float* dgp = a.dgi + gofs;
+      if (t < mylen) {
+        const size_t o = ((size_t)dir * a.U + my_b) * a.L + t;
+        const float* sgp = a.sg + o * 4 * HID + my_unit;
+        const float dh = a.dout[((size_t)my_b * a.L + t) * DIRS * HID + dir * HID + my_unit] + carry_h;
+        if constexpr (CELL == WSMG_CELL_LSTM) {
+          float gi_ = sgp[0], gf_ = sgp[HID], gg_ = sgp[2 * HID], go_ = sgp[3 * HID];
+          float cn = a.sc[o * HID + my_unit];
+          const int tp = dir == 0 ? t - 1 : t + 1;      // previous step in processing order (c = 0 before the first)
+          float cp = (tp >= 0 && tp < mylen) ? a.sc[(((size_t)dir * a.U + my_b) * a.L + tp) * HID + my_unit] : 0.f;
+          float tc = tanhf(cn);
+          float do_pre = dh * tc * go_ * (1.0f - go_);
+          float dc = dh * go_ * (1.0f - tc * tc) + carry_c;
+          float di_pre = dc * gg_ * gi_ * (1.0f - gi_);
+          float df_pre = dc * cp * gf_ * (1.0f - gf_);
+          float dg_pre = dc * gi_ * (1.0f - gg_ * gg_);
+          carry_c = dc * gf_;
+          dgp[0] = di_pre; dgp[HID] = df_pre; dgp[2 * HID] = dg_pre; dgp[3 * HID] = do_pre;
+          xcur[xgw] = di_pre; xcur[xgw + UNITS_WG] = df_pre; xcur[xgw + 2 * UNITS_WG] = dg_pre; xcur[xgw + 3 * UNITS_WG] = do_pre;
+        } else {
+          float r_ = sgp[0], z_ = sgp[HID], n_ = sgp[2 * HID], ghn = sgp[3 * HID];
+          const int tp = dir == 0 ? t - 1 : t + 1;      // the state before this step: 0 at the first active step
+          float hp = (tp >= 0 && tp < mylen) ? a.out[((size_t)my_b * a.L + tp) * DIRS * HID + dir * HID + my_unit] : 0.f;
+          float dn_pre = dh * (1.0f - z_) * (1.0f - n_ * n_);
+          float dz_pre = dh * (hp - n_) * z_ * (1.0f - z_);
+          float dr_pre = dn_pre * ghn * r_ * (1.0f - r_);
+          float dghn = dn_pre * r_;
+          float* dhp = a.dgh + gofs;
+          dgp[0] = dr_pre; dgp[HID] = dz_pre; dgp[2 * HID] = dn_pre;
+          dhp[0] = dr_pre; dhp[HID] = dz_pre; dhp[2 * HID] = dghn;
+          xcur[xgw] = dr_pre; xcur[xgw + UNITS_WG] = dz_pre; xcur[xgw + 2 * UNITS_WG] = dghn;
+          dh_direct = dh * z_;
+        }
+      } else {
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+          dgp[g * HID] = 0.f;
+          if constexpr (CELL != WSMG_CELL_LSTM) a.dgh[gofs + g * HID] = 0.f;
+          xcur[xgw + g * UNITS_WG] = 0.f;
+        }
+        dh_direct = carry_h;  // frozen state: gradient passes straight through
+      }
+    }
+    if (!grid_barrier(sync, (unsigned)NWG_D * (unsigned)(a.L - s), tid, &ok_lds, a.spin)) {
+      rnn_fail(a.status, 256u);
+      for (int g = 0; g < G; ++g) {
+        rnn_poison(a.dgi, (size_t)a.U * a.L, DIRS * G * HID, dir * G * HID + g * HID + wgi * UNITS_WG, UNITS_WG);
+        if (CELL != WSMG_CELL_LSTM)
+          rnn_poison(a.dgh, (size_t)a.U * a.L, DIRS * G * HID, dir * G * HID + g * HID + wgi * UNITS_WG, UNITS_WG);
+      }
+      return;
+    }
+    float acc[32];
+#pragma unroll
+    for (int i = 0; i < 32; ++i) acc[i] = 0.f;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+      if (b < a.U) {
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+          const int k = 64 * E * q + E * lane;         // gate row -> gate k / HID, unit k % HID
+          const int gate = k / HID, unit = k % HID;
+          float g[E];
+          ld_vec<E>(xcur + (unit >> 4) * LXG_WG + b * G * UNITS_WG + gate * UNITS_WG + (unit & 15), g);
+#pragma unroll
+          for (int e = 0; e < E; ++e)
+#pragma unroll
+            for (int u = 0; u < 4; ++u) acc[u * 8 + b] = fmaf(wt[u][q * E + e], g[e], acc[u * 8 + b]);
+        }
+      }
+    }
+    halve<32, 32>(acc, lane);
+    halve<16, 16>(acc, lane);
+    halve<8, 8>(acc, lane);
+    halve<4, 4>(acc, lane);
+    halve<2, 2>(acc, lane);
+    float sum = acc[0] + __shfl_xor(acc[0], 1, 64);
+    carry_h = dh_direct + sum;
+  }
+}
+
+bool irnn_supported(int cell, int hidden, int dirs) {
+  return (cell == WSMG_CELL_LSTM && hidden == 128 && dirs == 2) || (cell == WSMG_CELL_GRU && hidden == 128 && dirs == 2) ||
+         (cell == WSMG_CELL_LSTM && hidden == 256 && dirs == 1) || (cell == WSMG_CELL_GRU && hidden == 256 && dirs == 1);
+}
+
+}  // namespace
+
+// per token: forward image NB x 256 floats, backward image G times that (both shapes keep 256 units in flight)
+extern "C" int64_t wsmg_instr_rnn_workspace_bytes(int cell, int hidden, int dirs, int L) {
+  if (!irnn_supported(cell, hidden, dirs) || L <= 0) return 0;
+  return 256 + (int64_t)L * NB * (cell == WSMG_CELL_LSTM ? 4 : 3) * 256 * 4;
+}
+
+extern "C" int wsmg_instr_rnn_fwd(int cell, const float* gi, const float* w_hh, const float* b_hh, const int32_t* lengths, int U,
+                                  int L, int hidden, int dirs, float* out, float* save_gates, float* save_c, void* state_ws,
+                                  wsmg_stream_t stream) {
+  if (!irnn_supported(cell, hidden, dirs) || U <= 0 || U > NB || L <= 0) return WSMG_EINVAL;
+  if (((uintptr_t)state_ws & 127) != 0 || !gi || !w_hh || !b_hh || !lengths || !out || !save_gates) return WSMG_EINVAL;
+  if (cell == WSMG_CELL_LSTM && !save_c) return WSMG_EINVAL;
+  if (cell == WSMG_CELL_LSTM && hidden == LH)          // the default encoder: its own kernel, unchanged
+    return wsmg_lstm_fwd(gi, w_hh, b_hh, lengths, U, L, hidden, out, save_gates, save_c, state_ws, stream);
+  hipStream_t s = wsmg_s(stream);
+  hipError_t e = hipMemsetAsync(state_ws, 0, 256, s);   // barrier words
+  if (e != hipSuccess) return (int)e;
+  IrnnFwdArgs a{gi, w_hh, b_hh, lengths, out, (float*)((char*)state_ws + 256), save_gates, save_c,
+                (unsigned*)state_ws, U, L, rnn_status_dev(), g_spin};
+  if (cell == WSMG_CELL_GRU && hidden == 128) hipLaunchKernelGGL((irnn_fwd_kernel<WSMG_CELL_GRU, 128>), dim3(16), dim3(256), 0, s, a);
+  else if (cell == WSMG_CELL_GRU) hipLaunchKernelGGL((irnn_fwd_kernel<WSMG_CELL_GRU, 256>), dim3(16), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((irnn_fwd_kernel<WSMG_CELL_LSTM, 256>), dim3(16), dim3(256), 0, s, a);
+  WSMG_RETURN_LAUNCH();
+}
+
+extern "C" int wsmg_instr_rnn_bwd(int cell, const float* dout, const float* w_hh, const int32_t* lengths, const float* out,
+                                  const float* save_gates, const float* save_c, int U, int L, int hidden, int dirs, float* dgi,
+                                  float* dgh, void* state_ws, wsmg_stream_t stream) {
+  if (!irnn_supported(cell, hidden, dirs) || U <= 0 || U > NB || L <= 0) return WSMG_EINVAL;
+  if (((uintptr_t)state_ws & 127) != 0 || !dout || !w_hh || !lengths || !save_gates || !dgi) return WSMG_EINVAL;
+  if (cell == WSMG_CELL_LSTM ? !save_c : (!out || !dgh)) return WSMG_EINVAL;
+  if (cell == WSMG_CELL_LSTM && hidden == LH)
+    return wsmg_lstm_bwd(dout, w_hh, lengths, save_gates, save_c, U, L, hidden, dgi, state_ws, stream);
+  hipStream_t s = wsmg_s(stream);
+  hipError_t e = hipMemsetAsync(state_ws, 0, 256, s);
+  if (e != hipSuccess) return (int)e;
+  IrnnBwdArgs a{dout, w_hh, lengths, out, save_gates, save_c, dgi, dgh, (unsigned*)state_ws, (float*)((char*)state_ws + 256),
+                U, L, rnn_status_dev(), g_spin};
+  if (cell == WSMG_CELL_GRU && hidden == 128) hipLaunchKernelGGL((irnn_bwd_kernel<WSMG_CELL_GRU, 128>), dim3(16), dim3(256), 0, s, a);
+  else if (cell == WSMG_CELL_GRU) hipLaunchKernelGGL((irnn_bwd_kernel<WSMG_CELL_GRU, 256>), dim3(16), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((irnn_bwd_kernel<WSMG_CELL_LSTM, 256>), dim3(16), dim3(256), 0, s, a);
   WSMG_RETURN_LAUNCH();
 }

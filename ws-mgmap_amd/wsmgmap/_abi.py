@@ -145,6 +145,9 @@ _SIG["wsmg_lstm_state_bwd"] = [c_p] * 8 + [c_i] * 3 + [c_p] * 4 + [c_p]
 _SIG["wsmg_lstm_workspace_bytes"] = [c_i]
 _SIG["wsmg_lstm_fwd"] = [c_p] * 4 + [c_i] * 3 + [c_p] * 4 + [c_p]
 _SIG["wsmg_lstm_bwd"] = [c_p] * 5 + [c_i] * 3 + [c_p] * 2 + [c_p]
+_SIG["wsmg_instr_rnn_workspace_bytes"] = [c_i] * 4
+_SIG["wsmg_instr_rnn_fwd"] = [c_i] + [c_p] * 4 + [c_i] * 4 + [c_p] * 4 + [c_p]
+_SIG["wsmg_instr_rnn_bwd"] = [c_i] + [c_p] * 6 + [c_i] * 4 + [c_p] * 3 + [c_p]
 _SIG["wsmg_group_norm_nhwc_bf16"] = [c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_p, c_p]
 _SIG["wsmg_rnn_status"] = [c_i]
 _SIG["wsmg_rnn_debug_spin_limit"] = [ctypes.c_uint]
@@ -175,7 +178,8 @@ _SIG["wsmg_bev_index_compact"] = [c_p, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_f, c
 _SIG["wsmg_bev_scatter_rotate_compact"] = [c_p, c_p, c_p, c_p, c_f] + [c_i] * 6 + [c_p, c_p]
 _SIG["wsmg_colsum_multi"] = [c_p, c_i, c_p]
 _SIG["wsmg_attn_fp8_row_fwd"] = [c_p] * 5 + [c_f, c_i, c_i, c_i] + [c_p] * 4
-_RESTYPE = {"wsmg_cls_tail_workspace_floats": c_l, "wsmg_attn_fp8_workspace_bytes": c_l, "wsmg_lstm_workspace_bytes": c_l, "wsmg_build_info": ctypes.c_char_p, "wsmg_channel_reduce_workspace_bytes": c_l, "wsmg_gru_workspace_bytes": c_l, "wsmg_lstm_state_workspace_bytes": c_l}
+_RESTYPE = {"wsmg_cls_tail_workspace_floats": c_l, "wsmg_attn_fp8_workspace_bytes": c_l, "wsmg_lstm_workspace_bytes": c_l, "wsmg_build_info": ctypes.c_char_p, "wsmg_channel_reduce_workspace_bytes": c_l, "wsmg_gru_workspace_bytes": c_l, "wsmg_lstm_state_workspace_bytes": c_l,
+            "wsmg_instr_rnn_workspace_bytes": c_l}
 
 _lib = None
 
@@ -227,7 +231,7 @@ rnn_timeouts = 0      # persistent-RNN timeouts reported so far in this process
 defer_rnn_status = False
 
 STATUS_BITS = ((1, "gru_fwd"), (2, "gru_bwd"), (4, "lstm_fwd"), (8, "lstm_bwd"), (16, "attn_fp8_fused barrier"), (32, "lstm_state_fwd"),
-               (64, "lstm_state_bwd"))
+               (64, "lstm_state_bwd"), (128, "instr_rnn_fwd"), (256, "instr_rnn_bwd"))
 
 
 def check_rnn_status(sync=False, force=False):

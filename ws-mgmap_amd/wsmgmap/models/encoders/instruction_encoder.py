@@ -1,6 +1,8 @@
-"""Instruction encoder: embedding + packed bidirectional LSTM.  State_dict keys and config
-fields follow the reference (instruction_encoder.py:10-93).  On the GPU the recurrence runs as one
-persistent packed bi-LSTM launch (csrc/wsmg_rnn.hip) instead of ~10 MIOpen launches per token.
+"""Instruction encoder: embedding + packed GRU / LSTM.  State_dict keys and config fields follow the
+reference (instruction_encoder.py:10-93).  On the GPU the recurrence of every setting the policy admits
+(LSTM or GRU, bidirectional hidden 128 or unidirectional hidden 256) runs as one persistent packed launch
+(csrc/wsmg_rnn.hip) instead of ~10 MIOpen launches per token and direction; other shapes take nn.GRU /
+nn.LSTM on a packed sequence.
 
 Differences in data flow (results identical):
   * output is token-major [B, L, 256] (what the attention kernel streams), the reference's
@@ -117,60 +119,79 @@ class InstructionEncoder(nn.Module):
 
     _packed = None
 
+    def _rnn_params(self):
+        """(w_ih, b_ih, w_hh, b_hh) of each direction of encoder_rnn, forward direction first."""
+        r = self.encoder_rnn
+        return [tuple(getattr(r, n + "_l0" + sfx) for n in ("weight_ih", "bias_ih", "weight_hh", "bias_hh"))
+                for sfx in (("", "_reverse") if self.bidir else ("",))]
+
+    def _pack(self, per_dir):
+        """The directions' parameters as the kernels take them: W_ih / b_ih concatenated, W_hh / b_hh stacked."""
+        return (torch.cat([p[0] for p in per_dir], dim=0), torch.cat([p[1] for p in per_dir], dim=0),
+                torch.stack([p[2] for p in per_dir]), torch.stack([p[3] for p in per_dir]))
+
     @torch.no_grad()
-    def packed_lstm_weights(self, refresh_only=False):
-        """Without autograd: the two directions' LSTM parameters concatenated / stacked as the kernels take them, kept while the
+    def packed_rnn_weights(self, refresh_only=False):
+        """Without autograd: the directions' GRU / LSTM parameters concatenated / stacked as the kernels take them, kept while the
         parameters keep their versions and rewritten IN PLACE otherwise (a captured rollout step reads these addresses;
         MGMapNet.refresh_folded calls this with refresh_only before a replay).  Four launches per step otherwise."""
         if self._packed is None and refresh_only:
             return 0
-        r = self.encoder_rnn
-        src = (r.weight_ih_l0, r.weight_ih_l0_reverse, r.bias_ih_l0, r.bias_ih_l0_reverse, r.weight_hh_l0, r.weight_hh_l0_reverse,
-               r.bias_hh_l0, r.bias_hh_l0_reverse)
+        per_dir = self._rnn_params()
+        src = tuple(p[i] for i in range(4) for p in per_dir)
         ver = tuple(p._version for p in src)
         if self._packed is None:
-            self._packed = [None, torch.cat(src[0:2], dim=0), torch.cat(src[2:4], dim=0), torch.stack(src[4:6]), torch.stack(src[6:8])]
+            self._packed = [None, *self._pack(per_dir)]
         elif self._packed[0] != ver:
-            self._packed[1].copy_(torch.cat(src[0:2], dim=0))
-            self._packed[2].copy_(torch.cat(src[2:4], dim=0))
-            self._packed[3].copy_(torch.stack(src[4:6]))
-            self._packed[4].copy_(torch.stack(src[6:8]))
+            for dst, new in zip(self._packed[1:], self._pack(per_dir)):
+                dst.copy_(new)
         elif refresh_only:
             return 0
         self._packed[0] = ver
         return 1 if refresh_only else tuple(self._packed[1:])
 
+    packed_lstm_weights = packed_rnn_weights
+
+    @property
+    def kernel_cell(self):
+        """"LSTM" / "GRU" if the persistent kernels of csrc/wsmg_rnn.hip take this encoder's shape (hidden 128 x 2 directions
+        or 256 x 1), else None (the stock packed route)."""
+        from ...ops.rnn import instr_rnn_supported
+        cell = "LSTM" if isinstance(self.encoder_rnn, nn.LSTM) else "GRU"
+        dirs = 2 if self.bidir else 1
+        return cell if instr_rnn_supported(cell, self.encoder_rnn.hidden_size, dirs) and self.encoder_rnn.num_layers == 1 else None
+
     def encode_unique(self, instruction, stock=False, dedup=None, lstm_after=None):
         """-> (hidden [U, L, D] token-major, pad mask [U, L] bool, inverse [B]) with U unique rows.
-        stock=False: persistent HIP bi-LSTM (csrc/wsmg_rnn.hip); stock=True: nn.LSTM on a packed
-        sequence (MIOpen / CPU), kept for comparison in tests.  dedup: the result of `dedup()` for these tokens, if the caller
+        stock=False: persistent HIP GRU / LSTM (csrc/wsmg_rnn.hip) for the shapes they take (`kernel_cell`), the stock route for
+        any other; stock=True: nn.GRU / nn.LSTM on a packed sequence (MIOpen / CPU), kept for comparison in tests.  dedup: the result of `dedup()` for these tokens, if the caller
         already has it (no host read-back here then).  lstm_after: an event the persistent LSTM launch waits for (the dedup, the
         embedding and the input projection do not)."""
         uniq, inverse, len_host, len_dev = self.dedup(instruction) if dedup is None else dedup
         from ...debug import sw
-        if stock or sw.rnn_stock or not isinstance(self.encoder_rnn, nn.LSTM) or not self.bidir:
+        cell = self.kernel_cell
+        if stock or sw.rnn_stock or cell is None or not uniq.is_cuda:
             embedded = self.embedding_layer(uniq)
             packed = nn.utils.rnn.pack_padded_sequence(embedded, len_host, batch_first=True, enforce_sorted=False)
             output, _ = self.encoder_rnn(packed)
             hidden = nn.utils.rnn.pad_packed_sequence(output, batch_first=True)[0]  # [U, L, D]
         else:
             from ... import ops
-            r = self.encoder_rnn
             lmax = int(len_host.max())
             embedded = self.embedding_layer(uniq[:, :lmax])                     # [U, L, E]
             if torch.is_grad_enabled():
-                w_ih = torch.cat([r.weight_ih_l0, r.weight_ih_l0_reverse], dim=0)   # [2*4H, E]
-                b_ih = torch.cat([r.bias_ih_l0, r.bias_ih_l0_reverse], dim=0)
-                w_hh = torch.stack([r.weight_hh_l0, r.weight_hh_l0_reverse])
-                b_hh = torch.stack([r.bias_hh_l0, r.bias_hh_l0_reverse])
+                w_ih, b_ih, w_hh, b_hh = self._pack(self._rnn_params())    # [D*G*H, E], [D*G*H], [D, G*H, H], [D, G*H]
             else:
-                w_ih, b_ih, w_hh, b_hh = self.packed_lstm_weights()
+                w_ih, b_ih, w_hh, b_hh = self.packed_rnn_weights()
             U = uniq.shape[0]
-            gi = torch.addmm(b_ih, embedded.reshape(U * lmax, -1), w_ih.t()).view(U, lmax, 2, -1)
+            gi = torch.addmm(b_ih, embedded.reshape(U * lmax, -1), w_ih.t()).view(U, lmax, w_hh.shape[0], -1)
             lens = len_dev.to(torch.int32)
             if lstm_after is not None:
                 torch.cuda.current_stream().wait_event(lstm_after)
-            parts = [ops.bilstm(gi[c:c + 8], w_hh, b_hh, lens[c:c + 8]) for c in range(0, U, 8)]
+            if cell == "LSTM" and self.bidir:      # the default encoder
+                parts = [ops.bilstm(gi[c:c + 8], w_hh, b_hh, lens[c:c + 8]) for c in range(0, U, 8)]
+            else:
+                parts = [ops.instr_rnn(gi[c:c + 8], w_hh, b_hh, lens[c:c + 8], cell) for c in range(0, U, 8)]
             hidden = parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
         mask = (hidden == 0.0).all(dim=2)
         return hidden.contiguous(), mask, inverse

@@ -10,8 +10,9 @@ Attribute tree, state_dict keys and the in-place contract (writes `observations[
     token-major keys/values; the k=1 Conv1d key projections are MFMA GEMMs of the conv engine;
   * the BEV projection / scatter / global-map fuse run in the BEV kernels (operator 1);
   * instruction encoding is de-duplicated over the time axis of a teacher-forcing batch;
-  * the two GRU state encoders run as persistent whole-sequence kernels (csrc/wsmg_rnn.hip);
-  * the instruction LSTM cell, Linear heads and losses stay stock PyTorch-ROCm.
+  * the two GRU / LSTM state encoders run as persistent whole-sequence kernels (csrc/wsmg_rnn.hip);
+  * so does the instruction encoder's packed GRU / LSTM (bidirectional hidden 128 or unidirectional 256: every
+    setting whose output width the policy admits); other shapes take stock nn.GRU / nn.LSTM.
 """
 import numpy as np
 import torch
@@ -187,7 +188,7 @@ class MGMapNet(nn.Module):
                       getattr(getattr(self.depth_encoder, "visual_encoder", None), "_wcache", None)):
             if cache is not None:
                 n += cache.refresh()
-        return n + self.instruction_encoder.packed_lstm_weights(refresh_only=True)
+        return n + self.instruction_encoder.packed_rnn_weights(refresh_only=True)
 
     def _map_stack_rollout(self, ego_map):
         """The map stack in eval mode without autograd (the rollout step), bf16: every convolution takes cached, BatchNorm-

@@ -165,3 +165,66 @@ class _BiLSTM(torch.autograd.Function):
 def bilstm(gi, w_hh, b_hh, lengths):
     """Packed bidirectional LSTM over <= 8 sequences in one persistent launch."""
     return _BiLSTM.apply(gi.contiguous(), w_hh.contiguous(), b_hh.contiguous(), lengths.contiguous())
+
+
+# ----------------------------------------------------------------------------- persistent packed instruction GRU / LSTM
+CELLS = {"LSTM": 0, "GRU": 1}        # WSMG_CELL_* of include/wsmgmap.h
+INSTR_RNN_SHAPES = ((128, 2), (256, 1))   # (hidden, directions) the kernels take: 256 units in flight
+
+
+def instr_rnn_supported(cell, hidden, dirs):
+    return cell in CELLS and (hidden, dirs) in INSTR_RNN_SHAPES
+
+
+class _InstrRNN(torch.autograd.Function):
+    """gi [U,L,D,G*H], w_hh [D,G*H,H], b_hh [D,G*H], lengths int32 [U] -> out [U,L,D*H]; G = 4 (LSTM) or 3 (GRU)."""
+
+    @staticmethod
+    def forward(ctx, gi, w_hh, b_hh, lengths, cell):
+        _req(gi, w_hh, b_hh, lengths)
+        _f32(gi, w_hh, b_hh)
+        U, L, D, GH = gi.shape
+        H = w_hh.shape[2]
+        code = CELLS[cell]
+        dev = gi.device
+        out = torch.empty(U, L, D * H, device=dev, dtype=torch.float32)
+        sg = torch.zeros(D, U, L, 4, H, device=dev, dtype=torch.float32)
+        sc = torch.zeros(D, U, L, H, device=dev, dtype=torch.float32) if cell == "LSTM" else None
+        ws = _rnn_workspace(_abi.lib().wsmg_instr_rnn_workspace_bytes(code, H, D, L), dev)
+        _abi.call("wsmg_instr_rnn_fwd", code, _p(gi), _p(w_hh), _p(b_hh), _p(lengths), U, L, H, D, _p(out), _p(sg),
+                  None if sc is None else _p(sc), _p(ws), _stream())
+        _rnn_launched()
+        ctx.cell = cell
+        ctx.save_for_backward(w_hh, lengths, out, sg, sc)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        w_hh, lengths, out, sg, sc = ctx.saved_tensors
+        cell = ctx.cell
+        code = CELLS[cell]
+        U, L, DH = out.shape
+        D, GH, H = w_hh.shape
+        dev = out.device
+        dout = dout.contiguous()
+        dgi = torch.empty(U, L, D, GH, device=dev, dtype=torch.float32)
+        dgh = torch.empty_like(dgi) if cell == "GRU" else None
+        ws = _rnn_workspace(_abi.lib().wsmg_instr_rnn_workspace_bytes(code, H, D, L), dev)
+        _abi.call("wsmg_instr_rnn_bwd", code, _p(dout), _p(w_hh), _p(lengths), _p(out), _p(sg), None if sc is None else _p(sc),
+                  U, L, H, D, _p(dgi), None if dgh is None else _p(dgh), _p(ws), _stream())
+        _rnn_launched()
+        zero = torch.zeros(U, 1, H, device=dev, dtype=torch.float32)
+        hprev = [torch.cat([zero, out[:, :-1, :H]], dim=1)]               # state before step t (forward direction)
+        if D == 2:
+            hprev.append(torch.cat([out[:, 1:, H:], zero], dim=1))        # state before step t (reverse direction)
+        # per direction a contiguous [U L, G H] matrix (see _BiLSTM.backward)
+        dgd = (dgi if dgh is None else dgh).permute(2, 0, 1, 3).contiguous().view(D, U * L, GH)
+        dw = torch.stack([dgd[d].t() @ hprev[d].reshape(U * L, H) for d in range(D)])
+        from .heads import colsum_multi
+        db = torch.stack(colsum_multi([dgd[d] for d in range(D)]))
+        return dgi, dw, db, None, None
+
+
+def instr_rnn(gi, w_hh, b_hh, lengths, cell):
+    """Packed instruction GRU / LSTM (hidden 128 x 2 directions or 256 x 1) over <= 8 sequences in one persistent launch."""
+    return _InstrRNN.apply(gi.contiguous(), w_hh.contiguous(), b_hh.contiguous(), lengths.contiguous(), cell)

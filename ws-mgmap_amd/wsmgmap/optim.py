@@ -80,7 +80,7 @@ class Adam(torch.optim.Optimizer):
                         _abi.call("wsmg_adam_step_multi", descs, len(items), float(group["lr"]), float(b1), float(b2), float(group["eps"]),
                                   float(group["weight_decay"]), 1.0 - b1 ** step, 1.0 - b2 ** step, stream)
                 # the kernel wrote the parameters through raw pointers: advance their autograd version counters, which is what
-                # caches of derived operands (FoldCache, InstructionEncoder.packed_lstm_weights) compare
+                # caches of derived operands (FoldCache, InstructionEncoder.packed_rnn_weights) compare
                 torch.autograd.graph.increment_version([it[0] for it in items])
         return loss
 
