@@ -563,31 +563,18 @@ int wsmg_lstm_state_bwd(const float* dy, const float* dhT, const float* dcT, con
                         const float* masks, const float* save_gates, const float* save_c, int T, int N, int hidden,
                         float* dgates, float* dh0, float* dc0, void* sync_ws, wsmg_stream_t stream);
 
-/* ============================ persistent packed bidirectional LSTM ============================ */
-/* nn.LSTM(50 -> 128, bidirectional) over packed instructions (instruction_encoder.py:80-92): row b is
- * active at token t iff t < lengths[b]; inactive positions emit 0.  Both directions run concurrently
- * in one launch (8 cooperating workgroups each, W_hh in registers, one bounded barrier per token).
- * gi [U][L][2][4H] = x W_ih^T + b_ih for (forward, reverse); w_hh [2][4H][H]; b_hh [2][4H]; U <= 8.
- * out [U][L][2H] (forward | reverse); save_gates [2][U][L][4][H], save_c [2][U][L][H] feed the backward.
- * state_ws: wsmg_lstm_workspace_bytes(L) bytes of 128-B-aligned device scratch (barrier words + exchange image). */
-int64_t wsmg_lstm_workspace_bytes(int L);
-int wsmg_lstm_fwd(const float* gi, const float* w_hh, const float* b_hh, const int32_t* lengths, int U, int L,
-                  int hidden, float* out, float* save_gates, float* save_c, void* state_ws,
-                  wsmg_stream_t stream);
-/* backward through time: dout [U][L][2H] -> dgates [U][L][2][4H] (gradient of the gate pre-activations,
- * i.e. of gi and of W_hh h + b_hh); the caller forms dW_hh, db_hh and back-propagates through its GEMM. */
-int wsmg_lstm_bwd(const float* dout, const float* w_hh, const int32_t* lengths, const float* save_gates,
-                  const float* save_c, int U, int L, int hidden, float* dgates, void* state_ws,
-                  wsmg_stream_t stream);
-
-/* The other instruction encoders the policy admits (output width 256; instruction_encoder.py:80-93 with
- * MODEL.INSTRUCTION_ENCODER.rnn_type / .bidirectional / .hidden_size): cell WSMG_CELL_LSTM or WSMG_CELL_GRU (gate order
- * r, z, n; n = tanh(gi_n + r (W_hn h + b_hn))) at (hidden 128, dirs 2) or (hidden 256, dirs 1); any other combination,
- * U > 8 or L <= 0 returns WSMG_EINVAL before anything is enqueued.  Semantics and layouts as wsmg_lstm_fwd / _bwd with G = 4
- * (LSTM) or 3 (GRU) gate rows per unit: gi [U][L][dirs][G H]; w_hh [dirs][G H][H]; b_hh [dirs][G H]; out [U][L][dirs H];
- * save_gates [dirs][U][L][4][H] (LSTM i, f, g, o; GRU r, z, n, W_hn h + b_hn); save_c [dirs][U][L][H] (LSTM only, may be
- * NULL for the GRU).  (LSTM, 128, 2) runs wsmg_lstm_fwd / _bwd.  state_ws: wsmg_instr_rnn_workspace_bytes(cell, hidden,
- * dirs, L) bytes of 128-B-aligned device scratch (0 for an unsupported combination). */
+/* ============================ persistent packed instruction GRU / LSTM ============================ */
+/* The instruction encoder's packed nn.LSTM / nn.GRU (instruction_encoder.py:80-93; MODEL.INSTRUCTION_ENCODER.rnn_type /
+ * .bidirectional / .hidden_size) at the four settings the policy admits (output width 256): cell WSMG_CELL_LSTM (gate order
+ * i, f, g, o) or WSMG_CELL_GRU (gate order r, z, n; n = tanh(gi_n + r (W_hn h + b_hn))) at (hidden 128, dirs 2) or
+ * (hidden 256, dirs 1).  Any other combination, U > 8, L <= 0, a misaligned workspace or a NULL pointer the cell needs returns
+ * WSMG_EINVAL before anything is enqueued.  Row b is active at token t iff t < lengths[b]; inactive positions emit 0 and
+ * freeze the state (initial state zero).  All directions run concurrently in one launch (256 units in flight: 16 cooperating
+ * workgroups, W_hh in registers, one bounded barrier per token).  With G = 4 (LSTM) or 3 (GRU) gate rows per unit:
+ * gi [U][L][dirs][G H] = x W_ih^T + b_ih for (forward, reverse); w_hh [dirs][G H][H]; b_hh [dirs][G H]; U <= 8.
+ * out [U][L][dirs H] (forward | reverse); save_gates [dirs][U][L][4][H] (LSTM i, f, g, o; GRU r, z, n, W_hn h + b_hn) and
+ * save_c [dirs][U][L][H] (LSTM only, may be NULL for the GRU) feed the backward.  state_ws: wsmg_instr_rnn_workspace_bytes(cell,
+ * hidden, dirs, L) bytes of 128-B-aligned device scratch (barrier words + exchange image; 0 for an unsupported combination). */
 #define WSMG_CELL_LSTM 0
 #define WSMG_CELL_GRU 1
 int64_t wsmg_instr_rnn_workspace_bytes(int cell, int hidden, int dirs, int L);
@@ -596,10 +583,21 @@ int wsmg_instr_rnn_fwd(int cell, const float* gi, const float* w_hh, const float
                        wsmg_stream_t stream);
 /* backward through time: dout [U][L][dirs H] and the forward's out / save_gates / save_c -> dgi [U][L][dirs][G H] (gradient
  * of gi) and, for the GRU, dgh (gradient of W_hh h + b_hh: its n rows are r times dgi's); the LSTM's dgh equals dgi and may
- * be NULL.  out is read by the GRU only (the state before each step). */
+ * be NULL.  out is read by the GRU only (the state before each step).  The caller forms dW_hh, db_hh and back-propagates
+ * through its GEMM. */
 int wsmg_instr_rnn_bwd(int cell, const float* dout, const float* w_hh, const int32_t* lengths, const float* out,
                        const float* save_gates, const float* save_c, int U, int L, int hidden, int dirs, float* dgi,
                        float* dgh, void* state_ws, wsmg_stream_t stream);
+/* The default encoder, nn.LSTM(50 -> 128, bidirectional): wsmg_lstm_workspace_bytes(L), wsmg_lstm_fwd(...) and
+ * wsmg_lstm_bwd(..., dgates, ...) are wsmg_instr_rnn_*(WSMG_CELL_LSTM, ..., hidden, 2, ...) (hidden must be 128; dgates = dgi,
+ * dgh = NULL). */
+int64_t wsmg_lstm_workspace_bytes(int L);
+int wsmg_lstm_fwd(const float* gi, const float* w_hh, const float* b_hh, const int32_t* lengths, int U, int L,
+                  int hidden, float* out, float* save_gates, float* save_c, void* state_ws,
+                  wsmg_stream_t stream);
+int wsmg_lstm_bwd(const float* dout, const float* w_hh, const int32_t* lengths, const float* save_gates,
+                  const float* save_c, int U, int L, int hidden, float* dgates, void* state_ws,
+                  wsmg_stream_t stream);
 
 /* ============================ GroupNorm (frozen DD-PPO depth backbone, rollout path) ============================ */
 /* nn.GroupNorm(G, C) [+ residual] [+ ReLU] on NHWC activations, inference only: x [B][HW][C] float32 (x_f32 = 1: the
@@ -619,8 +617,9 @@ int wsmg_group_norm_nhwc_bf16(const void* x, int x_f32, const void* residual, co
  * wsmg_rnn_debug_spin_limit(n): bound every spin by n polls (0 = default, 2^20) — test hook to force a timeout.
  * Bit 16 (round 6): the grid barrier of wsmg_attn_fp8_mfma_fused timed out (its outputs are NaN).
  * Bits 32 and 64: wsmg_lstm_state_fwd / wsmg_lstm_state_bwd timed out (y, c_T / dgates, dh0, dc0 are NaN).
- * Bits 128 and 256: wsmg_instr_rnn_fwd / wsmg_instr_rnn_bwd timed out in their GRU / hidden-256 kernels (out / dgi, dgh
- * are NaN; the default bidirectional LSTM reports bits 4 and 8).
+ * Bits 4 and 8 are those of the default bidirectional LSTM (wsmg_lstm_* and wsmg_instr_rnn_* at (LSTM, 128, 2)); bits 128
+ * and 256: wsmg_instr_rnn_fwd / _bwd timed out at their other three settings (GRU, hidden 256).  Either way out / dgi, dgh
+ * are NaN.
  * wsmg_rnn_debug_inject(bits): OR `bits` into the word as a timed-out kernel would — test hook for the callers' error paths
  * (bench.py's in-process fallback, GradAllReducer's cross-rank agreement); returns the word after the OR. */
 int wsmg_rnn_status(int clear);

@@ -125,14 +125,14 @@ def test_instruction_rnn_timeout_bits_reach_the_caller():
 
 
 def test_instruction_rnn_bit_identical_next_to_concurrent_mfma_load():
-    """As test_rnn_handoff_under_concurrent_load: the three new kernel pairs beside a stream of bf16 MFMA convolutions, their
+    """As test_rnn_handoff_under_concurrent_load: the four kernel pairs beside a stream of bf16 MFMA convolutions, their
     exchange images poisoned with NaN before every launch, must repeat the unloaded run bit for bit."""
     from wsmgmap import ops
     torch.manual_seed(0)
     U, L = 8, 60
     lens = torch.tensor([60, 37, 1, 44, 60, 12, 55, 59], device="cuda", dtype=torch.int32)
     cases_ = []
-    for cell, D, H in (("GRU", 2, 128), ("LSTM", 1, 256), ("GRU", 1, 256)):
+    for cell, D, H in (("LSTM", 2, 128), ("GRU", 2, 128), ("LSTM", 1, 256), ("GRU", 1, 256)):
         G = 3 if cell == "GRU" else 4
         cases_.append((cell, torch.randn(U, L, D, G * H, device="cuda"), torch.randn(D, G * H, H, device="cuda") * (1.0 / H ** 0.5),
                        torch.randn(D, G * H, device="cuda") * 0.1, torch.randn(U, L, D * H, device="cuda")))

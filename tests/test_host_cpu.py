@@ -36,6 +36,18 @@ def test_abi_library_exports_every_declared_symbol():
     assert b"gfx950" in L.wsmg_build_info()
 
 
+def test_bilstm_abi_is_the_instruction_rnn_abi():
+    """wsmg_lstm_* are wsmg_instr_rnn_*(WSMG_CELL_LSTM, ..., hidden 128, 2 directions): the same workspace, and the same refusals
+    before anything is enqueued (an unsupported shape, U > 8, NULL pointers)."""
+    from wsmgmap import _abi
+    L = _abi.lib()
+    for n in (1, 7, 80, 200):
+        assert L.wsmg_lstm_workspace_bytes(n) == L.wsmg_instr_rnn_workspace_bytes(0, 128, 2, n) == 256 + 32768 * n
+    for U, hidden in ((9, 128), (1, 64), (1, 256), (1, 128)):
+        assert L.wsmg_lstm_fwd(None, None, None, None, U, 10, hidden, None, None, None, None, None) == -1
+        assert L.wsmg_lstm_bwd(None, None, None, None, None, U, 10, hidden, None, None, None) == -1
+
+
 def test_ops_refuse_cpu_tensors_no_fallback():
     from wsmgmap import _abi, ops
     x = torch.zeros(1, 4, 4, 32)

@@ -1055,273 +1055,21 @@ extern "C" int wsmg_lstm_state_bwd(const float* dy, const float* dhT, const floa
 }
 
 // =================================================================================================
-// Persistent packed bidirectional LSTM (instruction encoder, hidden 128 per direction, U <= 8 unique
-// instructions per launch).  Replaces the cuDNN/MIOpen packed-sequence LSTM behind nn.LSTM at
-// instruction_encoder.py:80-92 (about 10 tiny launches per token step and direction in MIOpen).
-// Same structure as the GRU kernels: per direction 8 workgroups x 4 waves, each wave keeps the
-// 16 gate rows (i,f,g,o of 4 hidden units) of W_hh in registers, lanes split K = 128, one bounded
-// grid barrier per token step per direction; both directions run concurrently in one launch.
-// Packed-sequence semantics: row b is active at step t iff t < len[b]; inactive steps freeze the
-// state and emit 0 (forward direction: after the end; reverse direction: before its first token).
-// Gate order i, f, g, o (PyTorch nn.LSTM).  gi = x W_ih^T + b_ih for both directions is one GEMM
-// done by the caller; so are dW_hh / dW_ih.
-namespace {
-
-constexpr int LH = 128;            // hidden per direction
-constexpr int L_NWG = LH / UNITS_WG;   // 8 workgroups per direction
-
-struct LstmFwdArgs {
-  const float* gi;     // [U][L][2][4*LH]
-  const float* whh;    // [2][4*LH][LH]
-  const float* bhh;    // [2][4*LH]
-  const int* len;      // [U]
-  float* out;          // [U][L][2*LH]
-  float* hs;           // exchange [2 dir][L][L_NWG][NB][UNITS_WG]: each line written once by one workgroup
-  float* sg;           // [2][U][L][4][LH] saved gates i,f,g,o
-  float* sc;           // [2][U][L][LH]    saved cell state c_t
-  unsigned* sync;      // per direction 16 words: [0] counter, [1] error
-  int U, L;
-  unsigned* status;    // host-mapped process status word (rnn_fail)
-  unsigned spin;
-};
-
-__global__ __launch_bounds__(256) void lstm_fwd_kernel(LstmFwdArgs a) {
-  __shared__ int ok_lds;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int dir = blockIdx.x / L_NWG;
-  const int u0 = (blockIdx.x % L_NWG) * UNITS_WG + wave * UNITS_WAVE;
-  const float* whh = a.whh + (size_t)dir * 4 * LH * LH;
-  const float* bhh = a.bhh + dir * 4 * LH;
-  unsigned* sync = a.sync + dir * 16;
-  // rows r = gate*4 + unit; k = 2*lane + e
-  float w[16][2];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int row = (r >> 2) * LH + u0 + (r & 3);
-    w[r][0] = whh[(size_t)row * LH + 2 * lane];
-    w[r][1] = whh[(size_t)row * LH + 2 * lane + 1];
-  }
-  const int my_unit = u0 + ((lane >> 2) & 3);
-  const int my_b0 = 2 * (lane & 3);
-  float bi = 0.f, bf = 0.f, bg = 0.f, bo = 0.f;
-  if (lane < 16) { bi = bhh[my_unit]; bf = bhh[LH + my_unit]; bg = bhh[2 * LH + my_unit]; bo = bhh[3 * LH + my_unit]; }
-  int mylen[2] = {0, 0};
-  if (lane < 16) {
-    if (my_b0 < a.U) mylen[0] = a.len[my_b0];
-    if (my_b0 + 1 < a.U) mylen[1] = a.len[my_b0 + 1];
-  }
-  float c[2] = {0.f, 0.f};
-  float* hs = a.hs + (size_t)dir * a.L * NB * LH;  // step-indexed image [L][L_NWG][NB][UNITS_WG]
-  const int wgi = blockIdx.x % L_NWG;
-  const int xk = ((2 * lane) >> 4) * NB * UNITS_WG + ((2 * lane) & 15);          // + b*16
-  const int xw = wgi * NB * UNITS_WG + wave * UNITS_WAVE + ((lane >> 2) & 3);    // + b*16
-
-  for (int s = 0; s < a.L; ++s) {
-    const int t = dir == 0 ? s : a.L - 1 - s;
-    const float* hprev = hs + (size_t)(s > 0 ? s - 1 : 0) * NB * LH;   // slot written in step s-1
-    float* hnext = hs + (size_t)s * NB * LH;
-    float hp[NB][2];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      hp[b][0] = s > 0 ? hprev[xk + b * UNITS_WG] : 0.f;       // initial state is zero
-      hp[b][1] = s > 0 ? hprev[xk + b * UNITS_WG + 1] : 0.f;
-    }
-    float acc[128];
-#pragma unroll
-    for (int r = 0; r < 16; ++r)
-#pragma unroll
-      for (int b = 0; b < NB; ++b) acc[r * 8 + b] = fmaf(w[r][1], hp[b][1], w[r][0] * hp[b][0]);
-    halve<128, 32>(acc, lane);
-    halve<64, 16>(acc, lane);
-    halve<32, 8>(acc, lane);
-    halve<16, 4>(acc, lane);
-    halve<8, 2>(acc, lane);
-    halve<4, 1>(acc, lane);
-    float f0 = __shfl(acc[0], lane + 16, 64), f1 = __shfl(acc[1], lane + 16, 64);
-    float g0 = __shfl(acc[0], lane + 32, 64), g1 = __shfl(acc[1], lane + 32, 64);
-    float o0 = __shfl(acc[0], lane + 48, 64), o1 = __shfl(acc[1], lane + 48, 64);
-    if (lane < 16) {
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int b = my_b0 + i;
-        if (b < a.U) {
-          const float hold = s > 0 ? hprev[xw + b * UNITS_WG] : 0.f;
-          const bool active = t < mylen[i];
-          float hnew = hold;
-          float outv = 0.f;
-          if (active) {
-            const float* g = a.gi + (((size_t)b * a.L + t) * 2 + dir) * 4 * LH;
-            float gi_ = sigmoidf_(g[my_unit] + (i ? acc[1] : acc[0]) + bi);
-            float gf_ = sigmoidf_(g[LH + my_unit] + (i ? f1 : f0) + bf);
-            float gg_ = tanhf(g[2 * LH + my_unit] + (i ? g1 : g0) + bg);
-            float go_ = sigmoidf_(g[3 * LH + my_unit] + (i ? o1 : o0) + bo);
-            c[i] = gf_ * c[i] + gi_ * gg_;
-            hnew = go_ * tanhf(c[i]);
-            outv = hnew;
-            float* sgp = a.sg + ((((size_t)dir * a.U + b) * a.L + t) * 4) * LH + my_unit;
-            sgp[0] = gi_; sgp[LH] = gf_; sgp[2 * LH] = gg_; sgp[3 * LH] = go_;
-            a.sc[(((size_t)dir * a.U + b) * a.L + t) * LH + my_unit] = c[i];
-          }
-          hnext[xw + b * UNITS_WG] = hnew;
-          a.out[((size_t)b * a.L + t) * 2 * LH + dir * LH + my_unit] = outv;
-        }
-      }
-    }
-    if (s + 1 < a.L) {
-      if (!grid_barrier(sync, (unsigned)L_NWG * (unsigned)(s + 1), tid, &ok_lds, a.spin)) {
-        rnn_fail(a.status, 4u);
-        rnn_poison(a.out, (size_t)a.U * a.L, 2 * LH, dir * LH + wgi * UNITS_WG, UNITS_WG);
-        return;
-      }
-    }
-  }
-}
-
-struct LstmBwdArgs {
-  const float* dout;   // [U][L][2*LH]
-  const float* whh;    // [2][4*LH][LH]
-  const int* len;      // [U]
-  const float* sg;     // [2][U][L][4][LH]
-  const float* sc;     // [2][U][L][LH]
-  float* dg;           // [U][L][2][4*LH]  gradient of the gate pre-activations (= d gi = d gh)
-  unsigned* sync;
-  float* xg;           // exchange [2 dir][L][L_NWG][NB][4][UNITS_WG]: each line written once
-  int U, L;
-  unsigned* status;    // host-mapped process status word (rnn_fail)
-  unsigned spin;
-};
-
-__global__ __launch_bounds__(256) void lstm_bwd_kernel(LstmBwdArgs a) {
-  __shared__ int ok_lds;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int dir = blockIdx.x / L_NWG;
-  const int u0 = (blockIdx.x % L_NWG) * UNITS_WG + wave * UNITS_WAVE;
-  const float* whh = a.whh + (size_t)dir * 4 * LH * LH;
-  unsigned* sync = a.sync + dir * 16;
-  // columns u0..u0+3 of W_hh over the 4*LH gate rows: k = 256*q + 4*lane + e
-  float wt[4][8];
-#pragma unroll
-  for (int q = 0; q < 2; ++q)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int row = 256 * q + 4 * lane + e;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) wt[u][q * 4 + e] = whh[(size_t)row * LH + u0 + u];
-    }
-  const int my_unit = u0 + (lane >> 4);
-  const int my_b = (lane >> 1) & 7;
-  const bool worker = ((lane & 1) == 0) && (my_b < a.U);
-  const int mylen = worker ? a.len[my_b] : 0;
-  float carry_h = 0.f, carry_c = 0.f;
-  constexpr int LXG_WG = NB * 4 * UNITS_WG;
-  const int wgi = blockIdx.x % L_NWG;
-  const int xgw = wgi * LXG_WG + my_b * 4 * UNITS_WG + wave * UNITS_WAVE + (lane >> 4);   // + gate*16
-
-  for (int s = a.L - 1; s >= 0; --s) {
-    const int t = dir == 0 ? s : a.L - 1 - s;
-    float* xcur = a.xg + ((size_t)dir * a.L + s) * L_NWG * LXG_WG;
-    float dh_direct = 0.f;
-    if (worker) {
-      float* dgp = a.dg + (((size_t)my_b * a.L + t) * 2 + dir) * 4 * LH + my_unit;
-      if (t < mylen) {
-        const size_t o = (((size_t)dir * a.U + my_b) * a.L + t);
-        const float* sgp = a.sg + o * 4 * LH + my_unit;
-        float gi_ = sgp[0], gf_ = sgp[LH], gg_ = sgp[2 * LH], go_ = sgp[3 * LH];
-        float cn = a.sc[o * LH + my_unit];
-        // previous cell state in processing order (0 at the first active step)
-        const int tp = dir == 0 ? t - 1 : t + 1;
-        float cp = (tp >= 0 && tp < mylen) ? a.sc[((((size_t)dir * a.U + my_b) * a.L + tp)) * LH + my_unit] : 0.f;
-        float dh = a.dout[((size_t)my_b * a.L + t) * 2 * LH + dir * LH + my_unit] + carry_h;
-        float tc = tanhf(cn);
-        float do_pre = dh * tc * go_ * (1.0f - go_);
-        float dc = dh * go_ * (1.0f - tc * tc) + carry_c;
-        float di_pre = dc * gg_ * gi_ * (1.0f - gi_);
-        float df_pre = dc * cp * gf_ * (1.0f - gf_);
-        float dg_pre = dc * gi_ * (1.0f - gg_ * gg_);
-        carry_c = dc * gf_;
-        dgp[0] = di_pre; dgp[LH] = df_pre; dgp[2 * LH] = dg_pre; dgp[3 * LH] = do_pre;
-        xcur[xgw] = di_pre; xcur[xgw + UNITS_WG] = df_pre; xcur[xgw + 2 * UNITS_WG] = dg_pre; xcur[xgw + 3 * UNITS_WG] = do_pre;
-      } else {
-        dgp[0] = 0.f; dgp[LH] = 0.f; dgp[2 * LH] = 0.f; dgp[3 * LH] = 0.f;
-        xcur[xgw] = 0.f; xcur[xgw + UNITS_WG] = 0.f; xcur[xgw + 2 * UNITS_WG] = 0.f; xcur[xgw + 3 * UNITS_WG] = 0.f;
-        dh_direct = carry_h;  // frozen state: gradient passes straight through
-      }
-    }
-    if (!grid_barrier(sync, (unsigned)L_NWG * (unsigned)(a.L - s), tid, &ok_lds, a.spin)) {
-      rnn_fail(a.status, 8u);
-      for (int g = 0; g < 4; ++g)
-        rnn_poison(a.dg, (size_t)a.U * a.L, 2 * 4 * LH, dir * 4 * LH + g * LH + wgi * UNITS_WG, UNITS_WG);
-      return;
-    }
-    float acc[32];
-#pragma unroll
-    for (int i = 0; i < 32; ++i) acc[i] = 0.f;
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      if (b < a.U) {
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          const int k = 256 * q + 4 * lane;          // gate row -> gate k/128, unit k%128
-          const int gate = k >> 7, unit = k & 127;
-          f32x4 g = *reinterpret_cast<const f32x4*>(xcur + (unit >> 4) * LXG_WG + b * 4 * UNITS_WG + gate * UNITS_WG + (unit & 15));
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-#pragma unroll
-            for (int u = 0; u < 4; ++u) acc[u * 8 + b] = fmaf(wt[u][q * 4 + e], g[e], acc[u * 8 + b]);
-        }
-      }
-    }
-    halve<32, 32>(acc, lane);
-    halve<16, 16>(acc, lane);
-    halve<8, 8>(acc, lane);
-    halve<4, 4>(acc, lane);
-    halve<2, 2>(acc, lane);
-    float sum = acc[0] + __shfl_xor(acc[0], 1, 64);
-    carry_h = dh_direct + sum;
-  }
-}
-
-}  // namespace
-
-// per token and direction: forward image NB*LH floats (4 KB), backward image 4x that (16 KB)
-extern "C" int64_t wsmg_lstm_workspace_bytes(int L) { return 256 + (int64_t)2 * L * L_NWG * NB * 4 * UNITS_WG * 4; }
-
-extern "C" int wsmg_lstm_fwd(const float* gi, const float* w_hh, const float* b_hh, const int32_t* lengths, int U, int L,
-                             int hidden, float* out, float* save_gates, float* save_c, void* state_ws,
-                             wsmg_stream_t stream) {
-  if (hidden != LH || U <= 0 || U > NB || L <= 0) return WSMG_EINVAL;
-  hipStream_t s = wsmg_s(stream);
-  if (((uintptr_t)state_ws & 127) != 0) return WSMG_EINVAL;
-  hipError_t e = hipMemsetAsync(state_ws, 0, 256, s);   // barrier words
-  if (e != hipSuccess) return (int)e;
-  LstmFwdArgs a{gi, w_hh, b_hh, lengths, out, (float*)((char*)state_ws + 256), save_gates, save_c,
-                (unsigned*)state_ws, U, L, rnn_status_dev(), g_spin};
-  hipLaunchKernelGGL(lstm_fwd_kernel, dim3(2 * L_NWG), dim3(256), 0, s, a);
-  WSMG_RETURN_LAUNCH();
-}
-
-extern "C" int wsmg_lstm_bwd(const float* dout, const float* w_hh, const int32_t* lengths, const float* save_gates,
-                             const float* save_c, int U, int L, int hidden, float* dgates, void* state_ws,
-                             wsmg_stream_t stream) {
-  if (hidden != LH || U <= 0 || U > NB || L <= 0) return WSMG_EINVAL;
-  hipStream_t s = wsmg_s(stream);
-  if (((uintptr_t)state_ws & 127) != 0) return WSMG_EINVAL;
-  hipError_t e = hipMemsetAsync(state_ws, 0, 256, s);
-  if (e != hipSuccess) return (int)e;
-  LstmBwdArgs a{dout, w_hh, lengths, save_gates, save_c, dgates, (unsigned*)state_ws, (float*)((char*)state_ws + 256), U, L, rnn_status_dev(), g_spin};
-  hipLaunchKernelGGL(lstm_bwd_kernel, dim3(2 * L_NWG), dim3(256), 0, s, a);
-  WSMG_RETURN_LAUNCH();
-}
-
-// =================================================================================================
-// Persistent packed instruction recurrences for the other three MODEL.INSTRUCTION_ENCODER settings the policy admits
-// (output width 256): GRU bidirectional hidden 128, LSTM unidirectional hidden 256, GRU unidirectional hidden 256.
-// The default bidirectional LSTM keeps lstm_fwd_kernel / lstm_bwd_kernel above, untouched.  Same structure: 256 hidden
-// units in flight per launch (DIRS x HID), 16 workgroups x 4 waves, 4 units per wave; the K = HID reduction is split
-// over the 64 lanes (HID / 64 per lane); one bounded grid barrier per token step and direction.  Packed-sequence
-// semantics as above.  GRU: PyTorch's r, z, n with n = tanh(gi_n + r * (W_hn h + b_hn)), h' = (1 - z) n + z h; its 12
-// gate rows per wave are padded to 16 in the reduction so that the lane layout of the LSTM carries over (lanes 48-63
-// hold the empty fourth gate).  Saved for the backward: LSTM i, f, g, o and c; GRU r, z, n and W_hn h + b_hn.
+// Persistent packed instruction recurrences: the instruction encoder's packed nn.LSTM / nn.GRU (instruction_encoder.py:80-93)
+// over U <= 8 unique instructions per launch, one launch forward and one backward instead of about 10 MIOpen launches per
+// token step and direction.  The four MODEL.INSTRUCTION_ENCODER settings the policy admits (output width 256) are the
+// instantiations <CELL, HID>: the default bidirectional LSTM with hidden 128, GRU bidirectional hidden 128, and LSTM or GRU
+// unidirectional hidden 256.  Each keeps 256 hidden units in flight per launch (DIRS x HID): 16 workgroups x 4 waves, 4 units
+// per wave whose gate rows of W_hh stay in registers; the K = HID reduction is split over the 64 lanes (HID / 64 per lane)
+// and combined by a halving butterfly; one bounded grid barrier per token step and direction, both directions concurrently.
+// Packed-sequence semantics: row b is active at step t iff t < len[b]; inactive steps freeze the state and emit 0 (forward
+// direction: after the end; reverse direction: before its first token); the initial state is zero.
+// LSTM: gate order i, f, g, o (PyTorch nn.LSTM).  GRU: PyTorch's r, z, n with n = tanh(gi_n + r * (W_hn h + b_hn)),
+// h' = (1 - z) n + z h; its 12 gate rows per wave are padded to 16 in the reduction so that the lane layout of the LSTM
+// carries over (lanes 48-63 hold the empty fourth gate).  Saved for the backward: LSTM i, f, g, o and c; GRU r, z, n and
+// W_hn h + b_hn.  gi = x W_ih^T + b_ih of all directions is one GEMM done by the caller; so are dW_hh / dW_ih.
+// Timeout status bits: 4 / 8 (lstm_fwd / lstm_bwd) for the default bidirectional LSTM, 128 / 256 (instr_rnn_fwd / _bwd)
+// for the other three settings.
 namespace {
 
 template <int CELL, int HID>
@@ -1332,6 +1080,9 @@ struct IrnnShape {
   static constexpr int KL = HID / 64;                        // forward: K elements per lane
   static constexpr int E = (G * HID / 64) % 4 == 0 ? 4 : 2;  // backward: consecutive W_hh rows per lane and chunk
   static constexpr int Q = G * HID / (64 * E);               // backward: chunks
+  static constexpr bool BILSTM = CELL == WSMG_CELL_LSTM && HID == 128;   // the default encoder
+  static constexpr unsigned FWD_BIT = BILSTM ? 4u : 128u;       // status bits on a timeout
+  static constexpr unsigned BWD_BIT = BILSTM ? 8u : 256u;
 };
 
 struct IrnnFwdArgs {
@@ -1459,7 +1210,7 @@ __global__ __launch_bounds__(256) void irnn_fwd_kernel(IrnnFwdArgs a) {
     }
     if (s + 1 < a.L) {
       if (!grid_barrier(sync, (unsigned)NWG_D * (unsigned)(s + 1), tid, &ok_lds, a.spin)) {
-        rnn_fail(a.status, 128u);
+        rnn_fail(a.status, S::FWD_BIT);
         rnn_poison(a.out, (size_t)a.U * a.L, DIRS * HID, dir * HID + wgi * UNITS_WG, UNITS_WG);
         return;
       }
@@ -1573,7 +1324,7 @@ __global__ __launch_bounds__(256) void irnn_bwd_kernel(IrnnBwdArgs a) {
       }
     }
     if (!grid_barrier(sync, (unsigned)NWG_D * (unsigned)(a.L - s), tid, &ok_lds, a.spin)) {
-      rnn_fail(a.status, 256u);
+      rnn_fail(a.status, S::BWD_BIT);
       for (int g = 0; g < G; ++g) {
         rnn_poison(a.dgi, (size_t)a.U * a.L, DIRS * G * HID, dir * G * HID + g * HID + wgi * UNITS_WG, UNITS_WG);
         if (CELL != WSMG_CELL_LSTM)
@@ -1615,6 +1366,17 @@ bool irnn_supported(int cell, int hidden, int dirs) {
          (cell == WSMG_CELL_LSTM && hidden == 256 && dirs == 1) || (cell == WSMG_CELL_GRU && hidden == 256 && dirs == 1);
 }
 
+// launches the instantiation for (cell, hidden), one of the four irnn_supported() admits
+template <int CELL, int HID>
+void irnn_launch(const IrnnFwdArgs& a, hipStream_t s) { hipLaunchKernelGGL((irnn_fwd_kernel<CELL, HID>), dim3(16), dim3(256), 0, s, a); }
+template <int CELL, int HID>
+void irnn_launch(const IrnnBwdArgs& a, hipStream_t s) { hipLaunchKernelGGL((irnn_bwd_kernel<CELL, HID>), dim3(16), dim3(256), 0, s, a); }
+template <class Args>
+void irnn_launch(int cell, int hidden, const Args& a, hipStream_t s) {
+  if (cell == WSMG_CELL_LSTM) hidden == 128 ? irnn_launch<WSMG_CELL_LSTM, 128>(a, s) : irnn_launch<WSMG_CELL_LSTM, 256>(a, s);
+  else hidden == 128 ? irnn_launch<WSMG_CELL_GRU, 128>(a, s) : irnn_launch<WSMG_CELL_GRU, 256>(a, s);
+}
+
 }  // namespace
 
 // per token: forward image NB x 256 floats, backward image G times that (both shapes keep 256 units in flight)
@@ -1629,16 +1391,12 @@ extern "C" int wsmg_instr_rnn_fwd(int cell, const float* gi, const float* w_hh, 
   if (!irnn_supported(cell, hidden, dirs) || U <= 0 || U > NB || L <= 0) return WSMG_EINVAL;
   if (((uintptr_t)state_ws & 127) != 0 || !gi || !w_hh || !b_hh || !lengths || !out || !save_gates) return WSMG_EINVAL;
   if (cell == WSMG_CELL_LSTM && !save_c) return WSMG_EINVAL;
-  if (cell == WSMG_CELL_LSTM && hidden == LH)          // the default encoder: its own kernel, unchanged
-    return wsmg_lstm_fwd(gi, w_hh, b_hh, lengths, U, L, hidden, out, save_gates, save_c, state_ws, stream);
   hipStream_t s = wsmg_s(stream);
   hipError_t e = hipMemsetAsync(state_ws, 0, 256, s);   // barrier words
   if (e != hipSuccess) return (int)e;
   IrnnFwdArgs a{gi, w_hh, b_hh, lengths, out, (float*)((char*)state_ws + 256), save_gates, save_c,
                 (unsigned*)state_ws, U, L, rnn_status_dev(), g_spin};
-  if (cell == WSMG_CELL_GRU && hidden == 128) hipLaunchKernelGGL((irnn_fwd_kernel<WSMG_CELL_GRU, 128>), dim3(16), dim3(256), 0, s, a);
-  else if (cell == WSMG_CELL_GRU) hipLaunchKernelGGL((irnn_fwd_kernel<WSMG_CELL_GRU, 256>), dim3(16), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((irnn_fwd_kernel<WSMG_CELL_LSTM, 256>), dim3(16), dim3(256), 0, s, a);
+  irnn_launch(cell, hidden, a, s);
   WSMG_RETURN_LAUNCH();
 }
 
@@ -1648,15 +1406,25 @@ extern "C" int wsmg_instr_rnn_bwd(int cell, const float* dout, const float* w_hh
   if (!irnn_supported(cell, hidden, dirs) || U <= 0 || U > NB || L <= 0) return WSMG_EINVAL;
   if (((uintptr_t)state_ws & 127) != 0 || !dout || !w_hh || !lengths || !save_gates || !dgi) return WSMG_EINVAL;
   if (cell == WSMG_CELL_LSTM ? !save_c : (!out || !dgh)) return WSMG_EINVAL;
-  if (cell == WSMG_CELL_LSTM && hidden == LH)
-    return wsmg_lstm_bwd(dout, w_hh, lengths, save_gates, save_c, U, L, hidden, dgi, state_ws, stream);
   hipStream_t s = wsmg_s(stream);
   hipError_t e = hipMemsetAsync(state_ws, 0, 256, s);
   if (e != hipSuccess) return (int)e;
   IrnnBwdArgs a{dout, w_hh, lengths, out, save_gates, save_c, dgi, dgh, (unsigned*)state_ws, (float*)((char*)state_ws + 256),
                 U, L, rnn_status_dev(), g_spin};
-  if (cell == WSMG_CELL_GRU && hidden == 128) hipLaunchKernelGGL((irnn_bwd_kernel<WSMG_CELL_GRU, 128>), dim3(16), dim3(256), 0, s, a);
-  else if (cell == WSMG_CELL_GRU) hipLaunchKernelGGL((irnn_bwd_kernel<WSMG_CELL_GRU, 256>), dim3(16), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((irnn_bwd_kernel<WSMG_CELL_LSTM, 256>), dim3(16), dim3(256), 0, s, a);
+  irnn_launch(cell, hidden, a, s);
   WSMG_RETURN_LAUNCH();
+}
+
+// the default encoder's entry points: (WSMG_CELL_LSTM, hidden 128, 2 directions) of the above
+extern "C" int64_t wsmg_lstm_workspace_bytes(int L) { return wsmg_instr_rnn_workspace_bytes(WSMG_CELL_LSTM, 128, 2, L); }
+
+extern "C" int wsmg_lstm_fwd(const float* gi, const float* w_hh, const float* b_hh, const int32_t* lengths, int U, int L,
+                             int hidden, float* out, float* save_gates, float* save_c, void* state_ws, wsmg_stream_t stream) {
+  return wsmg_instr_rnn_fwd(WSMG_CELL_LSTM, gi, w_hh, b_hh, lengths, U, L, hidden, 2, out, save_gates, save_c, state_ws, stream);
+}
+
+extern "C" int wsmg_lstm_bwd(const float* dout, const float* w_hh, const int32_t* lengths, const float* save_gates,
+                             const float* save_c, int U, int L, int hidden, float* dgates, void* state_ws, wsmg_stream_t stream) {
+  return wsmg_instr_rnn_bwd(WSMG_CELL_LSTM, dout, w_hh, lengths, nullptr, save_gates, save_c, U, L, hidden, 2, dgates, nullptr,
+                            state_ws, stream);
 }

@@ -165,8 +165,8 @@ class InstructionEncoder(nn.Module):
         """-> (hidden [U, L, D] token-major, pad mask [U, L] bool, inverse [B]) with U unique rows.
         stock=False: persistent HIP GRU / LSTM (csrc/wsmg_rnn.hip) for the shapes they take (`kernel_cell`), the stock route for
         any other; stock=True: nn.GRU / nn.LSTM on a packed sequence (MIOpen / CPU), kept for comparison in tests.  dedup: the result of `dedup()` for these tokens, if the caller
-        already has it (no host read-back here then).  lstm_after: an event the persistent LSTM launch waits for (the dedup, the
-        embedding and the input projection do not)."""
+        already has it (no host read-back here then).  lstm_after: an event the persistent GRU / LSTM launches wait for (the
+        dedup, the embedding and the input projection do not)."""
         uniq, inverse, len_host, len_dev = self.dedup(instruction) if dedup is None else dedup
         from ...debug import sw
         cell = self.kernel_cell
@@ -188,10 +188,7 @@ class InstructionEncoder(nn.Module):
             lens = len_dev.to(torch.int32)
             if lstm_after is not None:
                 torch.cuda.current_stream().wait_event(lstm_after)
-            if cell == "LSTM" and self.bidir:      # the default encoder
-                parts = [ops.bilstm(gi[c:c + 8], w_hh, b_hh, lens[c:c + 8]) for c in range(0, U, 8)]
-            else:
-                parts = [ops.instr_rnn(gi[c:c + 8], w_hh, b_hh, lens[c:c + 8], cell) for c in range(0, U, 8)]
+            parts = [ops.instr_rnn(gi[c:c + 8], w_hh, b_hh, lens[c:c + 8], cell) for c in range(0, U, 8)]
             hidden = parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
         mask = (hidden == 0.0).all(dim=2)
         return hidden.contiguous(), mask, inverse

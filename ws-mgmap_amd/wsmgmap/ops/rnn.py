@@ -1,4 +1,4 @@
-"""wsmgmap.ops.rnn — the persistent masked-GRU / masked-LSTM state-encoder and packed bi-LSTM sequence kernels.
+"""wsmgmap.ops.rnn — the persistent masked-GRU / masked-LSTM state-encoder and packed instruction GRU / LSTM kernels.
 """
 import ctypes
 
@@ -118,55 +118,6 @@ def masked_lstm(gi, w_hh, b_hh, h0, c0, masks):
                              masks.contiguous())
 
 
-# ----------------------------------------------------------------------------- persistent packed bi-LSTM
-class _BiLSTM(torch.autograd.Function):
-    """gi [U,L,2,4H], w_hh [2,4H,H], b_hh [2,4H], lengths int32 [U] -> out [U,L,2H]."""
-
-    @staticmethod
-    def forward(ctx, gi, w_hh, b_hh, lengths):
-        _req(gi, w_hh, b_hh, lengths)
-        _f32(gi, w_hh, b_hh)
-        U, L, _, H4 = gi.shape
-        H = H4 // 4
-        dev = gi.device
-        out = torch.empty(U, L, 2 * H, device=dev, dtype=torch.float32)
-        sg = torch.zeros(2, U, L, 4, H, device=dev, dtype=torch.float32)
-        sc = torch.zeros(2, U, L, H, device=dev, dtype=torch.float32)
-        ws = _rnn_workspace(_abi.lib().wsmg_lstm_workspace_bytes(L), dev)
-        _abi.call("wsmg_lstm_fwd", _p(gi), _p(w_hh), _p(b_hh), _p(lengths), U, L, H, _p(out), _p(sg), _p(sc), _p(ws), _stream())
-        _rnn_launched()
-        ctx.save_for_backward(w_hh, lengths, out, sg, sc)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        w_hh, lengths, out, sg, sc = ctx.saved_tensors
-        U, L, H2 = out.shape
-        H = H2 // 2
-        dev = out.device
-        dout = dout.contiguous()
-        dg = torch.empty(U, L, 2, 4 * H, device=dev, dtype=torch.float32)
-        ws = _rnn_workspace(_abi.lib().wsmg_lstm_workspace_bytes(L), dev)
-        _abi.call("wsmg_lstm_bwd", _p(dout), _p(w_hh), _p(lengths), _p(sg), _p(sc), U, L, H, _p(dg), _p(ws), _stream())
-        _rnn_launched()
-        zero = torch.zeros(U, 1, H, device=dev, dtype=torch.float32)
-        hprev_f = torch.cat([zero, out[:, :-1, :H]], dim=1)       # state before step t (forward direction)
-        hprev_r = torch.cat([out[:, 1:, H:], zero], dim=1)        # state before step t (reverse direction)
-        # one direction's gate gradients as a contiguous [U L, 4H] matrix first: on the strided view dg[:, :, d] (row pitch 8H)
-        # the GEMM library picked a 32 x 16 tile kernel that took 340 us for this 0.7 GFLOP product (beside the map stack's
-        # backward, on the instruction stream)
-        dgd = dg.permute(2, 0, 1, 3).contiguous().view(2, U * L, 4 * H)
-        dw = torch.stack([dgd[0].t() @ hprev_f.reshape(U * L, H), dgd[1].t() @ hprev_r.reshape(U * L, H)])
-        from .heads import colsum_multi    # stock sum over (0, 1) of the strided view: 324 us on the instruction stream
-        db = torch.stack(colsum_multi([dgd[0], dgd[1]]))
-        return dg, dw, db, None
-
-
-def bilstm(gi, w_hh, b_hh, lengths):
-    """Packed bidirectional LSTM over <= 8 sequences in one persistent launch."""
-    return _BiLSTM.apply(gi.contiguous(), w_hh.contiguous(), b_hh.contiguous(), lengths.contiguous())
-
-
 # ----------------------------------------------------------------------------- persistent packed instruction GRU / LSTM
 CELLS = {"LSTM": 0, "GRU": 1}        # WSMG_CELL_* of include/wsmgmap.h
 INSTR_RNN_SHAPES = ((128, 2), (256, 1))   # (hidden, directions) the kernels take: 256 units in flight
@@ -217,10 +168,12 @@ class _InstrRNN(torch.autograd.Function):
         hprev = [torch.cat([zero, out[:, :-1, :H]], dim=1)]               # state before step t (forward direction)
         if D == 2:
             hprev.append(torch.cat([out[:, 1:, H:], zero], dim=1))        # state before step t (reverse direction)
-        # per direction a contiguous [U L, G H] matrix (see _BiLSTM.backward)
+        # one direction's gate gradients as a contiguous [U L, G H] matrix first: on the strided view dgi[:, :, d] (row pitch
+        # D G H) the GEMM library picked a 32 x 16 tile kernel that took 340 us for the default encoder's 0.7 GFLOP product
+        # (beside the map stack's backward, on the instruction stream)
         dgd = (dgi if dgh is None else dgh).permute(2, 0, 1, 3).contiguous().view(D, U * L, GH)
         dw = torch.stack([dgd[d].t() @ hprev[d].reshape(U * L, H) for d in range(D)])
-        from .heads import colsum_multi
+        from .heads import colsum_multi    # stock sum over (0, 1) of the strided view: 324 us on the instruction stream
         db = torch.stack(colsum_multi([dgd[d] for d in range(D)]))
         return dgi, dw, db, None, None
 
@@ -228,3 +181,8 @@ class _InstrRNN(torch.autograd.Function):
 def instr_rnn(gi, w_hh, b_hh, lengths, cell):
     """Packed instruction GRU / LSTM (hidden 128 x 2 directions or 256 x 1) over <= 8 sequences in one persistent launch."""
     return _InstrRNN.apply(gi.contiguous(), w_hh.contiguous(), b_hh.contiguous(), lengths.contiguous(), cell)
+
+
+def bilstm(gi, w_hh, b_hh, lengths):
+    """The default encoder's packed bidirectional LSTM (hidden 128) over <= 8 sequences: instr_rnn with cell "LSTM"."""
+    return instr_rnn(gi, w_hh, b_hh, lengths, "LSTM")
