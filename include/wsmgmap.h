@@ -641,6 +641,22 @@ int wsmg_gru_bwd_chain(const float* dy, const float* dhT, const float* w_hh, con
                        void* sync_ws, int steps_per_chunk, const unsigned* in_count, unsigned in_target, unsigned* out_count,
                        wsmg_stream_t stream);
 int wsmg_gru_chain_workgroups(void);
+/* The same chaining for the persistent LSTM state encoders (the recurrent core of an LSTM policy): wsmg_lstm_state_fwd / _bwd's
+ * arguments plus (steps_per_chunk, in_count, in_target, out_count) as above.  The forward waits before reading a chunk's gi and
+ * reports the chunk when its y, save_gates and save_c are stored; the backward waits before reading a chunk's dy and reports the
+ * chunk when its dgates are stored; each adds wsmg_lstm_state_chain_workgroups() arrivals per chunk.  The workspace is the
+ * caller's, zeroed once and never cleared by these calls (zeroed again after a reported timeout: the error word is sticky).
+ * steps_per_chunk <= 0 or not dividing T, hidden != 512, N > 8, T > 1023, a misaligned workspace or a NULL pointer the call
+ * needs returns WSMG_EINVAL before anything is enqueued (dhT, dcT, in_count, out_count may be NULL).  Timeouts: bits 32 / 64. */
+int wsmg_lstm_state_fwd_chain(const float* gi, const float* w_hh, const float* b_hh, const float* h0, const float* c0,
+                              const float* masks, int T, int N, int hidden, float* y, float* c_T, float* save_gates,
+                              float* save_c, void* sync_ws, int steps_per_chunk, const unsigned* in_count, unsigned in_target,
+                              unsigned* out_count, wsmg_stream_t stream);
+int wsmg_lstm_state_bwd_chain(const float* dy, const float* dhT, const float* dcT, const float* w_hh, const float* c0,
+                              const float* masks, const float* save_gates, const float* save_c, int T, int N, int hidden,
+                              float* dgates, float* dh0, float* dc0, void* sync_ws, int steps_per_chunk, const unsigned* in_count,
+                              unsigned in_target, unsigned* out_count, wsmg_stream_t stream);
+int wsmg_lstm_state_chain_workgroups(void);
 int wsmg_rnn_debug_spin_limit(unsigned limit);
 
 /* ---- the update path's heads, auxiliary-loss reduction and trainer loss (csrc/wsmg_heads.hip) ----------------------------

@@ -7,7 +7,7 @@ feeds them the seeded inputs of oracle/cases.py with weights from oracle/detfill
 writes small .npz fixtures (data only: inputs are re-derivable, outputs are digests /
 small tensors) to tests/golden/.
 
-    python tools/make_goldens.py [g1 g2 g3 g4 g5 ... g12]
+    python tools/make_goldens.py [g1 g2 g3 g4 g5 ... g13]
 """
 import hashlib
 import os
@@ -173,16 +173,16 @@ def g3():
     np.savez_compressed(os.path.join(OUT, "g3_update.npz"), **out)
 
 
-def _update_golden(rnn_type="GRU", restarts=(), **instr):
-    """One teacher-forcing update of the reference policy (T = 4, N = 2) on cases.update_inputs; `restarts`: extra (t, n)
-    episode starts set to 0 in the masks; `instr`: the instruction encoder's settings (model_config)."""
+def _update_golden(rnn_type="GRU", restarts=(), T_=4, N=2, inputs=None, **instr):
+    """One teacher-forcing update of the reference policy (T_ steps x N environments, default 4 x 2) on cases.update_inputs (extra
+    keyword arguments of it: `inputs`); `restarts`: extra (t, n) episode starts set to 0 in the masks; `instr`: the instruction
+    encoder's settings (model_config)."""
     from vlnce_baselines.common.aux_losses import AuxLosses
     pol = build_policy(rnn_type=rnn_type, **instr)
     pol.train()
     pol.net.depth_encoder.eval()
     pol.net.rgb_encoder.eval()
-    T_, N = 4, 2
-    obs_np, prev, masks, weights = cases.update_inputs(T_, N)
+    obs_np, prev, masks, weights = cases.update_inputs(T_, N, **(inputs or {}))
     for t, n in restarts:
         masks[t * N + n] = 0.0
     obs = {k: T(v) for k, v in obs_np.items()}
@@ -262,6 +262,16 @@ def g10():
     print("g10 pred", out["pred"].ravel()[:4], "aux", float(out["aux_loss"]), "loss", float(out["loss"]),
           "h_out", out["h_out"].shape)
     np.savez_compressed(os.path.join(OUT, "g10_lstm_update.npz"), **out)
+
+
+# ============================================================================= G13
+def g13():
+    """The LSTM policy of g10 on a batch the pipelined recurrent core takes: T = 8, N = 4 (4 chunks of 2 steps by default), four
+    instructions of 80 / 37 / 1 / 55 tokens, and one more restart inside a chunk (t = 5, column 2)."""
+    out = _update_golden("LSTM", restarts=((5, 2),), T_=8, N=4, inputs=dict(n_tok=(80, 37, 1, 55), tag="g13"))
+    print("g13 pred", out["pred"].ravel()[:4], "aux", float(out["aux_loss"]), "loss", float(out["loss"]),
+          "h_out", out["h_out"].shape)
+    np.savez_compressed(os.path.join(OUT, "g13_lstm_core_update.npz"), **out)
 
 
 # ============================================================================= G11 / G12
@@ -437,6 +447,6 @@ def g8():
 
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["shapes", "g1", "g2", "g3", "g4", "g5", "g5f", "g8", "g9", "g10", "g11", "g12"]
+    which = sys.argv[1:] or ["shapes", "g1", "g2", "g3", "g4", "g5", "g5f", "g8", "g9", "g10", "g11", "g12", "g13"]
     for w in which:
         globals()[w]()

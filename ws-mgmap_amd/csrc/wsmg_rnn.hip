@@ -720,6 +720,8 @@ __attribute__((visibility("hidden"))) unsigned* wsmgi_rnn_status_dev() { return 
 //   * backward: the producer multiplies its 64 resident gate rows with its own gate gradients and publishes the
 //     partial sums of dh_{t-1} (gru_bwd8's ring); the dc recursion dc_{t-1} = dc_t f_t mask_t stays in the owning
 //     thread.  For an LSTM the gradients of gi and of W_hh h + b_hh are the same tensor: one output, dgates.
+// Both take the GRU pair's chaining hooks (chain_wait / chain_signal by time chunk), so the pipelined recurrent core runs an LSTM
+// policy as one launch per recurrence too (wsmg_lstm_state_*_chain; Tc = 0 in the plain entry points: no wait, no signal).
 // Status bits 32 (forward) and 64 (backward).
 namespace {
 
@@ -740,6 +742,11 @@ struct LstmStateFwdArgs {
   unsigned tagbase;
   unsigned* status;
   unsigned spin;
+  // chaining by time chunk, as GruFwdArgs: steps per chunk (0: none), the counters gi's chunks are ready behind / this launch reports on
+  int Tc;
+  const unsigned* in_cnt;
+  unsigned in_target;
+  unsigned* out_cnt;
 };
 
 __device__ __forceinline__ void lstm_state_fwd_fail(const LstmStateFwdArgs& a) {
@@ -773,6 +780,10 @@ __global__ __launch_bounds__(512) void lstm_state_fwd8_kernel(LstmStateFwdArgs a
   const int sw = tid >> 4, sb = (tid >> 1) & 7, sh = tid & 1;
   const int xw = (blockIdx.x * NB + my_b) * UNITS_WG + wave * UNITS_WAVE + grp;
   for (int t = 0; t < a.T; ++t) {
+    if (a.in_cnt && t % a.Tc == 0 && !chain_wait(a.in_cnt + t / a.Tc, a.in_target, a.sync, a.spin, tid)) {   // gi of this chunk is not there yet
+      lstm_state_fwd_fail(a);
+      return;
+    }
     float (*hcur)[H] = hs[t & 1];
     float xi = 0.f, xf = 0.f, xg = 0.f, xo = 0.f, mk = 0.f;
     const size_t orow = (size_t)t * a.N + my_b;
@@ -852,6 +863,7 @@ __global__ __launch_bounds__(512) void lstm_state_fwd8_kernel(LstmStateFwdArgs a
       a.sc[orow * H + my_unit] = c;
       if (t + 1 == a.T) a.cT[(size_t)my_b * H + my_unit] = c;
     }
+    if (a.out_cnt && (t + 1) % a.Tc == 0) chain_signal(a.out_cnt + t / a.Tc, tid);   // y, save_gates, save_c of this chunk are complete (this workgroup's part)
   }
 }
 
@@ -873,6 +885,11 @@ struct LstmStateBwdArgs {
   unsigned tagbase;
   unsigned* status;
   unsigned spin;
+  // chaining by time chunk, as GruBwdArgs: steps per chunk (0: none), the counters dy's chunks are ready behind / this launch reports on
+  int Tc;
+  const unsigned* in_cnt;
+  unsigned in_target;
+  unsigned* out_cnt;
 };
 
 __device__ __forceinline__ void lstm_state_bwd_fail(const LstmStateBwdArgs& a) {
@@ -905,6 +922,10 @@ __global__ __launch_bounds__(512) void lstm_state_bwd8_kernel(LstmStateBwdArgs a
   float mk_next = 0.f, dc_carry = 0.f;   // dc_carry: gradient reaching c_t from step t + 1 (already times f_{t+1} mask_{t+1})
   if (worker && a.dcT) dc_carry = a.dcT[(size_t)wb * H + my_unit];
   for (int t = a.T - 1; t >= -1; --t) {
+    if (a.in_cnt && t >= 0 && t % a.Tc == a.Tc - 1 && !chain_wait(a.in_cnt + t / a.Tc, a.in_target, a.sync, a.spin, tid)) {   // dy of this chunk
+      lstm_state_bwd_fail(a);
+      return;
+    }
     float dyv = 0.f, ig = 0.f, fg = 0.f, gg = 0.f, og = 0.f, ct = 0.f, cprev = 0.f, mk = 0.f;
     size_t row = 0;
     if (worker && t >= 0) {
@@ -1016,6 +1037,7 @@ __global__ __launch_bounds__(512) void lstm_state_bwd8_kernel(LstmStateBwdArgs a
         __hip_atomic_store(dst + b * UNITS_WG + 1, tag | __float_as_uint(v1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
+    if (a.out_cnt && t % a.Tc == 0) chain_signal(a.out_cnt + t / a.Tc, tid);   // dgates of this chunk are complete (this workgroup's part)
   }
 }
 
@@ -1024,35 +1046,72 @@ __global__ __launch_bounds__(512) void lstm_state_bwd8_kernel(LstmStateBwdArgs a
 // same exchange image / ring as the GRU kernels: the h values crossing workgroups per step are the same 4096 words
 extern "C" int64_t wsmg_lstm_state_workspace_bytes(int T) { return wsmg_gru_workspace_bytes(T); }
 
-extern "C" int wsmg_lstm_state_fwd(const float* gi, const float* w_hh, const float* b_hh, const float* h0, const float* c0,
-                                   const float* masks, int T, int N, int hidden, float* y, float* c_T, float* save_gates,
-                                   float* save_c, void* sync_ws, wsmg_stream_t stream) {
+// clear: the plain entry points zero the control words and the exchange image per launch (as wsmg_gru_fwd); the chained ones run
+// on a workspace the caller owns and zeroed once (as wsmg_gru_*_chain)
+static int lstm_state_fwd_launch(const float* gi, const float* w_hh, const float* b_hh, const float* h0, const float* c0, const float* masks,
+                                 int T, int N, int hidden, float* y, float* c_T, float* save_gates, float* save_c, void* sync_ws,
+                                 hipStream_t s, bool clear, int Tc = 0, const unsigned* in_cnt = nullptr, unsigned in_target = 0,
+                                 unsigned* out_cnt = nullptr) {
   if (hidden != H || T <= 0 || N <= 0 || N > NB) return WSMG_EINVAL;
   if (((uintptr_t)sync_ws & 127) != 0) return WSMG_EINVAL;
   if (T > 1023) return WSMG_EINVAL;
-  hipStream_t s = wsmg_s(stream);
-  hipError_t e = hipMemsetAsync(sync_ws, 0, 256 + (size_t)T * NWG * NB * UNITS_WG * 8, s);   // as wsmg_gru_fwd
-  if (e != hipSuccess) return (int)e;
+  if (!gi || !w_hh || !b_hh || !h0 || !c0 || !masks || !y || !c_T || !save_gates || !save_c || !sync_ws) return WSMG_EINVAL;
+  hipError_t e = hipSuccess;
+  if (clear && (e = hipMemsetAsync(sync_ws, 0, 256 + (size_t)T * NWG * NB * UNITS_WG * 8, s)) != hipSuccess) return (int)e;
   LstmStateFwdArgs a{gi, w_hh, b_hh, h0, c0, masks, y, c_T, save_gates, save_c, (unsigned*)sync_ws,
-                     (unsigned long long*)((char*)sync_ws + 256), T, N, next_tagbase(), rnn_status_dev(), g_spin};
+                     (unsigned long long*)((char*)sync_ws + 256), T, N, next_tagbase(), rnn_status_dev(), g_spin, Tc, in_cnt, in_target, out_cnt};
   hipLaunchKernelGGL(lstm_state_fwd8_kernel, dim3(NWG), dim3(512), 0, s, a);
   WSMG_RETURN_LAUNCH();
+}
+
+static int lstm_state_bwd_launch(const float* dy, const float* dhT, const float* dcT, const float* w_hh, const float* c0, const float* masks,
+                                 const float* save_gates, const float* save_c, int T, int N, int hidden, float* dgates, float* dh0,
+                                 float* dc0, void* sync_ws, hipStream_t s, bool clear, int Tc = 0, const unsigned* in_cnt = nullptr,
+                                 unsigned in_target = 0, unsigned* out_cnt = nullptr) {
+  if (hidden != H || T <= 0 || N <= 0 || N > NB) return WSMG_EINVAL;
+  if (((uintptr_t)sync_ws & 127) != 0) return WSMG_EINVAL;
+  if (T > 1023) return WSMG_EINVAL;
+  if (!dy || !w_hh || !c0 || !masks || !save_gates || !save_c || !dgates || !dh0 || !dc0 || !sync_ws) return WSMG_EINVAL;
+  hipError_t e = hipSuccess;
+  if (clear && (e = hipMemsetAsync(sync_ws, 0, 256 + (size_t)BWD_RING * XP_SLOT * 8, s)) != hipSuccess) return (int)e;
+  LstmStateBwdArgs a{dy, dhT, dcT, w_hh, c0, masks, save_gates, save_c, dgates, dh0, dc0, (unsigned*)sync_ws,
+                     (unsigned long long*)((char*)sync_ws + 256), T, N, next_tagbase(), rnn_status_dev(), g_spin, Tc, in_cnt, in_target, out_cnt};
+  hipLaunchKernelGGL(lstm_state_bwd8_kernel, dim3(NWG), dim3(512), 0, s, a);
+  WSMG_RETURN_LAUNCH();
+}
+
+extern "C" int wsmg_lstm_state_fwd(const float* gi, const float* w_hh, const float* b_hh, const float* h0, const float* c0,
+                                   const float* masks, int T, int N, int hidden, float* y, float* c_T, float* save_gates,
+                                   float* save_c, void* sync_ws, wsmg_stream_t stream) {
+  return lstm_state_fwd_launch(gi, w_hh, b_hh, h0, c0, masks, T, N, hidden, y, c_T, save_gates, save_c, sync_ws, wsmg_s(stream), true);
 }
 
 extern "C" int wsmg_lstm_state_bwd(const float* dy, const float* dhT, const float* dcT, const float* w_hh, const float* c0,
                                    const float* masks, const float* save_gates, const float* save_c, int T, int N, int hidden,
                                    float* dgates, float* dh0, float* dc0, void* sync_ws, wsmg_stream_t stream) {
-  if (hidden != H || T <= 0 || N <= 0 || N > NB) return WSMG_EINVAL;
-  if (((uintptr_t)sync_ws & 127) != 0) return WSMG_EINVAL;
-  if (T > 1023) return WSMG_EINVAL;
-  hipStream_t s = wsmg_s(stream);
-  hipError_t e = hipMemsetAsync(sync_ws, 0, 256 + (size_t)BWD_RING * XP_SLOT * 8, s);   // as wsmg_gru_bwd
-  if (e != hipSuccess) return (int)e;
-  LstmStateBwdArgs a{dy, dhT, dcT, w_hh, c0, masks, save_gates, save_c, dgates, dh0, dc0, (unsigned*)sync_ws,
-                     (unsigned long long*)((char*)sync_ws + 256), T, N, next_tagbase(), rnn_status_dev(), g_spin};
-  hipLaunchKernelGGL(lstm_state_bwd8_kernel, dim3(NWG), dim3(512), 0, s, a);
-  WSMG_RETURN_LAUNCH();
+  return lstm_state_bwd_launch(dy, dhT, dcT, w_hh, c0, masks, save_gates, save_c, T, N, hidden, dgates, dh0, dc0, sync_ws, wsmg_s(stream), true);
 }
+
+// Whole-sequence LSTM launches chained by time chunk (the pipelined recurrent core with rnn_type "LSTM"): the contract of
+// wsmg_gru_fwd_chain / _bwd_chain.  The forward reports a chunk when its y, save_gates and save_c are stored, the backward when its
+// dgates are; the forward waits before reading the chunk's gi, the backward before reading its dy.
+extern "C" int wsmg_lstm_state_fwd_chain(const float* gi, const float* w_hh, const float* b_hh, const float* h0, const float* c0,
+                                         const float* masks, int T, int N, int hidden, float* y, float* c_T, float* save_gates,
+                                         float* save_c, void* sync_ws, int steps_per_chunk, const unsigned* in_count, unsigned in_target,
+                                         unsigned* out_count, wsmg_stream_t stream) {
+  if (steps_per_chunk <= 0 || T % steps_per_chunk) return WSMG_EINVAL;
+  return lstm_state_fwd_launch(gi, w_hh, b_hh, h0, c0, masks, T, N, hidden, y, c_T, save_gates, save_c, sync_ws, wsmg_s(stream), false,
+                               steps_per_chunk, in_count, in_target, out_count);
+}
+extern "C" int wsmg_lstm_state_bwd_chain(const float* dy, const float* dhT, const float* dcT, const float* w_hh, const float* c0,
+                                         const float* masks, const float* save_gates, const float* save_c, int T, int N, int hidden,
+                                         float* dgates, float* dh0, float* dc0, void* sync_ws, int steps_per_chunk, const unsigned* in_count,
+                                         unsigned in_target, unsigned* out_count, wsmg_stream_t stream) {
+  if (steps_per_chunk <= 0 || T % steps_per_chunk) return WSMG_EINVAL;
+  return lstm_state_bwd_launch(dy, dhT, dcT, w_hh, c0, masks, save_gates, save_c, T, N, hidden, dgates, dh0, dc0, sync_ws, wsmg_s(stream), false,
+                               steps_per_chunk, in_count, in_target, out_count);
+}
+extern "C" int wsmg_lstm_state_chain_workgroups(void) { return NWG; }
 
 // =================================================================================================
 // Persistent packed instruction recurrences: the instruction encoder's packed nn.LSTM / nn.GRU (instruction_encoder.py:80-93)

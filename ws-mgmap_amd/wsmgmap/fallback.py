@@ -1,6 +1,6 @@
 """In-process fallback of the update's recurrent core after a persistent-kernel timeout (round 6).
 
-The two GRU recurrences and the instruction LSTM are persistent kernels whose cooperating workgroups wait for each other with BOUNDED
+The two state recurrences (GRU or LSTM) and the instruction encoder's recurrence are persistent kernels whose cooperating workgroups wait for each other with BOUNDED
 spins (csrc/wsmg_rnn.hip); the chained recurrent core adds kernels that spin on device counters (wsmgmap/recurrent.py).  A workgroup
 that does not become resident in time — beside a collective library's ring kernels, on a CU-masked device, beside another process —
 makes a spin run out: the kernel fills its outputs with NaN and sets a bit in a host-mapped status word.  `RecurrentCoreFallback`
@@ -20,7 +20,7 @@ import sys
 import torch
 import torch.distributed as dist
 
-from . import _abi, debug
+from . import _abi, debug, recurrent
 from .parallel import GradExchangeError
 
 
@@ -30,7 +30,8 @@ class RecurrentCoreFallback:
         net = policy.net
         self.level = 0
         self.reasons = []
-        chained = getattr(net, "recurrent_chunks", 0) > 0
+        # (an LSTM of another hidden size, or on the stock route, takes the staged route whatever recurrent_chunks says)
+        chained = getattr(net, "recurrent_chunks", 0) > 0 and recurrent.core_cell(net) is not None
         self.levels = [("chained (one launch per recurrence, device-side chunk counters)" if chained and debug.sw.recurrent_chain
                         else "pipelined chunk launches" if chained else "staged"),
                        "staged (fallback: one persistent kernel at a time, no chaining, no decoder side stream)",

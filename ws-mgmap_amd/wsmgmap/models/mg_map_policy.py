@@ -10,7 +10,8 @@ Attribute tree, state_dict keys and the in-place contract (writes `observations[
     token-major keys/values; the k=1 Conv1d key projections are MFMA GEMMs of the conv engine;
   * the BEV projection / scatter / global-map fuse run in the BEV kernels (operator 1);
   * instruction encoding is de-duplicated over the time axis of a teacher-forcing batch;
-  * the two GRU / LSTM state encoders run as persistent whole-sequence kernels (csrc/wsmg_rnn.hip);
+  * the two GRU / LSTM state encoders run as persistent whole-sequence kernels (csrc/wsmg_rnn.hip); in the update
+    both cells run the pipelined recurrent core, chained to the attention stage (wsmgmap/recurrent.py);
   * so does the instruction encoder's packed GRU / LSTM (bidirectional hidden 128 or unidirectional 256: every
     setting whose output width the policy admits); other shapes take stock nn.GRU / nn.LSTM.
 """
@@ -488,10 +489,14 @@ class MGMapNet(nn.Module):
         n1 = self.state_encoder.num_recurrent_layers
         ops.mark("state_in", state_in)
         n_env = rnn_hidden_states.size(1)
-        # The pipelined / chained recurrent core is GRU-only: `n1 == 1` and the 2-layer state exclude an LSTM state encoder
-        # (habitat's [h; c] layout: n1 == 2, 4 layers), which takes the staged route below whatever recurrent_chunks says.
-        if (self.recurrent_chunks > 0 and not ops.ranks_share_gpu() and torch.is_grad_enabled() and not rows and "map" in self._inputs and n1 == 1
-                and rnn_hidden_states.size(0) == 2 and recurrent.usable(state_in, map_tokens, n_env, text)):
+        # The pipelined / chained recurrent core runs GRU state encoders (n1 == 1, a 2-layer state) and LSTM state encoders on the
+        # persistent LSTM kernels (habitat's [h; c] layout: n1 == 2, 4 layers; recurrent.core_cell); an LSTM of another hidden size or
+        # on the stock route takes the staged route below whatever recurrent_chunks says.
+        cell = recurrent.core_cell(self) if self.recurrent_chunks > 0 else None
+        if (self.recurrent_chunks > 0 and not ops.ranks_share_gpu() and torch.is_grad_enabled() and not rows and "map" in self._inputs
+                and ((cell == "GRU" and n1 == 1 and rnn_hidden_states.size(0) == 2)
+                     or (cell == "LSTM" and rnn_hidden_states.size(0) == 2 * n1))
+                and recurrent.usable(state_in, map_tokens, n_env, text)):
             # GRU 1 -> text attention -> map attention -> compress -> GRU 2 as one autograd node, pipelined over time chunks on three
             # streams, parameter gradients off the chain (wsmgmap/recurrent.py); same kernels, same arithmetic row for row
             text_ready = torch.cuda.Event()
@@ -499,8 +504,10 @@ class MGMapNet(nn.Module):
             main = torch.cuda.current_stream()
             for t in text:
                 t.record_stream(main)
+            hs1, hs2 = ((rnn_hidden_states[0], rnn_hidden_states[1]) if cell == "GRU"
+                        else (rnn_hidden_states[0:n1], rnn_hidden_states[n1:]))
             x, self.att_map_t_m, h1n, h2n = recurrent.recurrent_block(
-                state_in, map_tokens, text, masks, rnn_hidden_states[0], rnn_hidden_states[1], self, n_env,
+                state_in, map_tokens, text, masks, hs1, hs2, self, n_env,
                 chunks=self.recurrent_chunks, sink=sink, text_ready=text_ready,
                 streams=None if capturing else (side, getattr(self.map_decoder, "_side", None)))
             rnn_hidden_states[0:n1] = h1n

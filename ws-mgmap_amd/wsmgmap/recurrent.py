@@ -8,7 +8,9 @@ Reference: MGMapNet.forward, vlnce_baselines/models/mg_map_policy.py:220-249 —
     x               = second_state_compress(cat(state, text_embedding, map_embedding))
     x               = second_state_encoder(x, h[1], masks)                        # GRU 2, T serial steps
 
-Only the two GRUs are recurrent; everything between them is per ROW.  Run stage after stage (rounds 1-3) the update's critical
+Only the two state encoders are recurrent — GRUs by default, LSTMs with MODEL.STATE_ENCODER.rnn_type = "LSTM" (both encoders share
+the type; the block runs either cell: G = 3 or 4 gate rows per unit, an LSTM's state is habitat's [h; c]) — and everything between
+them is per ROW.  Run stage after stage (rounds 1-3) the update's critical
 path holds 2 x T dependent GRU steps forward and 2 x T backward (4 x 64 steps of 5.6-6.0 us = 1.5 ms with 224 of the 256 CUs idle)
 plus ~60 dependent small launches around them.  Here the T steps are cut into K chunks: while GRU 1 runs chunk k+1 on one
 stream, the attention stage of chunk k runs on a second and GRU 2 of chunk k on a third (the carried hidden state is bit-exact
@@ -108,14 +110,28 @@ def _fork(main, *streams):
         st.wait_event(e)
 
 
-def rows_gemm_ok(H, C, in1):
-    """Shapes wsmg_rows_gemm_f32 takes for the attention stage's products (hidden size H, attention width C, GRU-2 input): every
-    product's reduction length is asked of the library (a multiple of 256 alone admitted K = 1280, which it refuses)."""
+def rows_gemm_ok(H, C, in1, G=3):
+    """Shapes wsmg_rows_gemm_f32 takes for the attention stage's products (hidden size H, attention width C, GRU-2 input, G gate rows
+    per unit of the second recurrence): every product's reduction length is asked of the library (a multiple of 256
+    alone admitted K = 1280, which it refuses)."""
     if not (_sw.rows_gemm and H % 256 == 0 and C % 256 == 0 and in1 % 256 == 0):
         return False
     ok = _abi.lib().wsmg_rows_gemm_supported
-    # forward: q1 (K = H), q2 / qf (C), compress (H + 2 C), gi2 (in1); backward: dxc (3 H), its split (in1), the queries (C, H)
-    return all(ok(int(k)) for k in (H, C, H + 2 * C, in1, 3 * H))
+    # forward: q1 (K = H), q2 / qf (C), compress (H + 2 C), gi2 (in1); backward: dxc (G H), its split (in1), the queries (C, H)
+    return all(ok(int(k)) for k in (H, C, H + 2 * C, in1, G * H))
+
+
+def core_cell(net):
+    """The cell the pipelined core runs for this policy's state encoders: "GRU", "LSTM" when both encoders run the persistent LSTM
+    kernels (hidden 512, not the stock route), or None: the staged route (an LSTM of another size, or on the stock route)."""
+    from .models.rnn_state_encoder import KERNEL_HIDDEN
+    encs = [getattr(net, n, None) for n in ("state_encoder", "second_state_encoder")]
+    lstm = [bool(getattr(e, "_is_lstm", False)) for e in encs]
+    if not any(lstm):
+        return "GRU"
+    if all(lstm) and not _sw.rnn_stock and all(e.rnn.hidden_size == KERNEL_HIDDEN for e in encs):
+        return "LSTM"
+    return None
 
 
 def _roles(streams, main):
@@ -161,6 +177,9 @@ class _RecurrentBlock(torch.autograd.Function):
         B = state_in.shape[0]
         T = B // N
         H = w_hh1.shape[1]
+        lstm = cfg["cell"] == "LSTM"
+        G = 4 if lstm else 3                  # gate rows per unit
+        assert w_hh1.shape[0] == G * H and w_hh2.shape[0] == G * H
         dev = state_in.device
         K, Tc = chunk_plan(T, K)
         rows = Tc * N
@@ -177,9 +196,15 @@ class _RecurrentBlock(torch.autograd.Function):
         # live on as saved tensors until the backward pass)
         gi1 = torch.addmm(b_ih1, state_in, w_ih1.t())
         y1 = torch.empty(T, N, H, **f32)
-        sv1 = [torch.empty(T, N, H, **f32) for _ in range(4)]
         y2 = torch.empty(T, N, H, **f32)
-        sv2 = [torch.empty(T, N, H, **f32) for _ in range(4)]
+        # saved for the backward: GRU r, z, n, W_hn h + b_hn [T, N, H] each; LSTM save_gates [T, N, 4H] (i, f, g, o) and save_c [T, N, H]
+        if lstm:
+            sv1 = [torch.empty(T, N, 4 * H, **f32), torch.empty(T, N, H, **f32)]
+            sv2 = [torch.empty(T, N, 4 * H, **f32), torch.empty(T, N, H, **f32)]
+            cT = torch.empty(2, N, H, **f32)      # the kernels' c_T outputs (the final c is save_c[T - 1] as well)
+        else:
+            sv1 = [torch.empty(T, N, H, **f32) for _ in range(4)]
+            sv2 = [torch.empty(T, N, H, **f32) for _ in range(4)]
         # (projection outputs start as their bias rows and are accumulated into: `addmm` with a 1-D bias takes hipBLASLt's bias-epilogue
         #  route, whose heuristic picks ONE 256 x 128 macro-tile for a 128-row chunk — 64 us for a 33-MFLOP product)
         q1 = torch.empty(B, wq1.shape[0], **f32)
@@ -190,16 +215,18 @@ class _RecurrentBlock(torch.autograd.Function):
         map_emb = torch.empty(B, C, **f32)
         att_map = torch.empty(B, I, **f32)
         x = None            # (the concatenation is an operand of the rows-GEMM route: the leaf pass rebuilds it for dW)
-        if not (rows_gemm_ok(H, C, wc.shape[0]) and wq1.shape[0] % 256 == 0 and wq2.shape[0] % 256 == 0):
+        rg = rows_gemm_ok(H, C, wc.shape[0], G) and wq1.shape[0] % 256 == 0 and wq2.shape[0] % 256 == 0
+        if not rg:
             x = torch.empty(B, wc.shape[1], **f32)
         xc = torch.empty(B, wc.shape[0], **f32)
-        gi2 = torch.empty(B, 3 * H, **f32)
+        gi2 = torch.empty(B, G * H, **f32)
         m = masks.reshape(T, N)
-        h01 = h01.clone()          # the caller overwrites rnn_hidden_states in place (reference contract)
+        h01 = h01.clone()          # the caller overwrites rnn_hidden_states in place (reference contract); an LSTM's is [h; c]
         h02 = h02.clone()
         tsfx = _sfx(text_k)
         ksfx = _sfx(tokens)
         nbytes = lib.wsmg_gru_workspace_bytes(Tc)
+        wsb = lib.wsmg_lstm_state_workspace_bytes if lstm else lib.wsmg_gru_workspace_bytes
         # (wsmgmap.parallel holds its buckets until this block's backward has queued its kernels: see _launch_ready there)
         _core.chain_in_flight = bool(sa is not main and any(ctx.needs_input_grad))
         forked = False
@@ -215,18 +242,36 @@ class _RecurrentBlock(torch.autograd.Function):
         # launch-unique tags in, so replays need the clearing form
         owned = not torch.cuda.is_current_stream_capturing()
 
-        def gru(gi, w_hh, b_hh, h0, y, sv, k, role):
+        def gru(gi, w_hh, b_hh, h0, y, sv, k, role, ci):
             t0 = k * Tc
+            if lstm:
+                # chunk k starts from (y[t0 - 1], save_c[t0 - 1]): the clearing entry point (there is no owned LSTM form)
+                hk, ck = (_p(h0), _prow(h0, 1)) if k == 0 else (_prow(y, t0 - 1), _prow(sv[1], t0 - 1))
+                ws = _rnn_workspace(nbytes, dev)
+                _abi.call("wsmg_lstm_state_fwd", _prow(gi, t0), _p(w_hh), _p(b_hh), hk, ck, _prow(m, t0), Tc, N, H, _prow(y, t0),
+                          _prow(cT, ci), _prow(sv[0], t0), _prow(sv[1], t0), _p(ws), _stream())
+                _rnn_launched()
+                return
             hk = h0 if k == 0 else y[t0 - 1]
             ws = _owned_ws(dev, role, nbytes) if owned else _rnn_workspace(nbytes, dev)
             _abi.call("wsmg_gru_fwd_owned" if owned else "wsmg_gru_fwd", _prow(gi, t0), _p(w_hh), _p(b_hh), _p(hk), _prow(m, t0), Tc, N, H,
                       _prow(y, t0), *[_prow(s_, t0) for s_ in sv], _p(ws), _stream())
             _rnn_launched()
 
-        gi1v, gi2v = gi1.view(T, N, 3 * H), gi2.view(T, N, 3 * H)
+        def chained(gi, w_hh, b_hh, h0, y, sv, role, ci, in_cnt, in_target, out_cnt):
+            ws = _p(_owned_ws(dev, role, wsb(T)))
+            if lstm:
+                _abi.call("wsmg_lstm_state_fwd_chain", _p(gi), _p(w_hh), _p(b_hh), _p(h0), _prow(h0, 1), _p(m), T, N, H, _p(y), _prow(cT, ci),
+                          *[_p(s_) for s_ in sv], ws, Tc, in_cnt, in_target, out_cnt, _stream())
+            else:
+                _abi.call("wsmg_gru_fwd_chain", _p(gi), _p(w_hh), _p(b_hh), _p(h0), _p(m), T, N, H, _p(y), *[_p(s_) for s_ in sv],
+                          ws, Tc, in_cnt, in_target, out_cnt, _stream())
+            _rnn_launched()
+
+        gi1v, gi2v = gi1.view(T, N, G * H), gi2.view(T, N, G * H)
         y1r = y1.view(B, H)
         multi = sa is not main
-        rg = rows_gemm_ok(H, C, wc.shape[0]) and wq1.shape[0] % 256 == 0 and wq2.shape[0] % 256 == 0
+        fail_bit = 32 if lstm else 1      # a chained product's wait names the recurrence it waits for (status bits of wsmg_rnn.hip)
         # round 5 — chained: each recurrence is ONE whole-sequence launch; the attention stage's first product of chunk k waits (on the
         # device) for the first recurrence's arrivals on counter k, its last product signals counter K + k, which the second
         # recurrence waits for at the first step of chunk k (csrc/wsmg_rnn.hip chain_wait).  No chunk prologues (W_hh into registers:
@@ -235,12 +280,10 @@ class _RecurrentBlock(torch.autograd.Function):
         cnt = None
         if chain:
             cnt = torch.zeros(3 * K, device=dev, dtype=torch.int32)     # [arrivals in | arrivals out | gate words] per chunk
-            nwg = int(lib.wsmg_gru_chain_workgroups())
+            nwg = int(lib.wsmg_lstm_state_chain_workgroups() if lstm else lib.wsmg_gru_chain_workgroups())
             _fork(main, sa, sg)          # (the counters are zeroed on main)
             forked = True
-            _abi.call("wsmg_gru_fwd_chain", _p(gi1), _p(w_hh1), _p(b_hh1), _p(h01), _p(m), T, N, H, _p(y1), *[_p(s_) for s_ in sv1],
-                      _p(_owned_ws(dev, "f1", lib.wsmg_gru_workspace_bytes(T))), Tc, None, 0, _p(cnt), _stream())
-            _rnn_launched()
+            chained(gi1, w_hh1, b_hh1, h01, y1, sv1, "f1", 0, None, 0, _p(cnt))
             _ops.mark("f.g1")
         if multi and not forked:
             _fork(main, sa, sg)
@@ -249,7 +292,7 @@ class _RecurrentBlock(torch.autograd.Function):
         # instead of eight times (the host has < 1.5 ms of lead over the GPU in this part of an update)
         ev1, eva = [], []
         for k in range(0 if chain else K):
-            gru(gi1v, w_hh1, b_hh1, h01, y1, sv1, k, "f1")                             # main
+            gru(gi1v, w_hh1, b_hh1, h01, y1, sv1, k, "f1", 0)                          # main
             _ops.mark("f.g1.%d" % k)
             if multi:
                 e1 = torch.cuda.Event()
@@ -268,7 +311,7 @@ class _RecurrentBlock(torch.autograd.Function):
                 if rg:
                     # round 5: every dense layer of the stage is ONE launch (csrc/wsmg_rows_gemm.hip): bias, the concatenation, the
                     # ReLU in the epilogue / operand segments — 7 launches per chunk instead of 9 + 4 pre-fills, each ~4 us
-                    _rg([y1r], wq1, False, [q1], r0, rows, bias=bq1, wait=(cnt.data_ptr() + 4 * k, nwg, cnt.data_ptr() + 4 * (2 * K + k)) if chain else None, fail_bit=1)
+                    _rg([y1r], wq1, False, [q1], r0, rows, bias=bq1, wait=(cnt.data_ptr() + 4 * k, nwg, cnt.data_ptr() + 4 * (2 * K + k)) if chain else None, fail_bit=fail_bit)
                 else:
                     q1[r0:r1].addmm_(y1r[r0:r1], wq1.t())
                 _abi.call("wsmg_attn_shared_fwd" + tsfx, _prow(q1, r0), _p(text_k), _p(text_v), _p(text_mask), _prow(inverse, r0),
@@ -296,15 +339,13 @@ class _RecurrentBlock(torch.autograd.Function):
                     eva.append(ea)
         with torch.cuda.stream(sg):
             if chain:
-                _abi.call("wsmg_gru_fwd_chain", _p(gi2), _p(w_hh2), _p(b_hh2), _p(h02), _p(m), T, N, H, _p(y2), *[_p(s_) for s_ in sv2],
-                          _p(_owned_ws(dev, "f2", lib.wsmg_gru_workspace_bytes(T))), Tc, ctypes.c_void_p(cnt.data_ptr() + 4 * K),
-                          int(lib.wsmg_rows_gemm_workgroups(rows, 3 * H)), None, _stream())
-                _rnn_launched()
+                chained(gi2, w_hh2, b_hh2, h02, y2, sv2, "f2", 1, ctypes.c_void_p(cnt.data_ptr() + 4 * K),
+                        int(lib.wsmg_rows_gemm_workgroups(rows, G * H)), None)
                 _ops.mark("f.g2")
             for k in range(0 if chain else K):
                 if multi:
                     sg.wait_event(eva[k])
-                gru(gi2v, w_hh2, b_hh2, h02, y2, sv2, k, "f2")
+                gru(gi2v, w_hh2, b_hh2, h02, y2, sv2, k, "f2", 1)
                 _ops.mark("f.g2.%d" % k)
         if sg is not main:
             main.wait_stream(sg)
@@ -313,21 +354,30 @@ class _RecurrentBlock(torch.autograd.Function):
                               gi1, y1, *sv1, y2, *sv2, q1, text_emb, attn_text, q2, qf, att_map, map_emb if x is None else x, xc)
         ctx.x_is_parts = x is None
         ctx.chain = chain
+        ctx.lstm = lstm
         ctx.cfg = (N, K, Tc, scale, sink, tuple(wk.shape), text_mask is not None)
         ctx.params = (w_ih1, b_ih1, w_hh1, b_hh1, wq1, bq1, wq2, bq2, wk, bk, wc, bc, w_ih2, b_ih2, w_hh2, b_hh2)
-        h1n, h2n = y1[-1:].clone(), y2[-1:].clone()
+        if lstm:      # habitat's [h; c] layout
+            h1n, h2n = torch.cat([y1[-1:], sv1[1][-1:]]), torch.cat([y2[-1:], sv2[1][-1:]])
+        else:
+            h1n, h2n = y1[-1:].clone(), y2[-1:].clone()
         ctx.mark_non_differentiable(h1n, h2n)
         ctx.set_materialize_grads(False)
         return y2.view(B, H), att_map, h1n, h2n
 
     @staticmethod
     def backward(ctx, dy2, datt, _dh1, _dh2):
-        (state_in, tokens, text_k, text_v, inverse, m, h01, h02, w_ih1, w_hh1, wq1, wq2, wk2, wc, w_ih2, w_hh2,
-         gi1, y1, sr1, sz1, sn1, sg1, y2, sr2, sz2, sn2, sg2, q1, text_emb, attn_text, q2, qf, att_map, x, xc) = ctx.saved_tensors
+        lstm = ctx.lstm
+        ns = 2 if lstm else 4        # saved tensors per recurrence (see forward)
+        saved = ctx.saved_tensors
+        (state_in, tokens, text_k, text_v, inverse, m, h01, h02, w_ih1, w_hh1, wq1, wq2, wk2, wc, w_ih2, w_hh2, gi1, y1) = saved[:18]
+        sv1, y2, sv2 = saved[18:18 + ns], saved[18 + ns], saved[19 + ns:19 + 2 * ns]
+        q1, text_emb, attn_text, q2, qf, att_map, x, xc = saved[19 + 2 * ns:]
         rg = ctx.x_is_parts          # the rows-GEMM route: `x` is map_emb, the concatenation is rebuilt on the leaf stream
         N, K, Tc, scale, sink, wk_shape, _ = ctx.cfg
         T = y1.shape[0]
         H = y1.shape[2]
+        G = 4 if lstm else 3
         B = T * N
         rows = Tc * N
         dev = y1.device
@@ -371,8 +421,9 @@ class _RecurrentBlock(torch.autograd.Function):
         tsfx, ksfx = _sfx(text_k), _sfx(tokens)
         # full-batch gradient buffers, allocated on the main stream and used on the others: the allocator must not hand their memory
         # to a later main-stream allocation while a side stream still works on them
-        dgi2, dgh2 = torch.empty(T, N, 3 * H, **f32), torch.empty(T, N, 3 * H, **f32)
-        dgi1, dgh1 = torch.empty(T, N, 3 * H, **f32), torch.empty(T, N, 3 * H, **f32)
+        # (an LSTM's one gate gradient is both the gradient of gi and of W_hh h + b_hh: dgh is dgi; its state gradients are [dh; dc])
+        dgi2, dgi1 = torch.empty(T, N, G * H, **f32), torch.empty(T, N, G * H, **f32)
+        dgh2, dgh1 = (dgi2, dgi1) if lstm else (torch.empty(T, N, 3 * H, **f32), torch.empty(T, N, 3 * H, **f32))
         dxc = torch.empty(B, wc.shape[0], **f32)
         dqf, dq2, dq1 = torch.empty(B, C, **f32), torch.empty(B, wq2.shape[0], **f32), torch.empty(B, wq1.shape[0], **f32)
         dtext = torch.empty(B, C, **f32)
@@ -380,9 +431,10 @@ class _RecurrentBlock(torch.autograd.Function):
         dl = torch.empty(B, L, **f32)
         dstate = torch.empty(T, N, H, **f32)
         dtokens = torch.empty_like(tokens)
-        dh01, dh02 = torch.empty(N, H, **f32), torch.empty(N, H, **f32)
-        carry2 = [torch.empty(N, H, **f32) for _ in range(2)]
-        carry1 = [torch.empty(N, H, **f32) for _ in range(2)]
+        sh = (2, N, H) if lstm else (N, H)
+        dh01, dh02 = torch.empty(sh, **f32), torch.empty(sh, **f32)
+        carry2 = [torch.empty(sh, **f32) for _ in range(2)]
+        carry1 = [torch.empty(sh, **f32) for _ in range(2)]
         if multi:
             # these are allocated from the main stream's pool and used on the others: they must not be handed to a later main-stream
             # allocation while a side stream still works on them — a reference is held until the pass's final callbacks, which run
@@ -396,39 +448,56 @@ class _RecurrentBlock(torch.autograd.Function):
         xcr = xc
         y1r = y1.view(B, H)
         dstate_r = dstate.view(B, H)
-        dgi2r = dgi2.view(B, 3 * H)
+        dgi2r = dgi2.view(B, G * H)
 
         owned = not torch.cuda.is_current_stream_capturing()
+        wsb = lib.wsmg_lstm_state_workspace_bytes if lstm else lib.wsmg_gru_workspace_bytes
 
         def gru_bwd(dy, w_hh, h0, y, sv, dgi, dgh, dh0_out, carry, k, role):
             t0 = k * Tc
-            hk = h0 if k == 0 else y[t0 - 1]
             dhT = None if k == K - 1 else carry[(k + 1) & 1]
             out = dh0_out if k == 0 else carry[k & 1]
+            if lstm:
+                # chunk k: c_{t0-1} = save_c[t0 - 1]; (dhT, dcT) = the later chunk's (dh0, dc0); the clearing entry point
+                ck = _prow(h0, 1) if k == 0 else _prow(sv[1], t0 - 1)
+                ws = _rnn_workspace(nbytes, dev)
+                _abi.call("wsmg_lstm_state_bwd", _prow(dy, t0), _p(dhT), None if dhT is None else _prow(dhT, 1), _p(w_hh), ck, _prow(m, t0),
+                          _prow(sv[0], t0), _prow(sv[1], t0), Tc, N, H, _prow(dgi, t0), _p(out), _prow(out, 1), _p(ws), _stream())
+                _rnn_launched()
+                return
+            hk = h0 if k == 0 else y[t0 - 1]
             ws = _owned_ws(dev, role, nbytes) if owned else _rnn_workspace(nbytes, dev)
             _abi.call("wsmg_gru_bwd_owned" if owned else "wsmg_gru_bwd", _prow(dy, t0), _p(dhT), _p(w_hh), _p(hk), _prow(m, t0), _prow(y, t0),
                       *[_prow(s_, t0) for s_ in sv], Tc, N, H, _prow(dgi, t0), _prow(dgh, t0), _p(out), _p(ws), _stream())
+            _rnn_launched()
+
+        def chained_bwd(dy, w_hh, h0, y, sv, dgi, dgh, dh0_out, role, in_cnt, in_target, out_cnt):
+            ws = _p(_owned_ws(dev, role, wsb(T)))
+            if lstm:
+                _abi.call("wsmg_lstm_state_bwd_chain", _p(dy), None, None, _p(w_hh), _prow(h0, 1), _p(m), *[_p(s_) for s_ in sv], T, N, H,
+                          _p(dgi), _p(dh0_out), _prow(dh0_out, 1), ws, Tc, in_cnt, in_target, out_cnt, _stream())
+            else:
+                _abi.call("wsmg_gru_bwd_chain", _p(dy), None, _p(w_hh), _p(h0), _p(m), _p(y), *[_p(s_) for s_ in sv], T, N, H,
+                          _p(dgi), _p(dgh), _p(dh0_out), ws, Tc, in_cnt, in_target, out_cnt, _stream())
             _rnn_launched()
 
         # stream by stream, as in forward: GRU 2's chunks (last chunk first), the attention stage's, GRU 1's
         ev2, eva = {}, {}
         chain = multi and rg and owned and ctx.chain and K > 1
         cnt = None
+        fail_bit = 64 if lstm else 2
         if chain:     # (see forward: one launch per recurrence, device-side waits on per-chunk arrival counters)
             cnt = torch.zeros(3 * K, device=dev, dtype=torch.int32)     # [arrivals in | arrivals out | gate words] per chunk
             keep.append(cnt)
-            nwg = int(lib.wsmg_gru_chain_workgroups())
+            nwg = int(lib.wsmg_lstm_state_chain_workgroups() if lstm else lib.wsmg_gru_chain_workgroups())
         if multi:
             _fork(main, sg, sa)      # once, behind everything the pass has queued on main so far (buffers, the chain's counters)
         with torch.cuda.stream(sg):
             if chain:
-                _abi.call("wsmg_gru_bwd_chain", _p(dy2), None, _p(w_hh2), _p(h02), _p(m), _p(y2), _p(sr2), _p(sz2), _p(sn2), _p(sg2), T, N, H,
-                          _p(dgi2), _p(dgh2), _p(dh02), _p(_owned_ws(dev, "b2", lib.wsmg_gru_workspace_bytes(T))), Tc, None, 0, _p(cnt),
-                          _stream())
-                _rnn_launched()
+                chained_bwd(dy2, w_hh2, h02, y2, sv2, dgi2, dgh2, dh02, "b2", None, 0, _p(cnt))
                 _ops.mark("b.g2")
             for k in range(K - 1 if not chain else -1, -1, -1):
-                gru_bwd(dy2, w_hh2, h02, y2, (sr2, sz2, sn2, sg2), dgi2, dgh2, dh02, carry2, k, "b2")
+                gru_bwd(dy2, w_hh2, h02, y2, sv2, dgi2, dgh2, dh02, carry2, k, "b2")
                 _ops.mark("b.g2.%d" % k)
                 if multi:
                     ev2[k] = torch.cuda.Event()
@@ -444,7 +513,7 @@ class _RecurrentBlock(torch.autograd.Function):
                     # round 5: five launches of wsmg_rows_gemm_f32 around the two attention kernels (was 9 GEMM-library launches + a
                     # threshold_backward): the ReLU mask, the split of d(cat) into its three parts and the two accumulate-intos
                     # (beta = 1, in place) ride in the epilogues
-                    _rg([dgi2r], w_ih2, True, [dxc], r0, rows, mask=xcr, wait=(cnt.data_ptr() + 4 * k, nwg, cnt.data_ptr() + 4 * (2 * K + k)) if chain else None, fail_bit=2)
+                    _rg([dgi2r], w_ih2, True, [dxc], r0, rows, mask=xcr, wait=(cnt.data_ptr() + 4 * k, nwg, cnt.data_ptr() + 4 * (2 * K + k)) if chain else None, fail_bit=fail_bit)
                     _rg([dxc], wc, True, [dstate_r, dtext, dmap_all], r0, rows)
                     _abi.call("wsmg_attn_bwd" + ksfx, _prow(qf, r0), _prow(tokens, r0), _prow(tokens, r0), _prow(att_map, r0), _prow(dmap_all, r0),
                               None if datt is None else _prow(datt, r0), scale, rows, I, C, _prow(dqf, r0), _prow(dtokens, r0),
@@ -475,17 +544,15 @@ class _RecurrentBlock(torch.autograd.Function):
                     eva[k] = torch.cuda.Event()
                     eva[k].record(sa)
         if chain:
-            _abi.call("wsmg_gru_bwd_chain", _p(dstate), None, _p(w_hh1), _p(h01), _p(m), _p(y1), _p(sr1), _p(sz1), _p(sn1), _p(sg1), T, N, H,
-                      _p(dgi1), _p(dgh1), _p(dh01), _p(_owned_ws(dev, "b1", lib.wsmg_gru_workspace_bytes(T))), Tc,
-                      ctypes.c_void_p(cnt.data_ptr() + 4 * K), int(lib.wsmg_rows_gemm_workgroups(rows, H)), None, _stream())
-            _rnn_launched()
+            chained_bwd(dstate, w_hh1, h01, y1, sv1, dgi1, dgh1, dh01, "b1", ctypes.c_void_p(cnt.data_ptr() + 4 * K),
+                        int(lib.wsmg_rows_gemm_workgroups(rows, H)), None)
             _ops.mark("b.g1")
         for k in range(K - 1 if not chain else -1, -1, -1):
             if multi:
                 main.wait_event(eva[k])
-            gru_bwd(dstate, w_hh1, h01, y1, (sr1, sz1, sn1, sg1), dgi1, dgh1, dh01, carry1, k, "b1")      # main
+            gru_bwd(dstate, w_hh1, h01, y1, sv1, dgi1, dgh1, dh01, carry1, k, "b1")      # main
             _ops.mark("b.g1.%d" % k)
-        d_state_in = torch.mm(dgi1.view(B, 3 * H), w_ih1) if ctx.needs_input_grad[1] else None
+        d_state_in = torch.mm(dgi1.view(B, G * H), w_ih1) if ctx.needs_input_grad[1] else None
         # gradients of the shared instruction sets (they feed the instruction branch's backward, on ITS stream): after the last
         # attention chunk on the attention stream, joined into main below — by then GRU 1's last chunk has long hidden them
         with torch.cuda.stream(sa):
@@ -500,12 +567,15 @@ class _RecurrentBlock(torch.autograd.Function):
         # parameter gradients: full-batch GEMMs and column sums, off the chain
         with torch.cuda.stream(sl):
             g2 = dgi2r
-            gh2 = dgh2.view(B, 3 * H)
-            g1 = dgi1.view(B, 3 * H)
-            gh1 = dgh1.view(B, 3 * H)
-            # the seven bias gradients (column sums) in one launch (round 6; torch: a reduction kernel + a memset each)
+            gh2 = dgh2.view(B, G * H)
+            g1 = dgi1.view(B, G * H)
+            gh1 = dgh1.view(B, G * H)
+            # the seven bias gradients (column sums) in one launch (round 6; torch: a reduction kernel + a memset each); an LSTM's
+            # db_hh = db_ih = colsum(dgates), two tensors of their own
             db_ih2, db_hh2, dbc, dbq2, dbq1, db_hh1, db_ih1 = _ops.colsum_multi([g2, gh2, dxc, dq2, dq1, gh1, g1])
             dw_ih2 = g2.t() @ xc
+            if lstm:
+                h01, h02 = h01[0], h02[0]           # (the h halves of [h; c]: dW_hh = dgates^T (mask * h_prev))
             hp2 = torch.cat([h02.unsqueeze(0), y2[:-1]], dim=0) * m.unsqueeze(-1)
             dw_hh2 = gh2.t() @ hp2.view(B, H)
             if rg:
@@ -540,15 +610,20 @@ class _RecurrentBlock(torch.autograd.Function):
 
 
 def recurrent_block(state_in, tokens, text, masks, h01, h02, net, n_env, chunks=4, sink=None, text_ready=None, streams=None):
-    """-> (x [B, H] = GRU 2's outputs, att_map [B, I], h1_n [1, N, H], h2_n [1, N, H]).
+    """-> (x [B, H] = the second recurrence's outputs, att_map [B, I], h1_n, h2_n: [1, N, H] each, [2, N, H] = [h; c] for an LSTM).
     state_in [B, in] (rows time-major, B = T * n_env); tokens [B, I, 256] map tokens (keys == values, the key projection
     `net.text_map_k_layer` folded into the query); text = (keys [U, L, 256], values [U, L, 256], pad mask uint8 [U, L], inverse
-    int64 [B]) of the U unique instructions; masks [B, 1]; h01 / h02 [N, H]; net: the MGMapNet whose layers these are;
-    text_ready: an event after which `text` is complete (recorded on the instruction branch's stream), or None when the caller's
-    stream already waited; streams: up to two helper streams that are idle while the block runs (see _roles), None = one stream."""
+    int64 [B]) of the U unique instructions; masks [B, 1]; h01 / h02 [N, H] (GRU) or [2, N, H] (LSTM: habitat's [h; c]); net: the
+    MGMapNet whose layers these are (core_cell(net) must not be None); text_ready: an event after which `text` is complete
+    (recorded on the instruction branch's stream), or None when the caller's stream already waited; streams: up to two helper
+    streams that are idle while the block runs (see _roles), None = one stream."""
+    cell = core_cell(net)
+    if cell is None:
+        raise _abi.WsmgError("recurrent_block: these state encoders take the staged route (an LSTM needs hidden 512 and the kernels)")
     r1, r2 = net.state_encoder.rnn, net.second_state_encoder.rnn
     tk, tv, tm, inv = text
-    cfg = dict(N=int(n_env), chunks=int(chunks), scale=float(net._scale_f), sink=sink, text_ready=text_ready, streams=tuple(streams or ()))
+    cfg = dict(N=int(n_env), chunks=int(chunks), scale=float(net._scale_f), sink=sink, text_ready=text_ready, streams=tuple(streams or ()),
+               cell=cell)
     return _RecurrentBlock.apply(
         cfg, state_in.contiguous(), tokens.contiguous(), tk, tv, tm, inv, masks.reshape(-1).float().contiguous(), h01, h02,
         r1.weight_ih_l0, r1.bias_ih_l0, r1.weight_hh_l0, r1.bias_hh_l0,
