@@ -773,8 +773,9 @@ int wsmg_instruction_dedup(const void* tokens, int is_f32, int B, int L, long lo
  * C: up to three column segments c_i [M][nc_i] (row stride ldc_i) — the split of d(cat) into its parts;
  * epilogue, in this order: + bias[N] (may be NULL), + cin_i (same segmentation as C, may be NULL: beta = 1), ReLU (relu != 0),
  * zero where mask[M][N] <= 0 (row stride ldmask, may be NULL: threshold_backward of the ReLU).
- * K % 64 == 0 (K / 16 a multiple of 16, or of 4, times 1-4, 6 or 8), ka_i % 16 == 0, nc_i % 16 == 0, strides % 4 == 0; WSMG_EINVAL
- * otherwise.  Deterministic (fixed reduction order).
+ * K in {256, 512, 768, 1024, 1536, 2048} (16 waves) or {64, 128, 192, 384} (4 waves) = wsmg_rows_gemm_supported(K), ka_i % 16 == 0,
+ * nc_i % 16 == 0, strides % 4 == 0; WSMG_EINVAL otherwise, before anything is enqueued (a refused chained call launches no gate).
+ * Deterministic (fixed reduction order).
  * Chaining to the whole-sequence GRU launches (wsmg_gru_fwd_chain / _bwd_chain): wait_count (may be NULL): the product does not
  * read its operands before *wait_count >= wait_target (they are produced by a kernel still running on another stream) — the wait,
  * bounded, is a ONE-workgroup launch in front of the product on the same stream (a grid of spinning workgroups could keep that

@@ -331,8 +331,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradArgs a) {
   }
 }
 
-// pipeline variant: WSMG_CONV_DB=0/1 (tuning knob; default set from measurements)
-bool conv_double_buffer() { return (0) != 0; }
+// pipeline variant: DB = false everywhere (set from measurements); the DB = true instantiations no dispatcher could select are
+// not compiled
 
 int check_conv(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH, int OW) {
   if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || KH <= 0 || KW <= 0) return WSMG_EINVAL;
@@ -353,10 +353,7 @@ extern "C" int wsmg_conv2d_fwd(const float* x, const float* w_ohwi, const float*
   a.mtiles = (int)wsmg_cdiv((int64_t)B * OH * OW, BM);
   a.ntiles = (int)wsmg_cdiv(Cout, BN);
   dim3 grid((unsigned)(a.mtiles * a.ntiles));
-  if (conv_double_buffer())
-    hipLaunchKernelGGL((conv_igemm_kernel<false, true>), grid, dim3(256), 0, wsmg_s(stream), a);
-  else
-    hipLaunchKernelGGL((conv_igemm_kernel<false, false>), grid, dim3(256), 0, wsmg_s(stream), a);
+  hipLaunchKernelGGL((conv_igemm_kernel<false, false>), grid, dim3(256), 0, wsmg_s(stream), a);
   WSMG_RETURN_LAUNCH();
 }
 
@@ -374,10 +371,7 @@ extern "C" int wsmg_conv2d_bwd_data(const float* dy, const float* w_ihwo, float*
   }
   a.mtiles = (int)wsmg_cdiv(mmax, BM);
   dim3 grid((unsigned)(a.mtiles * a.ntiles), (unsigned)classes);
-  if (conv_double_buffer())
-    hipLaunchKernelGGL((conv_igemm_kernel<true, true>), grid, dim3(256), 0, wsmg_s(stream), a);
-  else
-    hipLaunchKernelGGL((conv_igemm_kernel<true, false>), grid, dim3(256), 0, wsmg_s(stream), a);
+  hipLaunchKernelGGL((conv_igemm_kernel<true, false>), grid, dim3(256), 0, wsmg_s(stream), a);
   WSMG_RETURN_LAUNCH();
 }
 
@@ -405,10 +399,7 @@ int launch_wgrad_f32(const float* x, const float* dy, float* dw, long long slab,
   int gz = 1;
   wgrad_plan_f32(B, OH, OW, Cin, Cout, KH, KW, a.gx, a.gy, a.chunk, gz);
   dim3 grid((unsigned)((int64_t)a.gx * a.gy * gz));
-  if (conv_double_buffer())
-    hipLaunchKernelGGL(conv_wgrad_kernel<true>, grid, dim3(256), 0, stream, a);
-  else
-    hipLaunchKernelGGL(conv_wgrad_kernel<false>, grid, dim3(256), 0, stream, a);
+  hipLaunchKernelGGL(conv_wgrad_kernel<false>, grid, dim3(256), 0, stream, a);
   WSMG_RETURN_LAUNCH();
 }
 }  // namespace

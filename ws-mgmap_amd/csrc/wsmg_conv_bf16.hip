@@ -601,9 +601,9 @@ int check_conv(int B, int H, int W, int Cin, int Cout, int KH, int KW, int strid
   return 0;
 }
 
-// register prefetch depth (k-steps in flight).  Measured on MI355X (tools/bench_conv.py): the igemm
-// kernels are fastest at 1 (deeper costs occupancy, which hides more latency than the prefetch does).
-int conv_prefetch(int dflt) { return dflt; }
+// register prefetch depth (k-steps in flight) is PF = 1 everywhere.  Measured on MI355X (tools/bench_conv.py): the igemm
+// kernels are fastest at 1 (deeper costs occupancy, which hides more latency than the prefetch does); the PF = 2 / 3
+// instantiations no dispatcher could select are gone.
 
 int g_win3_tile = -1;
 int win3_tile() {   // WSMG_CONV_WIN3: 0 = off, 1 = by shape (default), 512 / 256 = that many pixels per workgroup
@@ -647,18 +647,6 @@ int win3_choice(int64_t M, int Kc, int N) {
   return ((M + 511) / 512) * (N / 128) >= 1024 ? 512 : 256;
 }
 
-template <bool BWD, int PF>
-void launch_igemm_pf(ConvArgsB& a, dim3 grid, bool bk64, bool bn128, hipStream_t s) {
-  if (bk64 && bn128)
-    hipLaunchKernelGGL((conv_igemm_bf16_kernel<BWD, 128, 64, PF>), grid, dim3(256), 0, s, a);
-  else if (bk64)
-    hipLaunchKernelGGL((conv_igemm_bf16_kernel<BWD, 64, 64, PF>), grid, dim3(256), 0, s, a);
-  else if (bn128)
-    hipLaunchKernelGGL((conv_igemm_bf16_kernel<BWD, 128, 32, PF>), grid, dim3(256), 0, s, a);
-  else
-    hipLaunchKernelGGL((conv_igemm_bf16_kernel<BWD, 64, 32, PF>), grid, dim3(256), 0, s, a);
-}
-
 template <bool BWD>
 int launch_igemm(ConvArgsB& a, int64_t mrows, int classes, hipStream_t s) {
   const bool bk64 = (a.Kc % 64) == 0;
@@ -667,12 +655,14 @@ int launch_igemm(ConvArgsB& a, int64_t mrows, int classes, hipStream_t s) {
   a.mtiles = (int)wsmg_cdiv(mrows, BM);
   a.ntiles = (int)wsmg_cdiv(a.N, bn);
   dim3 grid((unsigned)(a.mtiles * a.ntiles), (unsigned)classes);
-  switch (conv_prefetch(1)) {
-    case 1: launch_igemm_pf<BWD, 1>(a, grid, bk64, bn128, s); break;
-    case 3: launch_igemm_pf<BWD, 3>(a, grid, bk64, bn128, s); break;
-    case 2: launch_igemm_pf<BWD, 2>(a, grid, bk64, bn128, s); break;
-    default: launch_igemm_pf<BWD, 1>(a, grid, bk64, bn128, s); break;
-  }
+  if (bk64 && bn128)
+    hipLaunchKernelGGL((conv_igemm_bf16_kernel<BWD, 128, 64, 1>), grid, dim3(256), 0, s, a);
+  else if (bk64)
+    hipLaunchKernelGGL((conv_igemm_bf16_kernel<BWD, 64, 64, 1>), grid, dim3(256), 0, s, a);
+  else if (bn128)
+    hipLaunchKernelGGL((conv_igemm_bf16_kernel<BWD, 128, 32, 1>), grid, dim3(256), 0, s, a);
+  else
+    hipLaunchKernelGGL((conv_igemm_bf16_kernel<BWD, 64, 32, 1>), grid, dim3(256), 0, s, a);
   return 0;
 }
 
@@ -988,25 +978,22 @@ int launch_wgrad_bf16(const void* x, const void* dy, float* dw, long long slab_f
   a.gy = p.gy;
   const int tc = p.tc, tu = p.tu;
   dim3 grid((unsigned)((int64_t)p.gx * p.gy * p.nsplit));
-  const int pf = conv_prefetch(1) >= 2 ? 2 : 1;
   const int cch = Cin / 32, wun = 4 * tu;
   int upt = 1;
   for (int c = wun; c > 1; c >>= 1)
     if (cch % c == 0) { upt = c; break; }
-#define WSMG_WGRAD(TC_, TU_, PF_, UPT_) \
-  hipLaunchKernelGGL((conv_wgrad_bf16_kernel<TC_, TU_, PF_, UPT_>), grid, dim3(256), 0, stream, a)
-#define WSMG_WGRAD_U4(TC_, TU_, PF_) \
-  do { if (upt >= 4) WSMG_WGRAD(TC_, TU_, PF_, 4); else if (upt == 2) WSMG_WGRAD(TC_, TU_, PF_, 2); else WSMG_WGRAD(TC_, TU_, PF_, 1); } while (0)
-#define WSMG_WGRAD_U8(TC_, TU_, PF_) \
-  do { if (upt == 8) WSMG_WGRAD(TC_, TU_, PF_, 8); else WSMG_WGRAD_U4(TC_, TU_, PF_); } while (0)
+#define WSMG_WGRAD(TC_, TU_, UPT_) \
+  hipLaunchKernelGGL((conv_wgrad_bf16_kernel<TC_, TU_, 1, UPT_>), grid, dim3(256), 0, stream, a)
+#define WSMG_WGRAD_U4(TC_, TU_) \
+  do { if (upt >= 4) WSMG_WGRAD(TC_, TU_, 4); else if (upt == 2) WSMG_WGRAD(TC_, TU_, 2); else WSMG_WGRAD(TC_, TU_, 1); } while (0)
   if (tc == 4) {
-    if (pf == 1) WSMG_WGRAD_U8(4, 2, 1); else WSMG_WGRAD_U8(4, 2, 2);
+    if (upt == 8) WSMG_WGRAD(4, 2, 8); else WSMG_WGRAD_U4(4, 2);
   } else if (tu == 2) {
-    if (pf == 1) WSMG_WGRAD_U8(2, 2, 1); else WSMG_WGRAD_U8(2, 2, 2);
+    if (upt != 2) return WSMG_EINVAL;   // cannot happen: 64 co x 8 units is chosen for Cin = 64 only (two 32-channel groups per tap)
+    WSMG_WGRAD(2, 2, 2);
   } else {
-    if (pf == 1) WSMG_WGRAD_U4(2, 1, 1); else WSMG_WGRAD_U4(2, 1, 2);
+    WSMG_WGRAD_U4(2, 1);
   }
-#undef WSMG_WGRAD_U8
 #undef WSMG_WGRAD_U4
 #undef WSMG_WGRAD
   WSMG_RETURN_LAUNCH();

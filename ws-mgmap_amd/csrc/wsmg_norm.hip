@@ -375,10 +375,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply8_kernel(const bf16_t* __rest
   }
 }
 
-// WSMG_BN_VEC8=0: the 4-channel kernels for bf16 as well (A/B)
-bool bn_vec8() {
-  return (1) != 0;
-}
+// bf16 always takes the 8-channel kernels (chan_ok: every channel count is a multiple of 32); the 4-channel templates are compiled
+// for float32 only
 
 int stream_grid8(int64_t rows, int C) {
   int64_t rpi = 256 / (C / 8);
@@ -429,14 +427,12 @@ int bn_act_fwd_t(const T* x, const T* residual, const float* gamma, const float*
                        save_mean, save_invstd);
   }
   if constexpr (std::is_same<T, bf16_t>::value) {
-    if (bn_vec8()) {
-      hipLaunchKernelGGL(bn_apply8_kernel, dim3(stream_grid8(rows, C)), dim3(256), 0, s, x, residual, gamma, beta, save_mean,
-                         save_invstd, relu, rows, C, y);
-      WSMG_RETURN_LAUNCH();
-    }
+    hipLaunchKernelGGL(bn_apply8_kernel, dim3(stream_grid8(rows, C)), dim3(256), 0, s, x, residual, gamma, beta, save_mean,
+                       save_invstd, relu, rows, C, y);
+  } else {
+    hipLaunchKernelGGL(bn_apply_kernel<T>, dim3(stream_grid(rows, C)), dim3(256), 0, s, x, residual, gamma, beta,
+                       save_mean, save_invstd, relu, rows, C, y);
   }
-  hipLaunchKernelGGL(bn_apply_kernel<T>, dim3(stream_grid(rows, C)), dim3(256), 0, s, x, residual, gamma, beta,
-                     save_mean, save_invstd, relu, rows, C, y);
   WSMG_RETURN_LAUNCH();
 }
 
@@ -455,15 +451,13 @@ int bn_act_bwd_t(const T* dy, const T* x, const T* y, const float* gamma, const 
                      gamma, beta, relu, rows, C, workspace, ld_dy);
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(64), 0, s, workspace, nb, C, dgamma, dbeta);
   if constexpr (std::is_same<T, bf16_t>::value) {
-    if (bn_vec8()) {
-      hipLaunchKernelGGL(bn_bwd_apply8_kernel, dim3(stream_grid8(rows, C)), dim3(256), 0, s, dy, x, y, gamma, beta, save_mean,
-                         save_invstd, dgamma, dbeta, relu, 1.0f / (float)rows, rows, C, dx, dresidual, ld_dy, dx_lo);
-      WSMG_RETURN_LAUNCH();
-    }
+    hipLaunchKernelGGL(bn_bwd_apply8_kernel, dim3(stream_grid8(rows, C)), dim3(256), 0, s, dy, x, y, gamma, beta, save_mean,
+                       save_invstd, dgamma, dbeta, relu, 1.0f / (float)rows, rows, C, dx, dresidual, ld_dy, dx_lo);
+  } else {
+    if (dx_lo) return WSMG_EINVAL;
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, dim3(stream_grid(rows, C)), dim3(256), 0, s, dy, x, y, gamma, beta, save_mean,
+                       save_invstd, dgamma, dbeta, relu, 1.0f / (float)rows, rows, C, dx, dresidual, ld_dy);
   }
-  if (dx_lo) return WSMG_EINVAL;
-  hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, dim3(stream_grid(rows, C)), dim3(256), 0, s, dy, x, y, gamma, beta, save_mean,
-                     save_invstd, dgamma, dbeta, relu, 1.0f / (float)rows, rows, C, dx, dresidual, ld_dy);
   WSMG_RETURN_LAUNCH();
 }
 
@@ -479,12 +473,8 @@ extern "C" int wsmg_bn_act_fwd_bf16_pre(const void* x, const void* residual, con
   hipStream_t s = wsmg_s(stream);
   hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(C), dim3(64), 0, s, stats, nslab, C, rows, momentum, eps, running_mean,
                      running_var, save_mean, save_invstd, 1);
-  if (bn_vec8())
-    hipLaunchKernelGGL(bn_apply8_kernel, dim3(stream_grid8(rows, C)), dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)residual, gamma,
-                       beta, save_mean, save_invstd, relu, rows, C, (bf16_t*)y);
-  else
-    hipLaunchKernelGGL(bn_apply_kernel<bf16_t>, dim3(stream_grid(rows, C)), dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)residual,
-                       gamma, beta, save_mean, save_invstd, relu, rows, C, (bf16_t*)y);
+  hipLaunchKernelGGL(bn_apply8_kernel, dim3(stream_grid8(rows, C)), dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)residual, gamma,
+                     beta, save_mean, save_invstd, relu, rows, C, (bf16_t*)y);
   WSMG_RETURN_LAUNCH();
 }
 

@@ -190,6 +190,7 @@ extern "C" int wsmg_rows_gemm_f32(const float* a0, int lda0, int ka0, const floa
   const int K = ka0 + ka1 + ka2, N = nc0 + nc1 + nc2;
   if (K % 64 || ka0 % 16 || ka1 % 16 || ka2 % 16 || nc0 % 16 || nc1 % 16 || nc2 % 16) return WSMG_EINVAL;
   if ((lda0 | lda1 | lda2 | ldw) & 3) return WSMG_EINVAL;       // 16-byte loads along K (NT) / rows of A
+  if (!wsmg_rows_gemm_supported(K)) return WSMG_EINVAL;         // before the gate launch: a refused call leaves nothing on the stream
   const bool any_cin = cin0 != nullptr;
   if (any_cin && ((nc1 > 0 && !cin1) || (nc2 > 0 && !cin2))) return WSMG_EINVAL;
   RowsGemmArgs g;
@@ -235,10 +236,8 @@ extern "C" int wsmg_rows_gemm_f32(const float* a0, int lda0, int ka0, const floa
       case 1: launch_rows<4, 1>(g, grid, st); break;
       case 2: launch_rows<4, 2>(g, grid, st); break;
       case 3: launch_rows<4, 3>(g, grid, st); break;
-      case 4: launch_rows<4, 4>(g, grid, st); break;
       case 6: launch_rows<4, 6>(g, grid, st); break;
-      case 8: launch_rows<4, 8>(g, grid, st); break;
-      default: return WSMG_EINVAL;
+      default: return WSMG_EINVAL;                  // (K = 256 and 512 took the 16-wave forms above)
     }
   } else {
     return WSMG_EINVAL;
@@ -252,7 +251,8 @@ extern "C" int wsmg_rows_gemm_supported(int K) {
   const int c16 = K / 16;
   auto form = [](int n) { return n == 1 || n == 2 || n == 3 || n == 4 || n == 6 || n == 8; };
   if (c16 % 16 == 0 && c16 / 16 <= 8) return form(c16 / 16) ? 1 : 0;
-  return (c16 % 4 == 0 && c16 / 4 <= 8 && form(c16 / 4)) ? 1 : 0;
+  const int n4 = c16 / 4;                           // 4-wave forms: K = 64, 128, 192, 384 (256 and 512 are 16-wave shapes)
+  return (c16 % 4 == 0 && (n4 == 1 || n4 == 2 || n4 == 3 || n4 == 6)) ? 1 : 0;
 }
 
 extern "C" int wsmg_rows_gemm_workgroups(int M, int N) { return (M <= 0 || N <= 0) ? 0 : (N / 16) * (int)wsmg_cdiv(M, 16); }
