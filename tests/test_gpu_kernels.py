@@ -893,6 +893,54 @@ def test_fullsize_gru_sequence_split_cfg2(ops):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("name", ["GRU", "LSTM"])
+def test_state_cell_chunk_launches_equal_one_launch(ops, name):
+    """The cell description's launch_fwd / launch_bwd (ops.GRU, ops.LSTM) at T = 4, N = 3: two chunks of two steps (t0 = 0, then 2:
+    the second starts from the row the first left and hands its first-state gradient back) against one whole-sequence launch, bit
+    for bit — y, the final state, dgi (dgh for the GRU), the initial-state gradients.  One environment restarts at step 2, on the
+    chunk boundary.  Outputs start as NaN: a row a launch does not write cannot compare equal."""
+    cell = getattr(ops, name)
+    torch.manual_seed(13)
+    Tn, N, Hd = 4, 3, 512
+    G, R = cell.G, cell.state_rows
+    gi = torch.randn(Tn, N, G * Hd, device="cuda")
+    whh = torch.randn(G * Hd, Hd, device="cuda") * 0.04
+    bhh = torch.randn(G * Hd, device="cuda") * 0.1
+    h0 = torch.randn(R, N, Hd, device="cuda")
+    masks = torch.ones(Tn, N, device="cuda")
+    masks[2, 1] = 0
+    gy = torch.randn(Tn, N, Hd, device="cuda")
+    g_end = torch.randn(R, N, Hd, device="cuda")
+
+    def nan(*shape):
+        return torch.full(shape, float("nan"), device="cuda")
+
+    def run(cuts):
+        y, tail, saves = nan(Tn, N, Hd), nan(R - 1, N, Hd), [nan(*s.shape) for s in cell.new_saves(Tn, N, Hd, gi.device)]
+        for t0, steps in cuts:
+            ws = ops._rnn_workspace(cell.workspace_bytes(steps), gi.device)
+            cell.launch_fwd(gi, whh, bhh, cell.rows(h0), masks, y, tail, saves, t0, steps, ws)
+        dgi = nan(Tn, N, G * Hd)
+        dgh = nan(Tn, N, G * Hd) if cell.own_dgh else dgi
+        d_end, d0, carried = cell.rows(g_end), nan(R, N, Hd), []
+        for t0, steps in reversed(cuts):
+            d_start = d0 if t0 == 0 else nan(R, N, Hd)
+            carried.append(d_start)      # (d_end is an address: the tensor behind it must outlive the next launch)
+            ws = ops._rnn_workspace(cell.workspace_bytes(steps), gi.device)
+            cell.launch_bwd(gy, d_end, whh, cell.rows(h0), masks, y, saves, dgi, dgh, cell.rows(d_start), t0, steps, ws)
+            d_end = cell.rows(d_start)
+        torch.cuda.synchronize()
+        return {"y": y, "final state": cell.final_state(y, saves), "tail": tail, "dgi": dgi, "dgh": dgh, "d state 0": d0}
+
+    one, two = run([(0, Tn)]), run([(0, 2), (2, 2)])
+    ops.check_rnn_status()
+    assert one["final state"].shape == (R, N, Hd)
+    for k, v in one.items():
+        assert bool(torch.isfinite(v).all()), f"{name} {k}: not every element written by the whole-sequence launch"
+        assert torch.equal(two[k], v), f"{name} {k}: two chunk launches differ from one launch"
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
 def test_conv2d_with_fused_relu(ops, dt):
     """ops.conv2d(..., relu=True) == relu(conv2d(...)) (mg_map_policy.py:89-100 Conv3+ReLU heads), forward and all

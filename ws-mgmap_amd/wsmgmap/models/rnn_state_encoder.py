@@ -16,8 +16,8 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from ..recurrent import MAX_BATCH  # batch slots of the kernel; wider batches are processed in independent column chunks
 
-MAX_BATCH = 8  # batch slots of the kernel; wider batches are processed in independent column chunks
 KERNEL_HIDDEN = 512  # hidden size of the persistent LSTM kernels
 
 
@@ -66,27 +66,17 @@ class RNNStateEncoder(nn.Module):
         else:
             gi = torch.addmm(r.bias_ih_l0, x, r.weight_ih_l0.t()).view(t, n, -1)
         m = masks.reshape(t, n).float()
-        if self._is_lstm:
-            return self._forward_lstm(gi, hidden_states, m, t, n)
-        h0 = hidden_states[0].clone()  # the caller overwrites hidden_states in place (reference contract)
+        cell = ops.LSTM if self._is_lstm else ops.GRU
+        state = [s.clone() for s in hidden_states.unbind(0)]  # the caller overwrites hidden_states in place (reference contract)
+        w_hh, b_hh = r.weight_hh_l0, r.bias_hh_l0
         if n <= MAX_BATCH:
-            y = ops.masked_gru(gi, r.weight_hh_l0, r.bias_hh_l0, h0, m)
-        else:
-            y = torch.cat([ops.masked_gru(gi[:, c:c + MAX_BATCH], r.weight_hh_l0, r.bias_hh_l0, h0[c:c + MAX_BATCH],
-                                          m[:, c:c + MAX_BATCH]) for c in range(0, n, MAX_BATCH)], dim=1)
-        return y.reshape(t * n, -1), y[-1:]
-
-    def _forward_lstm(self, gi, hidden_states, m, t, n):
-        r = self.rnn
-        h0, c0 = hidden_states[0].clone(), hidden_states[1].clone()   # (overwritten in place by the caller, as above)
-        if n <= MAX_BATCH:
-            y, c_t = ops.masked_lstm(gi, r.weight_hh_l0, r.bias_hh_l0, h0, c0, m)
-        else:
-            parts = [ops.masked_lstm(gi[:, c:c + MAX_BATCH], r.weight_hh_l0, r.bias_hh_l0, h0[c:c + MAX_BATCH], c0[c:c + MAX_BATCH],
-                                     m[:, c:c + MAX_BATCH]) for c in range(0, n, MAX_BATCH)]
-            y = torch.cat([p[0] for p in parts], dim=1)
-            c_t = torch.cat([p[1] for p in parts], dim=0)
-        return y.reshape(t * n, -1), self._pack_hidden((y[-1:], c_t.unsqueeze(0)))
+            y, *tail = cell.masked(gi, w_hh, b_hh, state, m)
+        else:  # independent column chunks: outputs side by side on the batch dimension
+            parts = [cell.masked(gi[:, c:c + MAX_BATCH], w_hh, b_hh, [s[c:c + MAX_BATCH] for s in state], m[:, c:c + MAX_BATCH])
+                     for c in range(0, n, MAX_BATCH)]
+            y, *tail = [torch.cat(p, dim=1 if i == 0 else 0) for i, p in enumerate(zip(*parts))]
+        h_n = y[-1:]
+        return y.reshape(t * n, -1), torch.cat([h_n] + [c.unsqueeze(0) for c in tail]) if tail else h_n
 
     # -- stock formulation (MIOpen GRU / LSTM, split at restarts; one host sync) -------------------------
     @staticmethod

@@ -9,7 +9,7 @@ Reference: MGMapNet.forward, vlnce_baselines/models/mg_map_policy.py:220-249 —
     x               = second_state_encoder(x, h[1], masks)                        # GRU 2, T serial steps
 
 Only the two state encoders are recurrent — GRUs by default, LSTMs with MODEL.STATE_ENCODER.rnn_type = "LSTM" (both encoders share
-the type; the block runs either cell: G = 3 or 4 gate rows per unit, an LSTM's state is habitat's [h; c]) — and everything between
+the type; the block runs either cell, described once in ops/rnn.py: ops.GRU / ops.LSTM) — and everything between
 them is per ROW.  Run stage after stage (rounds 1-3) the update's critical
 path holds 2 x T dependent GRU steps forward and 2 x T backward (4 x 64 steps of 5.6-6.0 us = 1.5 ms with 224 of the 256 CUs idle)
 plus ~60 dependent small launches around them.  Here the T steps are cut into K chunks: while GRU 1 runs chunk k+1 on one
@@ -30,9 +30,9 @@ from . import _abi
 from . import ops as _ops
 from .ops import core as _core
 from .debug import sw as _sw
-from .ops import _join_side_at_end, _p, _rnn_launched, _rnn_workspace, _sfx, _stream
+from .ops import _join_side_at_end, _p, _prow, _rnn_workspace, _sfx, _stream
 
-MAX_BATCH = 8          # batch slots of the persistent GRU kernels
+MAX_BATCH = 8          # batch slots of the persistent state-encoder kernels (GRU and LSTM)
 
 
 _owned = {}      # (device index, role, stream handle) -> [workspace, bytes, timeouts seen]: the GRU chunk launches' persistent exchange images
@@ -77,11 +77,6 @@ def _post_hooks_visible():
     return _hooks_probe
 
 
-def _prow(t, row):
-    """Pointer to row `row` of a contiguous tensor (a view object per kernel argument costs more host time than the launch)."""
-    return ctypes.c_void_p(t.data_ptr() + row * t.stride(0) * t.element_size())
-
-
 def _rg(a_segs, w, w_is_kn, out_segs, r0, M, bias=None, cin_segs=None, mask=None, relu=False, wait=None, signal=None, fail_bit=1):
     """One launch of wsmg_rows_gemm_f32 on rows r0 .. r0 + M of full-batch row-major tensors: C = epilogue([A0|A1|A2] W^T) (w_is_kn
     False: W an nn.Linear weight [N, K]) or ([A0|A1|A2] W) (True: W [K, N], the backward product dY W).  a_segs / out_segs /
@@ -110,7 +105,7 @@ def _fork(main, *streams):
         st.wait_event(e)
 
 
-def rows_gemm_ok(H, C, in1, G=3):
+def rows_gemm_ok(H, C, in1, G):
     """Shapes wsmg_rows_gemm_f32 takes for the attention stage's products (hidden size H, attention width C, GRU-2 input, G gate rows
     per unit of the second recurrence): every product's reduction length is asked of the library (a multiple of 256
     alone admitted K = 1280, which it refuses)."""
@@ -177,8 +172,8 @@ class _RecurrentBlock(torch.autograd.Function):
         B = state_in.shape[0]
         T = B // N
         H = w_hh1.shape[1]
-        lstm = cfg["cell"] == "LSTM"
-        G = 4 if lstm else 3                  # gate rows per unit
+        cell = cfg["cell"]                    # ops.GRU or ops.LSTM: what the two recurrences' launches look like (ops/rnn.py)
+        G = cell.G
         assert w_hh1.shape[0] == G * H and w_hh2.shape[0] == G * H
         dev = state_in.device
         K, Tc = chunk_plan(T, K)
@@ -197,14 +192,9 @@ class _RecurrentBlock(torch.autograd.Function):
         gi1 = torch.addmm(b_ih1, state_in, w_ih1.t())
         y1 = torch.empty(T, N, H, **f32)
         y2 = torch.empty(T, N, H, **f32)
-        # saved for the backward: GRU r, z, n, W_hn h + b_hn [T, N, H] each; LSTM save_gates [T, N, 4H] (i, f, g, o) and save_c [T, N, H]
-        if lstm:
-            sv1 = [torch.empty(T, N, 4 * H, **f32), torch.empty(T, N, H, **f32)]
-            sv2 = [torch.empty(T, N, 4 * H, **f32), torch.empty(T, N, H, **f32)]
-            cT = torch.empty(2, N, H, **f32)      # the kernels' c_T outputs (the final c is save_c[T - 1] as well)
-        else:
-            sv1 = [torch.empty(T, N, H, **f32) for _ in range(4)]
-            sv2 = [torch.empty(T, N, H, **f32) for _ in range(4)]
+        sv1, sv2 = cell.new_saves(T, N, H, dev), cell.new_saves(T, N, H, dev)      # saved for the backward
+        # the kernels' outputs of the final rows below h (an LSTM's c_T: the final c is save_c[T - 1] as well), one per recurrence
+        tails = [torch.empty(cell.state_rows - 1, N, H, **f32) for _ in range(2)]
         # (projection outputs start as their bias rows and are accumulated into: `addmm` with a 1-D bias takes hipBLASLt's bias-epilogue
         #  route, whose heuristic picks ONE 256 x 128 macro-tile for a 128-row chunk — 64 us for a 33-MFLOP product)
         q1 = torch.empty(B, wq1.shape[0], **f32)
@@ -225,8 +215,7 @@ class _RecurrentBlock(torch.autograd.Function):
         h02 = h02.clone()
         tsfx = _sfx(text_k)
         ksfx = _sfx(tokens)
-        nbytes = lib.wsmg_gru_workspace_bytes(Tc)
-        wsb = lib.wsmg_lstm_state_workspace_bytes if lstm else lib.wsmg_gru_workspace_bytes
+        nbytes = cell.workspace_bytes(Tc)
         # (wsmgmap.parallel holds its buckets until this block's backward has queued its kernels: see _launch_ready there)
         _core.chain_in_flight = bool(sa is not main and any(ctx.needs_input_grad))
         forked = False
@@ -241,37 +230,21 @@ class _RecurrentBlock(torch.autograd.Function):
         # chunk launches run on workspaces this module owns (no clear in front of every launch); a HIP-graph capture bakes the
         # launch-unique tags in, so replays need the clearing form
         owned = not torch.cuda.is_current_stream_capturing()
+        own_chunks = owned and cell.fwd[1] is not None      # (no owned LSTM form: its chunk launches clear a fresh workspace)
 
-        def gru(gi, w_hh, b_hh, h0, y, sv, k, role, ci):
-            t0 = k * Tc
-            if lstm:
-                # chunk k starts from (y[t0 - 1], save_c[t0 - 1]): the clearing entry point (there is no owned LSTM form)
-                hk, ck = (_p(h0), _prow(h0, 1)) if k == 0 else (_prow(y, t0 - 1), _prow(sv[1], t0 - 1))
-                ws = _rnn_workspace(nbytes, dev)
-                _abi.call("wsmg_lstm_state_fwd", _prow(gi, t0), _p(w_hh), _p(b_hh), hk, ck, _prow(m, t0), Tc, N, H, _prow(y, t0),
-                          _prow(cT, ci), _prow(sv[0], t0), _prow(sv[1], t0), _p(ws), _stream())
-                _rnn_launched()
-                return
-            hk = h0 if k == 0 else y[t0 - 1]
-            ws = _owned_ws(dev, role, nbytes) if owned else _rnn_workspace(nbytes, dev)
-            _abi.call("wsmg_gru_fwd_owned" if owned else "wsmg_gru_fwd", _prow(gi, t0), _p(w_hh), _p(b_hh), _p(hk), _prow(m, t0), Tc, N, H,
-                      _prow(y, t0), *[_prow(s_, t0) for s_ in sv], _p(ws), _stream())
-            _rnn_launched()
-
-        def chained(gi, w_hh, b_hh, h0, y, sv, role, ci, in_cnt, in_target, out_cnt):
-            ws = _p(_owned_ws(dev, role, wsb(T)))
-            if lstm:
-                _abi.call("wsmg_lstm_state_fwd_chain", _p(gi), _p(w_hh), _p(b_hh), _p(h0), _prow(h0, 1), _p(m), T, N, H, _p(y), _prow(cT, ci),
-                          *[_p(s_) for s_ in sv], ws, Tc, in_cnt, in_target, out_cnt, _stream())
+        def rnn(gi, w_hh, b_hh, h0, y, sv, ci, role, t0=0, steps=T, link=None):
+            # one launch of a recurrence: chunk k of it (t0 = k Tc: it starts from what step t0 - 1 left), or, with
+            # link = (in_cnt, in_target, out_cnt), the whole sequence chained chunk by chunk to the attention stage
+            if link or own_chunks:
+                ws = _owned_ws(dev, role, cell.workspace_bytes(steps) if link else nbytes)
             else:
-                _abi.call("wsmg_gru_fwd_chain", _p(gi), _p(w_hh), _p(b_hh), _p(h0), _p(m), T, N, H, _p(y), *[_p(s_) for s_ in sv],
-                          ws, Tc, in_cnt, in_target, out_cnt, _stream())
-            _rnn_launched()
+                ws = _rnn_workspace(nbytes, dev)
+            cell.launch_fwd(gi, w_hh, b_hh, cell.rows(h0), m, y, tails[ci], sv, t0, steps, ws, own_chunks, link and (Tc, *link))
 
         gi1v, gi2v = gi1.view(T, N, G * H), gi2.view(T, N, G * H)
         y1r = y1.view(B, H)
         multi = sa is not main
-        fail_bit = 32 if lstm else 1      # a chained product's wait names the recurrence it waits for (status bits of wsmg_rnn.hip)
+        fail_bit = cell.fwd_bit           # a chained product's wait names the recurrence it waits for (status bits of wsmg_rnn.hip)
         # round 5 — chained: each recurrence is ONE whole-sequence launch; the attention stage's first product of chunk k waits (on the
         # device) for the first recurrence's arrivals on counter k, its last product signals counter K + k, which the second
         # recurrence waits for at the first step of chunk k (csrc/wsmg_rnn.hip chain_wait).  No chunk prologues (W_hh into registers:
@@ -280,10 +253,10 @@ class _RecurrentBlock(torch.autograd.Function):
         cnt = None
         if chain:
             cnt = torch.zeros(3 * K, device=dev, dtype=torch.int32)     # [arrivals in | arrivals out | gate words] per chunk
-            nwg = int(lib.wsmg_lstm_state_chain_workgroups() if lstm else lib.wsmg_gru_chain_workgroups())
+            nwg = cell.chain_workgroups()
             _fork(main, sa, sg)          # (the counters are zeroed on main)
             forked = True
-            chained(gi1, w_hh1, b_hh1, h01, y1, sv1, "f1", 0, None, 0, _p(cnt))
+            rnn(gi1v, w_hh1, b_hh1, h01, y1, sv1, 0, "f1", link=(None, 0, _p(cnt)))
             _ops.mark("f.g1")
         if multi and not forked:
             _fork(main, sa, sg)
@@ -292,7 +265,7 @@ class _RecurrentBlock(torch.autograd.Function):
         # instead of eight times (the host has < 1.5 ms of lead over the GPU in this part of an update)
         ev1, eva = [], []
         for k in range(0 if chain else K):
-            gru(gi1v, w_hh1, b_hh1, h01, y1, sv1, k, "f1", 0)                          # main
+            rnn(gi1v, w_hh1, b_hh1, h01, y1, sv1, 0, "f1", k * Tc, Tc)                 # main
             _ops.mark("f.g1.%d" % k)
             if multi:
                 e1 = torch.cuda.Event()
@@ -339,13 +312,13 @@ class _RecurrentBlock(torch.autograd.Function):
                     eva.append(ea)
         with torch.cuda.stream(sg):
             if chain:
-                chained(gi2, w_hh2, b_hh2, h02, y2, sv2, "f2", 1, ctypes.c_void_p(cnt.data_ptr() + 4 * K),
-                        int(lib.wsmg_rows_gemm_workgroups(rows, G * H)), None)
+                rnn(gi2v, w_hh2, b_hh2, h02, y2, sv2, 1, "f2", link=(ctypes.c_void_p(cnt.data_ptr() + 4 * K),
+                                                                     int(lib.wsmg_rows_gemm_workgroups(rows, G * H)), None))
                 _ops.mark("f.g2")
             for k in range(0 if chain else K):
                 if multi:
                     sg.wait_event(eva[k])
-                gru(gi2v, w_hh2, b_hh2, h02, y2, sv2, k, "f2", 1)
+                rnn(gi2v, w_hh2, b_hh2, h02, y2, sv2, 1, "f2", k * Tc, Tc)
                 _ops.mark("f.g2.%d" % k)
         if sg is not main:
             main.wait_stream(sg)
@@ -354,21 +327,18 @@ class _RecurrentBlock(torch.autograd.Function):
                               gi1, y1, *sv1, y2, *sv2, q1, text_emb, attn_text, q2, qf, att_map, map_emb if x is None else x, xc)
         ctx.x_is_parts = x is None
         ctx.chain = chain
-        ctx.lstm = lstm
+        ctx.cell = cell
         ctx.cfg = (N, K, Tc, scale, sink, tuple(wk.shape), text_mask is not None)
         ctx.params = (w_ih1, b_ih1, w_hh1, b_hh1, wq1, bq1, wq2, bq2, wk, bk, wc, bc, w_ih2, b_ih2, w_hh2, b_hh2)
-        if lstm:      # habitat's [h; c] layout
-            h1n, h2n = torch.cat([y1[-1:], sv1[1][-1:]]), torch.cat([y2[-1:], sv2[1][-1:]])
-        else:
-            h1n, h2n = y1[-1:].clone(), y2[-1:].clone()
+        h1n, h2n = cell.final_state(y1, sv1), cell.final_state(y2, sv2)      # habitat's layout: [h] or [h; c]
         ctx.mark_non_differentiable(h1n, h2n)
         ctx.set_materialize_grads(False)
         return y2.view(B, H), att_map, h1n, h2n
 
     @staticmethod
     def backward(ctx, dy2, datt, _dh1, _dh2):
-        lstm = ctx.lstm
-        ns = 2 if lstm else 4        # saved tensors per recurrence (see forward)
+        cell = ctx.cell
+        ns = len(cell.save_widths)   # saved tensors per recurrence (see forward)
         saved = ctx.saved_tensors
         (state_in, tokens, text_k, text_v, inverse, m, h01, h02, w_ih1, w_hh1, wq1, wq2, wk2, wc, w_ih2, w_hh2, gi1, y1) = saved[:18]
         sv1, y2, sv2 = saved[18:18 + ns], saved[18 + ns], saved[19 + ns:19 + 2 * ns]
@@ -377,7 +347,7 @@ class _RecurrentBlock(torch.autograd.Function):
         N, K, Tc, scale, sink, wk_shape, _ = ctx.cfg
         T = y1.shape[0]
         H = y1.shape[2]
-        G = 4 if lstm else 3
+        G = cell.G
         B = T * N
         rows = Tc * N
         dev = y1.device
@@ -417,13 +387,13 @@ class _RecurrentBlock(torch.autograd.Function):
         dy2 = torch.zeros(T, N, H, **f32) if dy2 is None else dy2.contiguous().float().view(T, N, H)
         datt = None if datt is None else datt.contiguous().float()
         lib = _abi.lib()
-        nbytes = lib.wsmg_gru_workspace_bytes(Tc)
+        nbytes = cell.workspace_bytes(Tc)
         tsfx, ksfx = _sfx(text_k), _sfx(tokens)
         # full-batch gradient buffers, allocated on the main stream and used on the others: the allocator must not hand their memory
         # to a later main-stream allocation while a side stream still works on them
         # (an LSTM's one gate gradient is both the gradient of gi and of W_hh h + b_hh: dgh is dgi; its state gradients are [dh; dc])
         dgi2, dgi1 = torch.empty(T, N, G * H, **f32), torch.empty(T, N, G * H, **f32)
-        dgh2, dgh1 = (dgi2, dgi1) if lstm else (torch.empty(T, N, 3 * H, **f32), torch.empty(T, N, 3 * H, **f32))
+        dgh2, dgh1 = (torch.empty_like(dgi2), torch.empty_like(dgi1)) if cell.own_dgh else (dgi2, dgi1)
         dxc = torch.empty(B, wc.shape[0], **f32)
         dqf, dq2, dq1 = torch.empty(B, C, **f32), torch.empty(B, wq2.shape[0], **f32), torch.empty(B, wq1.shape[0], **f32)
         dtext = torch.empty(B, C, **f32)
@@ -431,10 +401,9 @@ class _RecurrentBlock(torch.autograd.Function):
         dl = torch.empty(B, L, **f32)
         dstate = torch.empty(T, N, H, **f32)
         dtokens = torch.empty_like(tokens)
-        sh = (2, N, H) if lstm else (N, H)
-        dh01, dh02 = torch.empty(sh, **f32), torch.empty(sh, **f32)
-        carry2 = [torch.empty(sh, **f32) for _ in range(2)]
-        carry1 = [torch.empty(sh, **f32) for _ in range(2)]
+        dh01, dh02 = torch.empty(h01.shape, **f32), torch.empty(h02.shape, **f32)
+        carry2 = [torch.empty(h02.shape, **f32) for _ in range(2)]
+        carry1 = [torch.empty(h01.shape, **f32) for _ in range(2)]
         if multi:
             # these are allocated from the main stream's pool and used on the others: they must not be handed to a later main-stream
             # allocation while a side stream still works on them — a reference is held until the pass's final callbacks, which run
@@ -451,53 +420,36 @@ class _RecurrentBlock(torch.autograd.Function):
         dgi2r = dgi2.view(B, G * H)
 
         owned = not torch.cuda.is_current_stream_capturing()
-        wsb = lib.wsmg_lstm_state_workspace_bytes if lstm else lib.wsmg_gru_workspace_bytes
+        own_chunks = owned and cell.bwd[1] is not None
 
-        def gru_bwd(dy, w_hh, h0, y, sv, dgi, dgh, dh0_out, carry, k, role):
-            t0 = k * Tc
-            dhT = None if k == K - 1 else carry[(k + 1) & 1]
-            out = dh0_out if k == 0 else carry[k & 1]
-            if lstm:
-                # chunk k: c_{t0-1} = save_c[t0 - 1]; (dhT, dcT) = the later chunk's (dh0, dc0); the clearing entry point
-                ck = _prow(h0, 1) if k == 0 else _prow(sv[1], t0 - 1)
-                ws = _rnn_workspace(nbytes, dev)
-                _abi.call("wsmg_lstm_state_bwd", _prow(dy, t0), _p(dhT), None if dhT is None else _prow(dhT, 1), _p(w_hh), ck, _prow(m, t0),
-                          _prow(sv[0], t0), _prow(sv[1], t0), Tc, N, H, _prow(dgi, t0), _p(out), _prow(out, 1), _p(ws), _stream())
-                _rnn_launched()
-                return
-            hk = h0 if k == 0 else y[t0 - 1]
-            ws = _owned_ws(dev, role, nbytes) if owned else _rnn_workspace(nbytes, dev)
-            _abi.call("wsmg_gru_bwd_owned" if owned else "wsmg_gru_bwd", _prow(dy, t0), _p(dhT), _p(w_hh), _p(hk), _prow(m, t0), _prow(y, t0),
-                      *[_prow(s_, t0) for s_ in sv], Tc, N, H, _prow(dgi, t0), _prow(dgh, t0), _p(out), _p(ws), _stream())
-            _rnn_launched()
-
-        def chained_bwd(dy, w_hh, h0, y, sv, dgi, dgh, dh0_out, role, in_cnt, in_target, out_cnt):
-            ws = _p(_owned_ws(dev, role, wsb(T)))
-            if lstm:
-                _abi.call("wsmg_lstm_state_bwd_chain", _p(dy), None, None, _p(w_hh), _prow(h0, 1), _p(m), *[_p(s_) for s_ in sv], T, N, H,
-                          _p(dgi), _p(dh0_out), _prow(dh0_out, 1), ws, Tc, in_cnt, in_target, out_cnt, _stream())
+        def rnn_bwd(dy, w_hh, h0, y, sv, dgi, dgh, dh0_out, carry, role, k=0, steps=T, link=None):
+            # as `rnn` in forward; chunk k takes the gradient of its final state from chunk k + 1 and leaves that of its first
+            # state to chunk k - 1 (two buffers in turn); the whole-sequence launch (k = 0, steps = T) has neither
+            last = link or k == K - 1
+            if link or own_chunks:
+                ws = _owned_ws(dev, role, cell.workspace_bytes(steps) if link else nbytes)
             else:
-                _abi.call("wsmg_gru_bwd_chain", _p(dy), None, _p(w_hh), _p(h0), _p(m), _p(y), *[_p(s_) for s_ in sv], T, N, H,
-                          _p(dgi), _p(dgh), _p(dh0_out), ws, Tc, in_cnt, in_target, out_cnt, _stream())
-            _rnn_launched()
+                ws = _rnn_workspace(nbytes, dev)
+            cell.launch_bwd(dy, None if last else cell.rows(carry[(k + 1) & 1]), w_hh, cell.rows(h0), m, y, sv, dgi, dgh,
+                            cell.rows(dh0_out if k == 0 else carry[k & 1]), k * Tc, steps, ws, own_chunks, link and (Tc, *link))
 
         # stream by stream, as in forward: GRU 2's chunks (last chunk first), the attention stage's, GRU 1's
         ev2, eva = {}, {}
         chain = multi and rg and owned and ctx.chain and K > 1
         cnt = None
-        fail_bit = 64 if lstm else 2
+        fail_bit = cell.bwd_bit
         if chain:     # (see forward: one launch per recurrence, device-side waits on per-chunk arrival counters)
             cnt = torch.zeros(3 * K, device=dev, dtype=torch.int32)     # [arrivals in | arrivals out | gate words] per chunk
             keep.append(cnt)
-            nwg = int(lib.wsmg_lstm_state_chain_workgroups() if lstm else lib.wsmg_gru_chain_workgroups())
+            nwg = cell.chain_workgroups()
         if multi:
             _fork(main, sg, sa)      # once, behind everything the pass has queued on main so far (buffers, the chain's counters)
         with torch.cuda.stream(sg):
             if chain:
-                chained_bwd(dy2, w_hh2, h02, y2, sv2, dgi2, dgh2, dh02, "b2", None, 0, _p(cnt))
+                rnn_bwd(dy2, w_hh2, h02, y2, sv2, dgi2, dgh2, dh02, carry2, "b2", link=(None, 0, _p(cnt)))
                 _ops.mark("b.g2")
             for k in range(K - 1 if not chain else -1, -1, -1):
-                gru_bwd(dy2, w_hh2, h02, y2, sv2, dgi2, dgh2, dh02, carry2, k, "b2")
+                rnn_bwd(dy2, w_hh2, h02, y2, sv2, dgi2, dgh2, dh02, carry2, "b2", k, Tc)
                 _ops.mark("b.g2.%d" % k)
                 if multi:
                     ev2[k] = torch.cuda.Event()
@@ -544,13 +496,13 @@ class _RecurrentBlock(torch.autograd.Function):
                     eva[k] = torch.cuda.Event()
                     eva[k].record(sa)
         if chain:
-            chained_bwd(dstate, w_hh1, h01, y1, sv1, dgi1, dgh1, dh01, "b1", ctypes.c_void_p(cnt.data_ptr() + 4 * K),
-                        int(lib.wsmg_rows_gemm_workgroups(rows, H)), None)
+            rnn_bwd(dstate, w_hh1, h01, y1, sv1, dgi1, dgh1, dh01, carry1, "b1", link=(ctypes.c_void_p(cnt.data_ptr() + 4 * K),
+                                                                                 int(lib.wsmg_rows_gemm_workgroups(rows, H)), None))
             _ops.mark("b.g1")
         for k in range(K - 1 if not chain else -1, -1, -1):
             if multi:
                 main.wait_event(eva[k])
-            gru_bwd(dstate, w_hh1, h01, y1, sv1, dgi1, dgh1, dh01, carry1, k, "b1")      # main
+            rnn_bwd(dstate, w_hh1, h01, y1, sv1, dgi1, dgh1, dh01, carry1, "b1", k, Tc)      # main
             _ops.mark("b.g1.%d" % k)
         d_state_in = torch.mm(dgi1.view(B, G * H), w_ih1) if ctx.needs_input_grad[1] else None
         # gradients of the shared instruction sets (they feed the instruction branch's backward, on ITS stream): after the last
@@ -574,10 +526,7 @@ class _RecurrentBlock(torch.autograd.Function):
             # db_hh = db_ih = colsum(dgates), two tensors of their own
             db_ih2, db_hh2, dbc, dbq2, dbq1, db_hh1, db_ih1 = _ops.colsum_multi([g2, gh2, dxc, dq2, dq1, gh1, g1])
             dw_ih2 = g2.t() @ xc
-            if lstm:
-                h01, h02 = h01[0], h02[0]           # (the h halves of [h; c]: dW_hh = dgates^T (mask * h_prev))
-            hp2 = torch.cat([h02.unsqueeze(0), y2[:-1]], dim=0) * m.unsqueeze(-1)
-            dw_hh2 = gh2.t() @ hp2.view(B, H)
+            dw_hh2 = cell.hidden_weight_grads(dgh2, h02, y2, m)      # dgh^T (mask * h_prev): an LSTM's h_prev is the h row of [h; c]
             if rg:
                 x = torch.cat([y1r, text_emb, x], dim=1)          # (x held map_emb)
             dwc = dxc.t() @ x
@@ -586,8 +535,7 @@ class _RecurrentBlock(torch.autograd.Function):
             dbk = torch.zeros(wk_shape[0], **f32) if params[9] is not None else None
             dwq2 = dq2.t() @ text_emb
             dwq1 = dq1.t() @ y1r
-            hp1 = torch.cat([h01.unsqueeze(0), y1[:-1]], dim=0) * m.unsqueeze(-1)
-            dw_hh1 = gh1.t() @ hp1.view(B, H)
+            dw_hh1 = cell.hidden_weight_grads(dgh1, h01, y1, m)
             dw_ih1 = g1.t() @ state_in
         pgrads = [dw_ih1, db_ih1, dw_hh1, db_hh1, dwq1, dbq1, dwq2, dbq2, dwk, dbk, dwc, dbc, dw_ih2, db_ih2, dw_hh2, db_hh2]
         _core.chain_in_flight = False      # every kernel of this block's backward is queued: the gradient exchange may issue buckets again
@@ -623,7 +571,7 @@ def recurrent_block(state_in, tokens, text, masks, h01, h02, net, n_env, chunks=
     r1, r2 = net.state_encoder.rnn, net.second_state_encoder.rnn
     tk, tv, tm, inv = text
     cfg = dict(N=int(n_env), chunks=int(chunks), scale=float(net._scale_f), sink=sink, text_ready=text_ready, streams=tuple(streams or ()),
-               cell=cell)
+               cell=_ops.LSTM if cell == "LSTM" else _ops.GRU)
     return _RecurrentBlock.apply(
         cfg, state_in.contiguous(), tokens.contiguous(), tk, tv, tm, inv, masks.reshape(-1).float().contiguous(), h01, h02,
         r1.weight_ih_l0, r1.bias_ih_l0, r1.weight_hh_l0, r1.bias_hh_l0,
