@@ -509,6 +509,15 @@ int wsmg_collate_pad_nhwc_bf16(const void* const* src, const int* lengths, int N
 int wsmg_collate_ego_sparse_nhwc_bf16(const void* const* bits, const void* const* off, const void* const* base,
                                       const void* const* vals, const int* lengths, int N, int T, int C, int HW, float pad,
                                       void* dst, wsmg_stream_t stream);
+/* The WRITER of that form, for one rollout step of B independent rows (environments): x = float32 channels-last [B][HW][64], what
+ * the map retrieval writes.  Every element is cast to float16 first (round to nearest even, overflow to +-inf, subnormals kept: the
+ * on-disk dtype of common_trainer.py:514-532) and is present iff the float16 bit pattern is not 0 (-0.0 is present; a float32 that
+ * rounds to +0 is absent).  bits [B][HW][8] (8-byte aligned), off uint32 [B][HW] (non-zeros of the row in front of pixel p),
+ * nnz [B], vals = float16 [B][HW * 64]: row b's values compacted at the front of its own region, pixel by pixel, channel by channel
+ * (the rest of the region is not written).  Bit-identical to codec.sparse_pack_ego of the float16 map, and from run to run.
+ * WSMG_EINVAL before anything is enqueued: C != 64, B or HW <= 0, B > 65535, HW * 64 >= 2^32, a null pointer. */
+int wsmg_ego_sparse_pack(const float* x, int B, int C, int HW, uint8_t* bits, uint32_t* off, int64_t* nnz, void* vals,
+                         wsmg_stream_t stream);
 
 /* ============================ persistent masked-GRU state encoders ============================ */
 /* habitat-lab RNNStateEncoder (GRU, hidden 512) as used at mg_map_policy.py:118-123,147-152,220-227,242-249:

@@ -5,3 +5,4 @@ from .codec import (pack_record, unpack_record, change_data_type, pack_record_ra
 from .dataset import TrajectoryDataset, block_shuffle, shard_range  # noqa: F401
 from .collate import DeviceCollator, collate_fn  # noqa: F401
 from .feeder import DeviceFeeder  # noqa: F401
+from .recorder import SparseEgoRecorder, select_steps  # noqa: F401

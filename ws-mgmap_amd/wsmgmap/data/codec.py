@@ -88,7 +88,9 @@ RAW_MAGIC = b"WSMGRAW1"
 # (-0.0 counts as non-zero: the expansion is bit-exact.)  `wsmg_collate_ego_sparse_nhwc_bf16` expands it on the device straight into
 # the padded channels-last bf16 tensor the bf16 policy reads — one wave per pixel: the pixel's 8 presence bytes are one word, lane c's
 # value sits at base + off + popcount(word & lanes below c): a coalesced gather.  PCIe bytes per step at 30 % non-zeros: 0.12 (bits
-# + offsets) + 0.38 (values) MB instead of 1.28.
+# + offsets) + 0.38 (values) MB instead of 1.28.  The rollout can write this form directly: `wsmg_ego_sparse_pack` packs a step's float32
+# map on the device (cast to float16 first, then the rule above), `recorder.SparseEgoRecorder` keeps the steps of running episodes and
+# hands `pack_record_raw` the same five arrays `sparse_pack_ego` makes of the dense map.
 SPARSE_EGO = "rgb_ego_map"
 SPARSE_SUFFIXES = ("__bits", "__off", "__base", "__vals", "__shape")
 

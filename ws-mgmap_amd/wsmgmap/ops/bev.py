@@ -137,3 +137,40 @@ def map_retrieve(global_map, gps, compass, E, resolution=0.12, fused=None):
     scratch = torch.empty(B, E, E, C, device=gps.device, dtype=torch.float32)
     _abi.call("wsmg_map_retrieve", _p(global_map), _p(gps), _p(compass), B, C, E, G, float(resolution), _p(scratch), _p(out), _stream())
     return out
+
+
+def ego_channels_last_dims(ego):
+    """(B, H, W, C) of an ego map that is channels-last in memory: `observations['rgb_ego_map']` as the mapping module leaves it
+    ([B,C,H,W]: map_retrieve's NHWC tensor, permuted) or a plain contiguous NHWC tensor [B,H,W,C]; anything else raises."""
+    if not torch.is_tensor(ego) or not ego.is_cuda:
+        raise _abi.WsmgError("wsmgmap operators need GPU tensors: the HIP path is the only path (no CPU fallback)")
+    if ego.dim() != 4:
+        raise _abi.WsmgError(f"ego map: [B,C,H,W] over channels-last memory or NHWC [B,H,W,C] expected, got {tuple(ego.shape)}")
+    if ego.shape[1] == 64 and ego.permute(0, 2, 3, 1).is_contiguous():
+        B, C, H, W = ego.shape
+    elif ego.is_contiguous():
+        B, H, W, C = ego.shape
+    else:
+        raise _abi.WsmgError(f"ego map: must be channels-last in memory, got shape {tuple(ego.shape)} strides {ego.stride()}")
+    return int(B), int(H), int(W), int(C)
+
+
+@torch.no_grad()
+def ego_sparse_pack(ego):
+    """One rollout step of the ego map -> the sparse record form of wsmgmap/data/codec.py, packed on the device:
+    (bits uint8 [B,H*W,8], off uint32 [B,H*W], nnz int64 [B], vals float16 [B,H*W*64]); row b's values are vals[b, :nnz[b]],
+    the rest of its region is not written.  ego: float32, channels-last in memory (`ego_channels_last_dims`).  Bit for bit what
+    codec.sparse_pack_ego makes of the float16 map, row by row.  The format is defined for 64 channels only."""
+    B, H, W, C = ego_channels_last_dims(ego)
+    _f32(ego)
+    HW = H * W
+    if C != 64:
+        raise _abi.WsmgError(f"ego_sparse_pack: the sparse ego map is defined for 64 channels, got {C} (other maps are stored dense)")
+    if B <= 0 or HW <= 0:
+        raise _abi.WsmgError(f"ego_sparse_pack: empty map {tuple(ego.shape)}")
+    bits = torch.empty(B, HW, 8, device=ego.device, dtype=torch.uint8)
+    off = torch.empty(B, HW, device=ego.device, dtype=torch.uint32)
+    nnz = torch.empty(B, device=ego.device, dtype=torch.int64)
+    vals = torch.empty(B, HW * 64, device=ego.device, dtype=torch.float16)
+    _abi.call("wsmg_ego_sparse_pack", _p(ego), B, C, HW, _p(bits), _p(off), _p(nnz), _p(vals), _stream())
+    return bits, off, nnz, vals
