@@ -2,27 +2,35 @@
 
 Reference: MGMapNet.forward, vlnce_baselines/models/mg_map_policy.py:220-249 —
 
-    state           = state_encoder(state_in, h[0], masks)                       # GRU 1, T serial steps
+    state           = state_encoder(state_in, h[0], masks)                       # recurrence 1, T serial steps
     text_embedding  = _attn(state_text_q_layer(state), text_k, text_v, text_mask) # per row
     map_embedding   = _attn(text_map_q_layer(text_embedding), map_k, map_v)       # per row
     x               = second_state_compress(cat(state, text_embedding, map_embedding))
-    x               = second_state_encoder(x, h[1], masks)                        # GRU 2, T serial steps
+    x               = second_state_encoder(x, h[1], masks)                        # recurrence 2, T serial steps
 
 Only the two state encoders are recurrent — GRUs by default, LSTMs with MODEL.STATE_ENCODER.rnn_type = "LSTM" (both encoders share
-the type; the block runs either cell, described once in ops/rnn.py: ops.GRU / ops.LSTM) — and everything between
-them is per ROW.  Run stage after stage (rounds 1-3) the update's critical
-path holds 2 x T dependent GRU steps forward and 2 x T backward (4 x 64 steps of 5.6-6.0 us = 1.5 ms with 224 of the 256 CUs idle)
-plus ~60 dependent small launches around them.  Here the T steps are cut into K chunks: while GRU 1 runs chunk k+1 on one
-stream, the attention stage of chunk k runs on a second and GRU 2 of chunk k on a third (the carried hidden state is bit-exact
-across split launches: tests/test_gpu_kernels.py::test_fullsize_gru_sequence_split_cfg2), and the reverse order in backward:
-T + T/K serial steps each way instead of 2 T.  Weight and bias gradients are NOT part of the chain: the backward chain only
-produces activation gradients into full-batch buffers, and every parameter gradient is one full-batch GEMM / column sum on a
-"leaf" stream that joins the main stream when the whole backward pass ends (nothing but the optimizer waits for them).
+the type; the cell is described once in ops/rnn.py: ops.GRU / ops.LSTM) — and everything between them, the attention STAGE, is per
+ROW.  Run stage after stage the update's critical path holds 2 x T dependent steps forward and 2 x T backward (4 x 64 steps of
+5.6-6.0 us = 1.5 ms with 224 of the 256 CUs idle) plus ~60 dependent small launches around them.  Here the T steps are cut into K
+chunks: while recurrence 1 runs chunk k+1 on one stream, the stage of chunk k runs on a second and recurrence 2 of chunk k on a third
+(the carried hidden state is bit-exact across split launches: tests/test_gpu_kernels.py::test_fullsize_gru_sequence_split_cfg2),
+and the reverse order in backward: T + T/K serial steps each way instead of 2 T.
+
+The schedule is written once for both directions (_pipeline: it alone knows how chunks are ordered — an event per chunk and edge, or
+whole-sequence launches chained through _ChainCounters — and the one-stream case); the stage's dense layers come in two forms, each
+a "chunk forward / chunk backward" pair over one namespace of named buffers, chosen once per call (_RowsStage, _LibStage).
+
+Weight and bias gradients are NOT part of the chain: the backward chain only produces activation gradients into full-batch
+buffers, and every parameter gradient is one full-batch GEMM / column sum on a "leaf" stream that joins the main stream when the
+whole backward pass ends (nothing but the optimizer waits for them).
 
 Arithmetic: the same kernels and the same float32 GEMMs as the staged route, row for row; chunking changes no reduction order
 inside a row except where the GEMM library picks another kernel for 128 rows than for 512 (float32 rounding differences, <= 1e-6
 relative; tests/test_gpu_round4.py holds the block against the staged route)."""
+import contextlib
 import ctypes
+import functools
+from types import SimpleNamespace
 
 import torch
 
@@ -96,15 +104,6 @@ def _rg(a_segs, w, w_is_kn, out_segs, r0, M, bias=None, cin_segs=None, mask=None
               None if wait is None else ctypes.c_void_p(wait[2]), _stream())
 
 
-def _fork(main, *streams):
-    """Every stream of `streams` waits for what `main` has queued so far — ONE event record on `main` (stream.wait_stream(main)
-    records one per call, and a record between two dependent kernels costs the recording stream ~3 us: tools/exp/event_cost.hip)."""
-    e = torch.cuda.Event()
-    e.record(main)
-    for st in streams:
-        st.wait_event(e)
-
-
 def rows_gemm_ok(H, C, in1, G):
     """Shapes wsmg_rows_gemm_f32 takes for the attention stage's products (hidden size H, attention width C, GRU-2 input, G gate rows
     per unit of the second recurrence): every product's reduction length is asked of the library (a multiple of 256
@@ -163,212 +162,300 @@ def chunk_plan(T, want):
     return k, T // k
 
 
+class _ChainCounters:
+    """The device-side counters of one chained pass: 3 K int32 words zeroed on the current stream, [arrivals in | arrivals out | gate
+    words] per chunk.  The producing recurrence adds `in_target` arrivals to word k when chunk k's outputs are complete; the stage's
+    first product of chunk k waits for them (its gate launch reports in word 2 K + k) and its last product's workgroups add
+    `out_target` arrivals to word K + k, which the consuming recurrence waits for at the first step of chunk k (csrc/wsmg_rnn.hip
+    chain_wait / chain_signal).  No other code computes an address into the tensor: one wrong by a word is a missed wait."""
+
+    def __init__(self, K, dev, in_target, out_target):
+        self.words = torch.zeros(3 * K, device=dev, dtype=torch.int32)
+        self.K, self.base, self.in_target = K, self.words.data_ptr(), int(in_target)
+        self.head = (None, 0, ctypes.c_void_p(self.base))      # (in counters, in target, out counters) of the producer's whole-sequence launch
+        self.tail = (ctypes.c_void_p(self.base + 4 * K), int(out_target), None)      # ... and of the consumer's
+
+    def wait(self, k):        # `wait` of the stage's first product of chunk k (see _rg): producer chunk k's counter, its target, the gate word
+        return self.base + 4 * k, self.in_target, self.base + 4 * (2 * self.K + k)
+
+    def signal(self, k):      # `signal` of its last product
+        return self.base + 4 * (self.K + k)
+
+
+def _workspaces(cell, entry, dev, T, Tc):
+    """The workspaces of one pass's recurrence launches (entry: cell.fwd or cell.bwd) -> (owned, own_chunks, pick); pick(role, whole):
+    the workspace for a launch of `role` on the current stream, of a chunk or (chained) of the whole sequence.  Launches run on
+    workspaces this module owns (no clear in front of every launch); a HIP-graph capture bakes the launch-unique tags in, so replays
+    need the clearing form."""
+    owned = not torch.cuda.is_current_stream_capturing()
+    own_chunks = owned and entry[1] is not None      # (no owned LSTM form: its chunk launches clear a fresh workspace)
+    nbytes = cell.workspace_bytes(Tc)
+
+    def pick(role, whole):
+        if whole or own_chunks:
+            return _owned_ws(dev, role, cell.workspace_bytes(T) if whole else nbytes)
+        return _rnn_workspace(nbytes, dev)
+    return owned, own_chunks, pick
+
+
+class _Stage:
+    """The attention stage on rows k * rows .. (k + 1) * rows of the full-batch buffers `b` (a namespace: the forward's buffers; in
+    backward what it saved and the gradient buffers).  The two attention kernels are here, the dense layers around them in the
+    subclasses' fwd / bwd (k, wait, signal): wait / signal as _rg takes them, None unless chained (`chainable` forms only)."""
+    chainable = False
+
+    def __init__(self, b, rows, fail_bit):
+        self.b, self.rows, self.fail_bit = b, rows, fail_bit    # (the status bit a chained product's wait reports: the recurrence it waits for)
+        self.tsfx, self.ksfx, self.L, self.I, self.C = _sfx(b.text_k), _sfx(b.tokens), b.text_k.shape[1], b.tokens.shape[1], b.tokens.shape[2]
+
+    def alloc_fwd(self):
+        pass
+
+    alloc_bwd = begin_fwd = alloc_fwd
+
+    def text_fwd(self, r0):
+        b = self.b
+        _abi.call("wsmg_attn_shared_fwd" + self.tsfx, _prow(b.q1, r0), _p(b.text_k), _p(b.text_v), _p(b.text_mask), _prow(b.inverse, r0),
+                  b.scale, self.rows, self.L, self.C, _prow(b.text_emb, r0), _prow(b.attn_text, r0), _stream())
+
+    def map_fwd(self, r0):
+        b = self.b
+        _abi.call("wsmg_attn_fwd" + self.ksfx, _prow(b.qf, r0), _prow(b.tokens, r0), _prow(b.tokens, r0), None, b.scale, self.rows, self.I,
+                  self.C, _prow(b.map_emb, r0), _prow(b.att_map, r0), _stream())
+
+    def map_bwd(self, r0, dmap):
+        b = self.b
+        _abi.call("wsmg_attn_bwd" + self.ksfx, _prow(b.qf, r0), _prow(b.tokens, r0), _prow(b.tokens, r0), _prow(b.att_map, r0), dmap,
+                  None if b.datt is None else _prow(b.datt, r0), b.scale, self.rows, self.I, self.C, _prow(b.dqf, r0), _prow(b.dtokens, r0),
+                  _prow(b.dtokens, r0), _stream())
+
+    def text_bwd(self, r0):
+        b = self.b
+        _abi.call("wsmg_attn_shared_bwd" + self.tsfx, _prow(b.q1, r0), _p(b.text_k), _p(b.text_v), _prow(b.attn_text, r0), _prow(b.dtext, r0),
+                  None, _prow(b.inverse, r0), b.scale, self.rows, self.L, self.C, _prow(b.dq1, r0), _prow(b.dl, r0), _stream())
+
+
+class _RowsStage(_Stage):
+    """Every dense layer of the stage is ONE launch (csrc/wsmg_rows_gemm.hip): bias, the concatenation, the ReLU and its mask, the
+    split of d(cat) into its three parts and the accumulate-intos (beta = 1, in place) ride in the epilogues / operand segments —
+    7 launches per chunk forward and backward instead of 9 + 4 pre-fills / 9 + a threshold_backward, each ~4 us."""
+    chainable = True
+    saves = ("map_emb",)
+
+    def alloc_bwd(self):
+        self.b.dmap_all = torch.empty_like(self.b.dtext)
+
+    def fwd(self, k, wait, signal):
+        b, M, r0 = self.b, self.rows, k * self.rows
+        _rg([b.y1r], b.wq1, False, [b.q1], r0, M, bias=b.bq1, wait=wait, fail_bit=self.fail_bit)
+        self.text_fwd(r0)
+        _rg([b.text_emb], b.wq2, False, [b.q2], r0, M, bias=b.bq2)
+        _rg([b.q2], b.wk2, True, [b.qf], r0, M)
+        self.map_fwd(r0)
+        _rg([b.y1r, b.text_emb, b.map_emb], b.wc, False, [b.xc], r0, M, bias=b.bc, relu=True)
+        _rg([b.xc], b.w_ih2, False, [b.gi2], r0, M, bias=b.b_ih2, signal=signal)
+
+    def bwd(self, k, wait, signal):
+        b, M, r0 = self.b, self.rows, k * self.rows
+        _rg([b.dgi2r], b.w_ih2, True, [b.dxc], r0, M, mask=b.xc, wait=wait, fail_bit=self.fail_bit)
+        _rg([b.dxc], b.wc, True, [b.dstate_r, b.dtext, b.dmap_all], r0, M)
+        self.map_bwd(r0, _prow(b.dmap_all, r0))
+        _rg([b.dqf], b.wk2, False, [b.dq2], r0, M)
+        _rg([b.dq2], b.wq2, True, [b.dtext], r0, M, cin_segs=[b.dtext])
+        self.text_bwd(r0)
+        _rg([b.dq1], b.wq1, True, [b.dstate_r], r0, M, cin_segs=[b.dstate_r], signal=signal)
+
+    def concat(self):      # cat(state, text_embedding, map_embedding) for dW of second_state_compress: only ever operand segments here
+        return torch.cat([self.b.y1r, self.b.text_emb, self.b.map_emb], dim=1)
+
+
+class _LibStage(_Stage):
+    """The dense layers on the GEMM library.  Projection outputs start as their bias rows and are accumulated into: `addmm` with a 1-D
+    bias takes hipBLASLt's bias-epilogue route, whose heuristic picks ONE 256 x 128 macro-tile for a 128-row chunk — 64 us for a
+    33-MFLOP product."""
+    saves = ("x",)
+
+    def alloc_fwd(self):
+        self.b.x = torch.empty(self.b.y1r.shape[0], self.b.wc.shape[1], device=self.b.xc.device, dtype=torch.float32)
+
+    def begin_fwd(self):
+        for out, bias in ((self.b.q1, self.b.bq1), (self.b.q2, self.b.bq2), (self.b.xc, self.b.bc), (self.b.gi2, self.b.b_ih2)):
+            out.copy_(bias.expand_as(out))
+
+    def alloc_bwd(self):
+        self.wc_parts, self.wk2t = self.b.wc.split((self.b.y1r.shape[1], self.C, self.C), dim=1), self.b.wk2.t()
+
+    def fwd(self, k, wait, signal):
+        b, r0, r1 = self.b, k * self.rows, (k + 1) * self.rows
+        b.q1[r0:r1].addmm_(b.y1r[r0:r1], b.wq1.t())
+        self.text_fwd(r0)
+        b.q2[r0:r1].addmm_(b.text_emb[r0:r1], b.wq2.t())
+        torch.mm(b.q2[r0:r1], b.wk2, out=b.qf[r0:r1])
+        self.map_fwd(r0)
+        torch.cat([b.y1r[r0:r1], b.text_emb[r0:r1], b.map_emb[r0:r1]], dim=1, out=b.x[r0:r1])
+        b.xc[r0:r1].addmm_(b.x[r0:r1], b.wc.t())
+        torch.relu_(b.xc[r0:r1])
+        b.gi2[r0:r1].addmm_(b.xc[r0:r1], b.w_ih2.t())
+
+    def bwd(self, k, wait, signal):
+        b, r0, r1 = self.b, k * self.rows, (k + 1) * self.rows
+        # ReLU of second_state_compress: d(pre-activation) = d(xc) where xc > 0
+        dxc_k, dq2_k = b.dxc[r0:r1], b.dq2[r0:r1]
+        torch.ops.aten.threshold_backward.grad_input(torch.mm(b.dgi2r[r0:r1], b.w_ih2), b.xc[r0:r1], 0.0, grad_input=dxc_k)
+        dstate_a, dtext_a, dmap = [torch.mm(dxc_k, w) for w in self.wc_parts]
+        self.map_bwd(r0, _p(dmap))
+        torch.mm(b.dqf[r0:r1], self.wk2t, out=dq2_k)
+        torch.addmm(dtext_a, dq2_k, b.wq2, out=b.dtext[r0:r1])
+        self.text_bwd(r0)
+        torch.addmm(dstate_a, b.dq1[r0:r1], b.wq1, out=b.dstate_r[r0:r1])
+
+    def concat(self):
+        return self.b.x
+
+
+def _pipeline(names, main, streams, order, chain, dev, producer, stage, consumer, begin=None):
+    """Enqueues "producer recurrence -> stage chunks -> consumer recurrence" over the chunks `order` (ascending in forward, descending
+    in backward) on streams = (producer's, stage's, consumer's); names: their `_ops.mark` names.  producer / consumer (k, link=None)
+    launch chunk k or, with a chain link, the whole sequence; stage (k, wait, signal); begin: runs on the stage's stream in front of
+    its chunks.  Chunk k of each waits for chunk k of the one before it: through one event per chunk and edge, or, with chain =
+    (arrivals per chunk of a recurrence launch, of the stage's last product), on the device — each recurrence is ONE whole-sequence
+    launch that waits on _ChainCounters: no chunk prologues (W_hh into registers: ~10 us, 16 times per update), no launch gaps, no
+    events; a waiter is enqueued after its producers.  With the stage on `main` (K = 1) there is one stream and nothing to order.
+    The side streams fork from `main` once, behind what is queued on it so far (the buffers' earlier users, the counters' zeroing);
+    joining them is the caller's.  Enqueue order: stream by stream — the dependencies are events or counters, so the GPU sees the
+    same pipeline as with a chunk-by-chunk order, and the host changes its current stream twice instead of eight times (it has
+    < 1.5 ms of lead over the GPU in this part of an update).  -> the counter tensor (the caller keeps it alive) or None."""
+    multi = streams[1] is not main
+    cnt = _ChainCounters(len(order), dev, *chain) if chain else None
+    if multi:
+        # ONE event record on `main` (stream.wait_stream(main) records one per call, and a record between two dependent kernels costs
+        # the recording stream ~3 us: tools/exp/event_cost.hip)
+        e = torch.cuda.Event()
+        e.record(main)
+        for st in streams:
+            if st is not main:
+                st.wait_event(e)
+    evented = multi and cnt is None
+
+    def run(st, name, launch, waits=None, record=False, link=None, first=None):
+        done = {}
+        with (contextlib.nullcontext() if st is main else torch.cuda.stream(st)):
+            if first:
+                first()
+            if link:
+                launch(0, link)
+                _ops.mark(name)
+                return done
+            for k in order:
+                if waits:
+                    st.wait_event(waits[k])
+                launch(k)
+                _ops.mark("%s.%d" % (name, k))
+                if record:
+                    done[k] = torch.cuda.Event()
+                    done[k].record(st)
+        return done
+
+    ev = run(streams[0], names[0], producer, record=evented, link=cnt and cnt.head)
+    chunk = (lambda k: stage(k, cnt.wait(k), cnt.signal(k))) if cnt else (lambda k: stage(k, None, None))
+    ev = run(streams[1], names[1], chunk, ev, evented, first=begin)
+    run(streams[2], names[2], consumer, ev, link=cnt and cnt.tail)
+    return cnt and cnt.words
+
+
+_SAVED = ("state_in", "tokens", "text_k", "text_v", "inverse", "m", "h01", "h02", "w_ih1", "w_hh1", "wq1", "wq2", "wk2", "wc", "w_ih2", "w_hh2",
+          "gi1", "y1", "sv1", "y2", "sv2", "q1", "text_emb", "attn_text", "q2", "qf", "att_map", "xc")
+
+
+def _save(ctx, b, names):
+    """save_for_backward of the named buffers of `b`, a list (sv1, sv2) item by item -> the layout `_load` names them by again."""
+    vals = [getattr(b, n) for n in names]
+    ctx.save_for_backward(*[t for v in vals for t in (v if isinstance(v, list) else [v])])
+    return [(n, len(v) if isinstance(v, list) else None) for n, v in zip(names, vals)]
+
+
+def _load(ctx, layout):
+    it = iter(ctx.saved_tensors)
+    return SimpleNamespace(**{n: next(it) if c is None else [next(it) for _ in range(c)] for n, c in layout})
+
+
 class _RecurrentBlock(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cfg, state_in, tokens, text_k, text_v, text_mask, inverse, masks, h01, h02,
                 w_ih1, b_ih1, w_hh1, b_hh1, wq1, bq1, wq2, bq2, wk, bk, wc, bc, w_ih2, b_ih2, w_hh2, b_hh2):
-        N, K, scale, sink, text_ev = cfg["N"], cfg["chunks"], cfg["scale"], cfg["sink"], cfg["text_ready"]
-        ctx.streams = cfg["streams"]
-        B = state_in.shape[0]
+        N, scale, text_ev, cell = cfg["N"], cfg["scale"], cfg["text_ready"], cfg["cell"]   # cell: ops.GRU or ops.LSTM (ops/rnn.py)
+        B, H, G, dev = state_in.shape[0], w_hh1.shape[1], cell.G, state_in.device
         T = B // N
-        H = w_hh1.shape[1]
-        cell = cfg["cell"]                    # ops.GRU or ops.LSTM: what the two recurrences' launches look like (ops/rnn.py)
-        G = cell.G
         assert w_hh1.shape[0] == G * H and w_hh2.shape[0] == G * H
-        dev = state_in.device
-        K, Tc = chunk_plan(T, K)
-        rows = Tc * N
+        K, Tc = chunk_plan(T, cfg["chunks"])
         main = torch.cuda.current_stream()
-        sa, sg, _ = _roles(ctx.streams if K > 1 else None, main)
-        if sa is main:
-            K, Tc, rows = 1, T, B
-        f32 = dict(device=dev, dtype=torch.float32)
-        wk2 = wk.reshape(wk.shape[0], -1)
-        I, C = tokens.shape[1], tokens.shape[2]
-        L = text_k.shape[1]
-        lib = _abi.lib()
-        # full-batch buffers (main stream's pool; every other stream is joined into main before this function returns, and they
-        # live on as saved tensors until the backward pass)
-        gi1 = torch.addmm(b_ih1, state_in, w_ih1.t())
-        y1 = torch.empty(T, N, H, **f32)
-        y2 = torch.empty(T, N, H, **f32)
-        sv1, sv2 = cell.new_saves(T, N, H, dev), cell.new_saves(T, N, H, dev)      # saved for the backward
-        # the kernels' outputs of the final rows below h (an LSTM's c_T: the final c is save_c[T - 1] as well), one per recurrence
-        tails = [torch.empty(cell.state_rows - 1, N, H, **f32) for _ in range(2)]
-        # (projection outputs start as their bias rows and are accumulated into: `addmm` with a 1-D bias takes hipBLASLt's bias-epilogue
-        #  route, whose heuristic picks ONE 256 x 128 macro-tile for a 128-row chunk — 64 us for a 33-MFLOP product)
-        q1 = torch.empty(B, wq1.shape[0], **f32)
-        text_emb = torch.empty(B, C, **f32)
-        attn_text = torch.empty(B, L, **f32)
-        q2 = torch.empty(B, wq2.shape[0], **f32)
-        qf = torch.empty(B, C, **f32)
-        map_emb = torch.empty(B, C, **f32)
-        att_map = torch.empty(B, I, **f32)
-        x = None            # (the concatenation is an operand of the rows-GEMM route: the leaf pass rebuilds it for dW)
-        rg = rows_gemm_ok(H, C, wc.shape[0], G) and wq1.shape[0] % 256 == 0 and wq2.shape[0] % 256 == 0
-        if not rg:
-            x = torch.empty(B, wc.shape[1], **f32)
-        xc = torch.empty(B, wc.shape[0], **f32)
-        gi2 = torch.empty(B, G * H, **f32)
-        m = masks.reshape(T, N)
-        h01 = h01.clone()          # the caller overwrites rnn_hidden_states in place (reference contract); an LSTM's is [h; c]
-        h02 = h02.clone()
-        tsfx = _sfx(text_k)
-        ksfx = _sfx(tokens)
-        nbytes = cell.workspace_bytes(Tc)
-        # (wsmgmap.parallel holds its buckets until this block's backward has queued its kernels: see _launch_ready there)
-        _core.chain_in_flight = bool(sa is not main and any(ctx.needs_input_grad))
-        forked = False
-        if sa is not main:
-            # the buffers above come from the main stream's pool: whatever used their memory before is queued on main
-            # (forked below, once: the chained route after it has zeroed its counters on main)
-            if text_ev is not None:
-                sa.wait_event(text_ev)
-        elif text_ev is not None:
-            main.wait_event(text_ev)
-
-        # chunk launches run on workspaces this module owns (no clear in front of every launch); a HIP-graph capture bakes the
-        # launch-unique tags in, so replays need the clearing form
-        owned = not torch.cuda.is_current_stream_capturing()
-        own_chunks = owned and cell.fwd[1] is not None      # (no owned LSTM form: its chunk launches clear a fresh workspace)
-
-        def rnn(gi, w_hh, b_hh, h0, y, sv, ci, role, t0=0, steps=T, link=None):
-            # one launch of a recurrence: chunk k of it (t0 = k Tc: it starts from what step t0 - 1 left), or, with
-            # link = (in_cnt, in_target, out_cnt), the whole sequence chained chunk by chunk to the attention stage
-            if link or own_chunks:
-                ws = _owned_ws(dev, role, cell.workspace_bytes(steps) if link else nbytes)
-            else:
-                ws = _rnn_workspace(nbytes, dev)
-            cell.launch_fwd(gi, w_hh, b_hh, cell.rows(h0), m, y, tails[ci], sv, t0, steps, ws, own_chunks, link and (Tc, *link))
-
-        gi1v, gi2v = gi1.view(T, N, G * H), gi2.view(T, N, G * H)
-        y1r = y1.view(B, H)
+        sa, sg, _ = _roles(cfg["streams"] if K > 1 else None, main)
         multi = sa is not main
-        fail_bit = cell.fwd_bit           # a chained product's wait names the recurrence it waits for (status bits of wsmg_rnn.hip)
-        # round 5 — chained: each recurrence is ONE whole-sequence launch; the attention stage's first product of chunk k waits (on the
-        # device) for the first recurrence's arrivals on counter k, its last product signals counter K + k, which the second
-        # recurrence waits for at the first step of chunk k (csrc/wsmg_rnn.hip chain_wait).  No chunk prologues (W_hh into registers:
-        # ~10 us, 16 times per update), no launch gaps, no events; a waiter is enqueued after its producers.
-        chain = multi and rg and owned and _sw.recurrent_chain and K > 1
-        cnt = None
-        if chain:
-            cnt = torch.zeros(3 * K, device=dev, dtype=torch.int32)     # [arrivals in | arrivals out | gate words] per chunk
-            nwg = cell.chain_workgroups()
-            _fork(main, sa, sg)          # (the counters are zeroed on main)
-            forked = True
-            rnn(gi1v, w_hh1, b_hh1, h01, y1, sv1, 0, "f1", link=(None, 0, _p(cnt)))
-            _ops.mark("f.g1")
-        if multi and not forked:
-            _fork(main, sa, sg)
-        # Enqueue order: stream by stream (all of GRU 1's chunks, then all attention chunks, then all of GRU 2's) — the dependencies are
-        # events, so the GPU sees the same pipeline as with a chunk-by-chunk order, and the host changes its current stream twice
-        # instead of eight times (the host has < 1.5 ms of lead over the GPU in this part of an update)
-        ev1, eva = [], []
-        for k in range(0 if chain else K):
-            rnn(gi1v, w_hh1, b_hh1, h01, y1, sv1, 0, "f1", k * Tc, Tc)                 # main
-            _ops.mark("f.g1.%d" % k)
-            if multi:
-                e1 = torch.cuda.Event()
-                e1.record(main)
-                ev1.append(e1)
-        with torch.cuda.stream(sa):
-            if not rg:
-                q1.copy_(bq1.expand_as(q1))
-                q2.copy_(bq2.expand_as(q2))
-                xc.copy_(bc.expand_as(xc))
-                gi2.copy_(b_ih2.expand_as(gi2))
-            for k in range(K):
-                r0, r1 = k * rows, (k + 1) * rows
-                if multi and not chain:
-                    sa.wait_event(ev1[k])
-                if rg:
-                    # round 5: every dense layer of the stage is ONE launch (csrc/wsmg_rows_gemm.hip): bias, the concatenation, the
-                    # ReLU in the epilogue / operand segments — 7 launches per chunk instead of 9 + 4 pre-fills, each ~4 us
-                    _rg([y1r], wq1, False, [q1], r0, rows, bias=bq1, wait=(cnt.data_ptr() + 4 * k, nwg, cnt.data_ptr() + 4 * (2 * K + k)) if chain else None, fail_bit=fail_bit)
-                else:
-                    q1[r0:r1].addmm_(y1r[r0:r1], wq1.t())
-                _abi.call("wsmg_attn_shared_fwd" + tsfx, _prow(q1, r0), _p(text_k), _p(text_v), _p(text_mask), _prow(inverse, r0),
-                          scale, rows, L, C, _prow(text_emb, r0), _prow(attn_text, r0), _stream())
-                if rg:
-                    _rg([text_emb], wq2, False, [q2], r0, rows, bias=bq2)
-                    _rg([q2], wk2, True, [qf], r0, rows)
-                else:
-                    q2[r0:r1].addmm_(text_emb[r0:r1], wq2.t())
-                    torch.mm(q2[r0:r1], wk2, out=qf[r0:r1])
-                _abi.call("wsmg_attn_fwd" + ksfx, _prow(qf, r0), _prow(tokens, r0), _prow(tokens, r0), None, scale, rows, I, C,
-                          _prow(map_emb, r0), _prow(att_map, r0), _stream())
-                if rg:
-                    _rg([y1r, text_emb, map_emb], wc, False, [xc], r0, rows, bias=bc, relu=True)
-                    _rg([xc], w_ih2, False, [gi2], r0, rows, bias=b_ih2, signal=cnt.data_ptr() + 4 * (K + k) if chain else None)
-                else:
-                    torch.cat([y1r[r0:r1], text_emb[r0:r1], map_emb[r0:r1]], dim=1, out=x[r0:r1])
-                    xc[r0:r1].addmm_(x[r0:r1], wc.t())
-                    torch.relu_(xc[r0:r1])
-                    gi2[r0:r1].addmm_(xc[r0:r1], w_ih2.t())
-                _ops.mark("f.at.%d" % k)
-                if multi and not chain:
-                    ea = torch.cuda.Event()
-                    ea.record(sa)
-                    eva.append(ea)
-        with torch.cuda.stream(sg):
-            if chain:
-                rnn(gi2v, w_hh2, b_hh2, h02, y2, sv2, 1, "f2", link=(ctypes.c_void_p(cnt.data_ptr() + 4 * K),
-                                                                     int(lib.wsmg_rows_gemm_workgroups(rows, G * H)), None))
-                _ops.mark("f.g2")
-            for k in range(0 if chain else K):
-                if multi:
-                    sg.wait_event(eva[k])
-                rnn(gi2v, w_hh2, b_hh2, h02, y2, sv2, 1, "f2", k * Tc, Tc)
-                _ops.mark("f.g2.%d" % k)
-        if sg is not main:
+        K, Tc = (K, Tc) if multi else (1, T)
+        rows = Tc * N
+        I, C, L = tokens.shape[1], tokens.shape[2], text_k.shape[1]
+        E = functools.partial(torch.empty, device=dev, dtype=torch.float32)
+        # full-batch buffers (main stream's pool; every other stream is joined into main before this function returns, and they
+        # live on as saved tensors until the backward pass).  h01 / h02 are copies: the caller overwrites rnn_hidden_states in place
+        # (reference contract); an LSTM's is [h; c]
+        b = SimpleNamespace(
+            state_in=state_in, tokens=tokens, text_k=text_k, text_v=text_v, text_mask=text_mask, inverse=inverse, m=masks.reshape(T, N),
+            scale=scale, w_ih1=w_ih1, w_hh1=w_hh1, wq1=wq1, bq1=bq1, wq2=wq2, bq2=bq2, wk2=wk.reshape(wk.shape[0], -1), wc=wc, bc=bc,
+            w_ih2=w_ih2, b_ih2=b_ih2, w_hh2=w_hh2, gi1=torch.addmm(b_ih1, state_in, w_ih1.t()), y1=E(T, N, H), y2=E(T, N, H),
+            sv1=cell.new_saves(T, N, H, dev), sv2=cell.new_saves(T, N, H, dev), q1=E(B, wq1.shape[0]), text_emb=E(B, C),
+            attn_text=E(B, L), q2=E(B, wq2.shape[0]), qf=E(B, C), map_emb=E(B, C), att_map=E(B, I), xc=E(B, wc.shape[0]), gi2=E(B, G * H),
+            h01=h01.clone(), h02=h02.clone())
+        b.y1r = b.y1.view(B, H)
+        # the kernels' outputs of the final rows below h (an LSTM's c_T: the final c is save_c[T - 1] as well), one per recurrence
+        tails = [E(cell.state_rows - 1, N, H) for _ in range(2)]
+        form = _RowsStage if rows_gemm_ok(H, C, wc.shape[0], G) and wq1.shape[0] % 256 == 0 and wq2.shape[0] % 256 == 0 else _LibStage
+        stage = form(b, rows, cell.fwd_bit)
+        stage.alloc_fwd()
+        # (wsmgmap.parallel holds its buckets until this block's backward has queued its kernels: see _launch_ready there)
+        _core.chain_in_flight = bool(multi and any(ctx.needs_input_grad))
+        if text_ev is not None:
+            sa.wait_event(text_ev)
+        owned, own_chunks, ws = _workspaces(cell, cell.fwd, dev, T, Tc)
+
+        def rnn(gi, w_hh, b_hh, h0, y, sv, tail, role, k, link=None):
+            # chunk k of a recurrence (it starts from what step k Tc - 1 left), or, with a chain link, the whole sequence
+            cell.launch_fwd(gi, w_hh, b_hh, cell.rows(h0), b.m, y, tail, sv, k * Tc, T if link else Tc, ws(role, link),
+                            own_chunks, link and (Tc, *link))
+
+        chain = multi and stage.chainable and owned and _sw.recurrent_chain and K > 1
+        _pipeline(("f.g1", "f.at", "f.g2"), main, (main, sa, sg), range(K),
+                  chain and (cell.chain_workgroups(), _abi.lib().wsmg_rows_gemm_workgroups(rows, G * H)), dev,
+                  functools.partial(rnn, b.gi1.view(T, N, G * H), w_hh1, b_hh1, b.h01, b.y1, b.sv1, tails[0], "f1"), stage.fwd,
+                  functools.partial(rnn, b.gi2.view(T, N, G * H), w_hh2, b_hh2, b.h02, b.y2, b.sv2, tails[1], "f2"), stage.begin_fwd)
+        if multi:
             main.wait_stream(sg)
             main.wait_stream(sa)
-        ctx.save_for_backward(state_in, tokens, text_k, text_v, inverse, m, h01, h02, w_ih1, w_hh1, wq1, wq2, wk2, wc, w_ih2, w_hh2,
-                              gi1, y1, *sv1, y2, *sv2, q1, text_emb, attn_text, q2, qf, att_map, map_emb if x is None else x, xc)
-        ctx.x_is_parts = x is None
-        ctx.chain = chain
-        ctx.cell = cell
-        ctx.cfg = (N, K, Tc, scale, sink, tuple(wk.shape), text_mask is not None)
+        ctx.form, ctx.chain, ctx.cell, ctx.layout = form, chain, cell, _save(ctx, b, _SAVED + form.saves)
+        ctx.cfg, ctx.streams = (N, K, Tc, scale, cfg["sink"], tuple(wk.shape)), cfg["streams"]
         ctx.params = (w_ih1, b_ih1, w_hh1, b_hh1, wq1, bq1, wq2, bq2, wk, bk, wc, bc, w_ih2, b_ih2, w_hh2, b_hh2)
-        h1n, h2n = cell.final_state(y1, sv1), cell.final_state(y2, sv2)      # habitat's layout: [h] or [h; c]
+        h1n, h2n = cell.final_state(b.y1, b.sv1), cell.final_state(b.y2, b.sv2)      # habitat's layout: [h] or [h; c]
         ctx.mark_non_differentiable(h1n, h2n)
         ctx.set_materialize_grads(False)
-        return y2.view(B, H), att_map, h1n, h2n
+        return b.y2.view(B, H), b.att_map, h1n, h2n
 
     @staticmethod
     def backward(ctx, dy2, datt, _dh1, _dh2):
-        cell = ctx.cell
-        ns = len(cell.save_widths)   # saved tensors per recurrence (see forward)
-        saved = ctx.saved_tensors
-        (state_in, tokens, text_k, text_v, inverse, m, h01, h02, w_ih1, w_hh1, wq1, wq2, wk2, wc, w_ih2, w_hh2, gi1, y1) = saved[:18]
-        sv1, y2, sv2 = saved[18:18 + ns], saved[18 + ns], saved[19 + ns:19 + 2 * ns]
-        q1, text_emb, attn_text, q2, qf, att_map, x, xc = saved[19 + 2 * ns:]
-        rg = ctx.x_is_parts          # the rows-GEMM route: `x` is map_emb, the concatenation is rebuilt on the leaf stream
-        N, K, Tc, scale, sink, wk_shape, _ = ctx.cfg
-        T = y1.shape[0]
-        H = y1.shape[2]
-        G = cell.G
-        B = T * N
-        rows = Tc * N
-        dev = y1.device
-        I, C = tokens.shape[1], tokens.shape[2]
-        L = text_k.shape[1]
-        U = text_k.shape[0]
-        f32 = dict(device=dev, dtype=torch.float32)
+        cell, params, b = ctx.cell, ctx.params, _load(ctx, ctx.layout)
+        N, K, Tc, b.scale, sink, wk_shape = ctx.cfg
+        T, _, H = b.y1.shape
+        G, B, dev, U = cell.G, T * N, b.y1.device, b.text_k.shape[0]
         main = torch.cuda.current_stream()
-        params = ctx.params
-        # Side streams only when this pass SETS the gradients of leaf parameters that nothing but this block uses: the parameter
-        # gradients are produced on the leaf stream, so they must not pass through autograd's AccumulateGrad — it runs on the main
-        # stream right after this function returns and, whenever it does not simply keep the tensor (an existing .grad to add to; a
-        # tensor it decides to copy), launches a kernel there that reads a gradient the leaf stream has not written yet (seen as
-        # one wrong weight gradient in 8 runs of two ranks sharing a GPU).  In that mode this function ASSIGNS p.grad itself, runs
-        # the parameters' post-accumulate hooks (wsmgmap.parallel.GradAllReducer's bucket hooks) and returns None for them.
-        # A stock DistributedDataParallel wrap hooks the AccumulateGrad nodes instead: there the block stays on one stream.
+        # Side streams only when this pass SETS the gradients of leaf parameters that nothing but this block uses: the parameter gradients are
+        # produced on the leaf stream, so they must not pass through autograd's AccumulateGrad — it runs on the main stream right after this function
+        # returns and, whenever it does not simply keep the tensor (an existing .grad to add to; a tensor it decides to copy), launches a kernel there
+        # that reads a gradient the leaf stream has not written yet (seen as one wrong weight gradient in 8 runs of two ranks sharing a GPU)..  In that
+        # mode this function ASSIGNS p.grad itself, runs the parameters' post-accumulate hooks (wsmgmap.parallel.GradAllReducer's bucket hooks) and
+        # returns None for them. A stock DistributedDataParallel wrap hooks the AccumulateGrad nodes instead: there the block stays on one stream.
         own = [p for p in params if p is not None and p.requires_grad]
         # (a parameter with a tensor hook — `register_hook`, which AccumulateGrad's input would have run — keeps the one-stream,
-        #  through-autograd form: assigning .grad here would silently skip it; ADVICE r04.  These parameters have no consumer
-        #  outside this block — `is_leaf and grad is None` at entry is the whole contract: nothing else can add to them in this pass)
-        multi = (ctx.cfg[1] > 1 and _post_hooks_visible()
+        #  through-autograd form: assigning .grad here would silently skip it.  These parameters have no consumer outside this
+        #  block — `is_leaf and grad is None` at entry is the whole contract: nothing else can add to them in this pass)
+        multi = (K > 1 and _post_hooks_visible()
                  and all(p.is_leaf and p.grad is None and not getattr(p, "_backward_hooks", None) for p in own))
         if multi and torch.distributed.is_available() and torch.distributed.is_initialized():
             multi = all(getattr(p, "_wsmg_reducer", False) for p in own)
@@ -383,134 +470,53 @@ class _RecurrentBlock(torch.autograd.Function):
                 multi = False
         if not multi:
             sa = sg = sl = main
-            K, Tc, rows = 1, T, B
-        dy2 = torch.zeros(T, N, H, **f32) if dy2 is None else dy2.contiguous().float().view(T, N, H)
-        datt = None if datt is None else datt.contiguous().float()
-        lib = _abi.lib()
-        nbytes = cell.workspace_bytes(Tc)
-        tsfx, ksfx = _sfx(text_k), _sfx(tokens)
-        # full-batch gradient buffers, allocated on the main stream and used on the others: the allocator must not hand their memory
-        # to a later main-stream allocation while a side stream still works on them
-        # (an LSTM's one gate gradient is both the gradient of gi and of W_hh h + b_hh: dgh is dgi; its state gradients are [dh; dc])
-        dgi2, dgi1 = torch.empty(T, N, G * H, **f32), torch.empty(T, N, G * H, **f32)
-        dgh2, dgh1 = (torch.empty_like(dgi2), torch.empty_like(dgi1)) if cell.own_dgh else (dgi2, dgi1)
-        dxc = torch.empty(B, wc.shape[0], **f32)
-        dqf, dq2, dq1 = torch.empty(B, C, **f32), torch.empty(B, wq2.shape[0], **f32), torch.empty(B, wq1.shape[0], **f32)
-        dtext = torch.empty(B, C, **f32)
-        dmap_all = torch.empty(B, C, **f32) if rg else None
-        dl = torch.empty(B, L, **f32)
-        dstate = torch.empty(T, N, H, **f32)
-        dtokens = torch.empty_like(tokens)
-        dh01, dh02 = torch.empty(h01.shape, **f32), torch.empty(h02.shape, **f32)
-        carry2 = [torch.empty(h02.shape, **f32) for _ in range(2)]
-        carry1 = [torch.empty(h01.shape, **f32) for _ in range(2)]
+            K, Tc = 1, T
+        rows = Tc * N
+        E = functools.partial(torch.empty, device=dev, dtype=torch.float32)
+        # full-batch gradient buffers (an LSTM's one gate gradient is both the gradient of gi and of W_hh h + b_hh: dgh is dgi; its state gradients are [dh; dc])
+        b.dy2 = torch.zeros(T, N, H, device=dev, dtype=torch.float32) if dy2 is None else dy2.contiguous().float().view(T, N, H)
+        b.datt = None if datt is None else datt.contiguous().float()
+        b.dgi2, b.dgi1 = E(T, N, G * H), E(T, N, G * H)
+        b.dgh2, b.dgh1 = (torch.empty_like(b.dgi2), torch.empty_like(b.dgi1)) if cell.own_dgh else (b.dgi2, b.dgi1)
+        b.dxc, b.dqf, b.dq2, b.dq1 = E(B, b.wc.shape[0]), E(B, b.qf.shape[1]), E(B, b.wq2.shape[0]), E(B, b.wq1.shape[0])
+        b.dtext, b.dl, b.dstate, b.dtokens = E(B, b.qf.shape[1]), E(B, b.text_k.shape[1]), E(T, N, H), torch.empty_like(b.tokens)
+        b.dh01, b.dh02 = E(*b.h01.shape), E(*b.h02.shape)
+        b.carry2, b.carry1 = [E(*b.h02.shape) for _ in range(2)], [E(*b.h01.shape) for _ in range(2)]
+        b.y1r, b.dstate_r, b.dgi2r = b.y1.view(B, H), b.dstate.view(B, H), b.dgi2.view(B, G * H)
+        stage = ctx.form(b, rows, cell.bwd_bit)
+        stage.alloc_bwd()
         if multi:
-            # these are allocated from the main stream's pool and used on the others: they must not be handed to a later main-stream
-            # allocation while a side stream still works on them — a reference is held until the pass's final callbacks, which run
-            # after the leaf stream has been joined into main (cheaper than ~50 record_stream calls, and legal under graph capture)
-            # — and so do the tensors SAVED by the forward pass: autograd drops them the moment this function returns, long before
-            # the leaf stream's GEMMs have read x, xc, q2, text_emb, y1, y2, ... (seen as one wrong weight gradient in ~8 runs of two
-            # ranks sharing a GPU, where the leaf stream starts late)
-            keep = [dgi2, dgh2, dgi1, dgh1, dxc, dqf, dq2, dq1, dtext, dmap_all, dl, dstate, dtokens, dh02, dy2, datt, carry2, carry1,
-                    list(ctx.saved_tensors)]
+            # the buffers are allocated from the main stream's pool and used on the others: they must not be handed to a later main-stream allocation
+            # while a side stream still works on them — a reference is held until the pass's final callbacks, which run after the leaf stream has been
+            # joined into main (cheaper than ~50 record_stream calls, and legal under graph capture) — and so do the tensors SAVED by the forward
+            # pass: autograd drops them the moment this function returns, long before the leaf stream's GEMMs have read x, xc, q2, text_emb, y1, y2,
+            # ... (seen as one wrong weight gradient in ~8 runs of two ranks sharing a GPU, where the leaf stream starts late)..  `b` names them all
+            # (and the chain's counters, below)
+            keep = [b]
             torch.autograd.Variable._execution_engine.queue_callback(keep.clear)
-        xcr = xc
-        y1r = y1.view(B, H)
-        dstate_r = dstate.view(B, H)
-        dgi2r = dgi2.view(B, G * H)
+        owned, own_chunks, ws = _workspaces(cell, cell.bwd, dev, T, Tc)
 
-        owned = not torch.cuda.is_current_stream_capturing()
-        own_chunks = owned and cell.bwd[1] is not None
-
-        def rnn_bwd(dy, w_hh, h0, y, sv, dgi, dgh, dh0_out, carry, role, k=0, steps=T, link=None):
+        def rnn_bwd(dy, w_hh, h0, y, sv, dgi, dgh, dh0_out, carry, role, k, link=None):
             # as `rnn` in forward; chunk k takes the gradient of its final state from chunk k + 1 and leaves that of its first
-            # state to chunk k - 1 (two buffers in turn); the whole-sequence launch (k = 0, steps = T) has neither
+            # state to chunk k - 1 (two buffers in turn); the whole-sequence launch (k = 0) has neither
             last = link or k == K - 1
-            if link or own_chunks:
-                ws = _owned_ws(dev, role, cell.workspace_bytes(steps) if link else nbytes)
-            else:
-                ws = _rnn_workspace(nbytes, dev)
-            cell.launch_bwd(dy, None if last else cell.rows(carry[(k + 1) & 1]), w_hh, cell.rows(h0), m, y, sv, dgi, dgh,
-                            cell.rows(dh0_out if k == 0 else carry[k & 1]), k * Tc, steps, ws, own_chunks, link and (Tc, *link))
+            cell.launch_bwd(dy, None if last else cell.rows(carry[(k + 1) & 1]), w_hh, cell.rows(h0), b.m, y, sv, dgi, dgh,
+                            cell.rows(dh0_out if k == 0 else carry[k & 1]), k * Tc, T if link else Tc, ws(role, link), own_chunks,
+                            link and (Tc, *link))
 
-        # stream by stream, as in forward: GRU 2's chunks (last chunk first), the attention stage's, GRU 1's
-        ev2, eva = {}, {}
-        chain = multi and rg and owned and ctx.chain and K > 1
-        cnt = None
-        fail_bit = cell.bwd_bit
-        if chain:     # (see forward: one launch per recurrence, device-side waits on per-chunk arrival counters)
-            cnt = torch.zeros(3 * K, device=dev, dtype=torch.int32)     # [arrivals in | arrivals out | gate words] per chunk
-            keep.append(cnt)
-            nwg = cell.chain_workgroups()
-        if multi:
-            _fork(main, sg, sa)      # once, behind everything the pass has queued on main so far (buffers, the chain's counters)
-        with torch.cuda.stream(sg):
-            if chain:
-                rnn_bwd(dy2, w_hh2, h02, y2, sv2, dgi2, dgh2, dh02, carry2, "b2", link=(None, 0, _p(cnt)))
-                _ops.mark("b.g2")
-            for k in range(K - 1 if not chain else -1, -1, -1):
-                rnn_bwd(dy2, w_hh2, h02, y2, sv2, dgi2, dgh2, dh02, carry2, "b2", k, Tc)
-                _ops.mark("b.g2.%d" % k)
-                if multi:
-                    ev2[k] = torch.cuda.Event()
-                    ev2[k].record(sg)
-        with torch.cuda.stream(sa):
-            wc_s, wc_t, wc_m = wc[:, :H], wc[:, H:H + C], wc[:, H + C:]
-            wk2t = wk2.t()
-            for k in range(K - 1, -1, -1):
-                r0, r1 = k * rows, (k + 1) * rows
-                if multi and not chain:
-                    sa.wait_event(ev2[k])
-                if rg:
-                    # round 5: five launches of wsmg_rows_gemm_f32 around the two attention kernels (was 9 GEMM-library launches + a
-                    # threshold_backward): the ReLU mask, the split of d(cat) into its three parts and the two accumulate-intos
-                    # (beta = 1, in place) ride in the epilogues
-                    _rg([dgi2r], w_ih2, True, [dxc], r0, rows, mask=xcr, wait=(cnt.data_ptr() + 4 * k, nwg, cnt.data_ptr() + 4 * (2 * K + k)) if chain else None, fail_bit=fail_bit)
-                    _rg([dxc], wc, True, [dstate_r, dtext, dmap_all], r0, rows)
-                    _abi.call("wsmg_attn_bwd" + ksfx, _prow(qf, r0), _prow(tokens, r0), _prow(tokens, r0), _prow(att_map, r0), _prow(dmap_all, r0),
-                              None if datt is None else _prow(datt, r0), scale, rows, I, C, _prow(dqf, r0), _prow(dtokens, r0),
-                              _prow(dtokens, r0), _stream())
-                    _rg([dqf], wk2, False, [dq2], r0, rows)
-                    _rg([dq2], wq2, True, [dtext], r0, rows, cin_segs=[dtext])
-                    _abi.call("wsmg_attn_shared_bwd" + tsfx, _prow(q1, r0), _p(text_k), _p(text_v), _prow(attn_text, r0), _prow(dtext, r0),
-                              None, _prow(inverse, r0), scale, rows, L, C, _prow(dq1, r0), _prow(dl, r0), _stream())
-                    _rg([dq1], wq1, True, [dstate_r], r0, rows, cin_segs=[dstate_r], signal=cnt.data_ptr() + 4 * (K + k) if chain else None)
-                else:
-                    # ReLU of second_state_compress: d(pre-activation) = d(xc) where xc > 0
-                    dxc_k = dxc[r0:r1]
-                    torch.ops.aten.threshold_backward.grad_input(torch.mm(dgi2r[r0:r1], w_ih2), xcr[r0:r1], 0.0, grad_input=dxc_k)
-                    dstate_a = torch.mm(dxc_k, wc_s)
-                    dtext_a = torch.mm(dxc_k, wc_t)
-                    dmap = torch.mm(dxc_k, wc_m)
-                    _abi.call("wsmg_attn_bwd" + ksfx, _prow(qf, r0), _prow(tokens, r0), _prow(tokens, r0), _prow(att_map, r0), _p(dmap),
-                              None if datt is None else _prow(datt, r0), scale, rows, I, C, _prow(dqf, r0), _prow(dtokens, r0),
-                              _prow(dtokens, r0), _stream())
-                    dq2_k = dq2[r0:r1]
-                    torch.mm(dqf[r0:r1], wk2t, out=dq2_k)
-                    torch.addmm(dtext_a, dq2_k, wq2, out=dtext[r0:r1])
-                    _abi.call("wsmg_attn_shared_bwd" + tsfx, _prow(q1, r0), _p(text_k), _p(text_v), _prow(attn_text, r0), _prow(dtext, r0),
-                              None, _prow(inverse, r0), scale, rows, L, C, _prow(dq1, r0), _prow(dl, r0), _stream())
-                    torch.addmm(dstate_a, dq1[r0:r1], wq1, out=dstate_r[r0:r1])
-                _ops.mark("b.at.%d" % k)
-                if multi and not chain:
-                    eva[k] = torch.cuda.Event()
-                    eva[k].record(sa)
-        if chain:
-            rnn_bwd(dstate, w_hh1, h01, y1, sv1, dgi1, dgh1, dh01, carry1, "b1", link=(ctypes.c_void_p(cnt.data_ptr() + 4 * K),
-                                                                                 int(lib.wsmg_rows_gemm_workgroups(rows, H)), None))
-            _ops.mark("b.g1")
-        for k in range(K - 1 if not chain else -1, -1, -1):
-            if multi:
-                main.wait_event(eva[k])
-            rnn_bwd(dstate, w_hh1, h01, y1, sv1, dgi1, dgh1, dh01, carry1, "b1", k, Tc)      # main
-            _ops.mark("b.g1.%d" % k)
-        d_state_in = torch.mm(dgi1.view(B, G * H), w_ih1) if ctx.needs_input_grad[1] else None
+        chain = multi and stage.chainable and owned and ctx.chain and K > 1
+        b.cnt = _pipeline(("b.g2", "b.at", "b.g1"), main, (sg, sa, main), range(K - 1, -1, -1),
+                          chain and (cell.chain_workgroups(), _abi.lib().wsmg_rows_gemm_workgroups(rows, H)), dev,
+                          functools.partial(rnn_bwd, b.dy2, b.w_hh2, b.h02, b.y2, b.sv2, b.dgi2, b.dgh2, b.dh02, b.carry2, "b2"), stage.bwd,
+                          functools.partial(rnn_bwd, b.dstate, b.w_hh1, b.h01, b.y1, b.sv1, b.dgi1, b.dgh1, b.dh01, b.carry1, "b1"))
+        g2, gh2, g1, gh1 = b.dgi2r, b.dgh2.view(B, G * H), b.dgi1.view(B, G * H), b.dgh1.view(B, G * H)
+        d_state_in = torch.mm(g1, b.w_ih1) if ctx.needs_input_grad[1] else None
         # gradients of the shared instruction sets (they feed the instruction branch's backward, on ITS stream): after the last
-        # attention chunk on the attention stream, joined into main below — by then GRU 1's last chunk has long hidden them
+        # attention chunk on the attention stream, joined into main below — by then recurrence 1's last chunk has long hidden them
         with torch.cuda.stream(sa):
-            member = torch.nn.functional.one_hot(inverse, U).to(torch.float32).t()            # [U, B]
-            dk = torch.matmul((member.unsqueeze(2) * dl.unsqueeze(0)).transpose(1, 2), q1).to(text_k.dtype)
-            dv = torch.matmul((member.unsqueeze(2) * attn_text.unsqueeze(0)).transpose(1, 2), dtext).to(text_v.dtype)
+            member = torch.nn.functional.one_hot(b.inverse, U).to(torch.float32).t()            # [U, B]
+            dk = torch.matmul((member.unsqueeze(2) * b.dl.unsqueeze(0)).transpose(1, 2), b.q1).to(b.text_k.dtype)
+            dv = torch.matmul((member.unsqueeze(2) * b.attn_text.unsqueeze(0)).transpose(1, 2), b.dtext).to(b.text_v.dtype)
         if multi:
             ekv = torch.cuda.Event()
             ekv.record(sa)
@@ -518,25 +524,19 @@ class _RecurrentBlock(torch.autograd.Function):
             sl.wait_stream(sg)
         # parameter gradients: full-batch GEMMs and column sums, off the chain
         with torch.cuda.stream(sl):
-            g2 = dgi2r
-            gh2 = dgh2.view(B, G * H)
-            g1 = dgi1.view(B, G * H)
-            gh1 = dgh1.view(B, G * H)
-            # the seven bias gradients (column sums) in one launch (round 6; torch: a reduction kernel + a memset each); an LSTM's
+            # the seven bias gradients (column sums) in one launch (torch: a reduction kernel + a memset each); an LSTM's
             # db_hh = db_ih = colsum(dgates), two tensors of their own
-            db_ih2, db_hh2, dbc, dbq2, dbq1, db_hh1, db_ih1 = _ops.colsum_multi([g2, gh2, dxc, dq2, dq1, gh1, g1])
-            dw_ih2 = g2.t() @ xc
-            dw_hh2 = cell.hidden_weight_grads(dgh2, h02, y2, m)      # dgh^T (mask * h_prev): an LSTM's h_prev is the h row of [h; c]
-            if rg:
-                x = torch.cat([y1r, text_emb, x], dim=1)          # (x held map_emb)
-            dwc = dxc.t() @ x
-            dwk = (q2.t() @ dqf).reshape(wk_shape)
+            db_ih2, db_hh2, dbc, dbq2, dbq1, db_hh1, db_ih1 = _ops.colsum_multi([g2, gh2, b.dxc, b.dq2, b.dq1, gh1, g1])
+            dw_ih2 = g2.t() @ b.xc
+            dw_hh2 = cell.hidden_weight_grads(b.dgh2, b.h02, b.y2, b.m)      # dgh^T (mask * h_prev): an LSTM's h_prev is the h row of [h; c]
+            dwc = b.dxc.t() @ stage.concat()
+            dwk = (b.q2.t() @ b.dqf).reshape(wk_shape)
             # (the key projection's bias adds the same number to every token's logit: it cancels in the softmax, gradient exactly 0)
-            dbk = torch.zeros(wk_shape[0], **f32) if params[9] is not None else None
-            dwq2 = dq2.t() @ text_emb
-            dwq1 = dq1.t() @ y1r
-            dw_hh1 = cell.hidden_weight_grads(dgh1, h01, y1, m)
-            dw_ih1 = g1.t() @ state_in
+            dbk = torch.zeros(wk_shape[0], device=dev, dtype=torch.float32) if params[9] is not None else None
+            dwq2 = b.dq2.t() @ b.text_emb
+            dwq1 = b.dq1.t() @ b.y1r
+            dw_hh1 = cell.hidden_weight_grads(b.dgh1, b.h01, b.y1, b.m)
+            dw_ih1 = g1.t() @ b.state_in
         pgrads = [dw_ih1, db_ih1, dw_hh1, db_hh1, dwq1, dbq1, dwq2, dbq2, dwk, dbk, dwc, dbc, dw_ih2, db_ih2, dw_hh2, db_hh2]
         _core.chain_in_flight = False      # every kernel of this block's backward is queued: the gradient exchange may issue buckets again
         if multi:
@@ -552,9 +552,8 @@ class _RecurrentBlock(torch.autograd.Function):
         # the map tokens' gradient: parked for the token mean's backward, which merges its broadcast row and the producing
         # convolution's ReLU mask into it in one pass (ops.TokenGradSink), or returned
         if sink is not None:
-            sink.park(dtokens)
-            dtokens = None
-        return (None, d_state_in, dtokens, dk, dv, None, None, None, dh01, dh02, *pgrads)
+            sink.park(b.dtokens)
+        return (None, d_state_in, b.dtokens if sink is None else None, dk, dv, None, None, None, b.dh01, b.dh02, *pgrads)
 
 
 def recurrent_block(state_in, tokens, text, masks, h01, h02, net, n_env, chunks=4, sink=None, text_ready=None, streams=None):
@@ -578,3 +577,4 @@ def recurrent_block(state_in, tokens, text, masks, h01, h02, net, n_env, chunks=
         net.state_text_q_layer.weight, net.state_text_q_layer.bias, net.text_map_q_layer.weight, net.text_map_q_layer.bias,
         net.text_map_k_layer.weight, net.text_map_k_layer.bias, net.second_state_compress[0].weight, net.second_state_compress[0].bias,
         r2.weight_ih_l0, r2.bias_ih_l0, r2.weight_hh_l0, r2.bias_hh_l0)
+
