@@ -736,6 +736,22 @@ int wsmg_attn_fp8_mfma_fwd(const uint8_t* q_codes, const float* q_scale, const u
                            const int* set_start, float scale, int B, int U, int L, int C, float* out, float* attn,
                            wsmg_stream_t stream);
 
+/* Backward of wsmg_attn_fp8_mfma_fwd on the matrix cores (csrc/wsmg_attn_fp8_mfma_bwd.hip), two launches.  Codes, scales, row_ids and
+ * set_start as the forward read them; inverse [B] (the forward's grouping came from it); attn [B][L] the forward's weights; dout
+ * [B][256] and dattn [B][L], either may be NULL (an absent gradient).  With q^, K^, V^ the de-quantised operands:
+ *   dp = dout V^^T + dattn, dl = attn o (dp - sum_l attn o dp), dq [B][256] = scale dl K^,
+ *   dk [U][L][256] = scale sum_{b in u} dl_b^T q^_b, dv [U][L][256] = sum_{b in u} attn_b^T dout_b
+ * — the straight-through gradients of the de-quantised q, k_sets, v_sets.  All four contractions run on v_mfma_f32_32x32x16_bf16: e4m3
+ * operands converted exactly, float32 operands as bf16 (hi, lo) pairs, the softmax gradient in float32.  dk and dv are reduced inside
+ * one workgroup per (set, 32 tokens) that walks the set's rows in ascending row index: bit-reproducible, no atomics; every element of
+ * dq, dk, dv is written (a set without rows gets zeros; tokens at or past the set's length get exact zeros because their attn is 0).
+ * dl_scratch: [B][L] float32, the only scratch.  WSMG_EINVAL, before any launch, for a NULL operand or output, C != 256, L > 224,
+ * U > 1024 or a non-positive size. */
+int wsmg_attn_fp8_mfma_bwd(const uint8_t* q_codes, const float* q_scale, const uint8_t* k_codes, const float* k_scale,
+                           const uint8_t* v_codes, const float* v_scale, const int* row_ids, const int* set_start,
+                           const int64_t* inverse, const float* attn, const float* dout, const float* dattn, float scale, int B, int U,
+                           int L, int C, float* dq, float* dk, float* dv, float* dl_scratch, wsmg_stream_t stream);
+
 /* The operands of wsmg_attn_fp8_mfma_fwd from float32 tensors in two launches (round 3): per-tensor scales (x_scale > 0: the
  * caller's; otherwise max(amax|x| * float32(1/448), 1e-30) — bit-equal to torch's `(x.abs().amax() / 448.0).clamp_min(1e-30)` — a NaN
  * input giving a NaN scale), the e4m3 codes of q [B][C], k_sets and v_sets

@@ -1,12 +1,85 @@
 #!/usr/bin/env python3
 """GPU-box tool: BASELINE configs[4] — text attention, B=64, L=160, e4m3 tokens — time and bandwidth of the fused
-kernel (algorithmic bytes per row = 256*L token bytes + 256*4 query + (256+L)*4 outputs)."""
+kernel (algorithmic bytes per row = 256*L token bytes + 256*4 query + (256+L)*4 outputs).
+
+    tools/bench_attn_fp8.py                       # the forward kernels and the single-query backward, as before
+    tools/bench_attn_fp8.py --shared-bwd [--out FILE]
+        the shared-set backward on the matrix cores (wsmg_attn_fp8_mfma_bwd, through ops.attention_fp8_shared's autograd node)
+        against the float32 ops.attention_shared's backward at (B, U, L) = (64, 8, 160) and (512, 8, 80): HIP events, the two arms
+        interleaved in one process per shape, each shape a child process under its own time limit; nothing starts after a failure."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "ws-mgmap_amd"))
+BWD_SHAPES = ((64, 8, 160), (512, 8, 80))
+
+
+def _shared_bwd_parent(argv):
+    import subprocess
+    out = argv[argv.index("--out") + 1] if "--out" in argv else None
+    lines = ["shared-set attention backward, B rows over U sets of L tokens: ops.attention_fp8_shared (wsmg_attn_fp8_mfma_bwd, two launches) "
+             "against the float32 ops.attention_shared (kernel + one-hot membership + two batched GEMMs); us per backward, HIP events "
+             "around 50 calls, three interleaved rounds"]
+    for shape in BWD_SHAPES:
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--shared-bwd-shape", ",".join(map(str, shape))],
+                           capture_output=True, text=True, timeout=180)
+        lines += [l for l in r.stdout.splitlines() if l.strip()]
+        if r.returncode != 0:
+            lines.append(f"shape {shape}: exit status {r.returncode}; stopping\n{r.stderr[-2000:]}")
+            break
+    text = "\n".join(lines) + "\n"
+    sys.stdout.write(text)
+    if out:
+        with open(out, "w") as f:
+            f.write(text)
+    return 0 if "exit status" not in text else 1
+
+
+if "--shared-bwd" in sys.argv:
+    sys.exit(_shared_bwd_parent(sys.argv))
+
 import torch
 from wsmgmap import ops, _abi
 P = ops._p; st = ops._stream
+
+
+def _shared_bwd_shape(B, U, L):
+    C = 256
+    torch.manual_seed(2)
+    q = torch.randn(B, C, device="cuda"); k = torch.randn(U, L, C, device="cuda") * 0.7; v = torch.randn(U, L, C, device="cuda")
+    inv = torch.arange(B, device="cuda") % U
+    lens = torch.full((U,), L, dtype=torch.int32, device="cuda")
+    mask = torch.zeros(U, L, dtype=torch.uint8, device="cuda")
+    dout = torch.randn(B, C, device="cuda"); dattn = torch.randn(B, L, device="cuda")
+    arms = {}
+    for name, fwd in (("fp8 MFMA", lambda a, b, c: ops.attention_fp8_shared(a, b, c, lens, inv, 1 / 16)),
+                      ("float32", lambda a, b, c: ops.attention_shared(a, b, c, mask, inv, 1 / 16))):
+        leaves = [t.clone().requires_grad_(True) for t in (q, k, v)]
+        outs = fwd(*leaves)
+        arms[name] = lambda outs=outs, leaves=leaves: torch.autograd.grad(outs, leaves, (dout, dattn), retain_graph=True)
+    # the new entry point alone (no autograd node, no allocation)
+    sc = [float(t.abs().max() / 448.0) for t in (q, k, v)]
+    _, attn, (qc, kc, vc, s3, order, start) = sys.modules["wsmgmap.ops.attention"]._fp8_shared_staged(q, k, v, lens, inv, sc, 1 / 16)
+    dq = torch.empty(B, C, device="cuda"); dk = torch.empty(U, L, C, device="cuda"); dv = torch.empty_like(dk); dl = torch.empty(B, L, device="cuda")
+    arms["fp8 MFMA, entry point alone"] = lambda: _abi.call(
+        "wsmg_attn_fp8_mfma_bwd", P(qc), P(s3[0:1]), P(kc), P(s3[1:2]), P(vc), P(s3[2:3]), P(order), P(start), P(inv), P(attn), P(dout), P(dattn),
+        1 / 16, B, U, L, C, P(dq), P(dk), P(dv), P(dl), st())
+    res = {n: [] for n in arms}
+    for rnd in range(3):
+        for n, f in arms.items():
+            for _ in range(5): f()
+            torch.cuda.synchronize()
+            a = torch.cuda.Event(enable_timing=True); e = torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(50): f()
+            e.record(); torch.cuda.synchronize()
+            res[n].append(a.elapsed_time(e) / 50 * 1e3)
+    print(f"  B={B} U={U} L={L}: " + "; ".join(f"{n} {sorted(t)[1]:.1f} us (rounds {', '.join(f'{x:.1f}' for x in t)})" for n, t in res.items()))
+
+
+if "--shared-bwd-shape" in sys.argv:
+    _shared_bwd_shape(*(int(x) for x in sys.argv[sys.argv.index("--shared-bwd-shape") + 1].split(",")))
+    sys.exit(0)
+
 def _floor():
     t = torch.zeros(256, device="cuda")
     f = lambda: _abi.call("wsmg_relu_fwd", P(t), P(t), 256, st())

@@ -173,6 +173,7 @@ _SIG["wsmg_lstm_state_bwd_chain"] = [c_p] * 8 + [c_i] * 3 + [c_p] * 4 + [c_i, c_
 _SIG["wsmg_lstm_state_chain_workgroups"] = []
 _SIG["wsmg_attn_fp8_mfma_fused"] = [c_p] * 5 + [c_f] * 4 + [c_i] * 4 + [c_p, ctypes.c_uint, c_i, c_p, c_p, c_p, c_p]
 _SIG["wsmg_attn_fp8_mfma_fused_arrivals"] = [c_i] * 4
+_SIG["wsmg_attn_fp8_mfma_bwd"] = [c_p] * 12 + [c_f] + [c_i] * 4 + [c_p] * 5
 _SIG["wsmg_collate_ego_sparse_nhwc_bf16"] = [c_p] * 5 + [c_i] * 4 + [c_f, c_p, c_p]
 _SIG["wsmg_ego_sparse_pack"] = [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]
 _SIG["wsmg_debug_occupy"] = [c_i, c_i, c_i, c_p, c_p, c_p]

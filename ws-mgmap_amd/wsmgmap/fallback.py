@@ -31,9 +31,13 @@ class RecurrentCoreFallback:
         self.level = 0
         self.reasons = []
         # (an LSTM of another hidden size, or on the stock route, takes the staged route whatever recurrent_chunks says)
-        chained = getattr(net, "recurrent_chunks", 0) > 0 and recurrent.core_cell(net) is not None
+        # (so does MODEL.TEXT_ATTENTION = "fp8": the e4m3 instruction attention is not wired into the recurrent core)
+        fp8_text = getattr(net, "text_attention", "f32") == "fp8"
+        chained = getattr(net, "recurrent_chunks", 0) > 0 and recurrent.core_cell(net) is not None and not fp8_text
         self.levels = [("chained (one launch per recurrence, device-side chunk counters)" if chained and debug.sw.recurrent_chain
-                        else "pipelined chunk launches" if chained else "staged"),
+                        else "pipelined chunk launches" if chained
+                        else "staged (MODEL.TEXT_ATTENTION = fp8: the e4m3 instruction attention runs outside the recurrent core)" if fp8_text
+                        else "staged"),
                        "staged (fallback: one persistent kernel at a time, no chaining, no decoder side stream)",
                        "stock MIOpen GRU / LSTM (fallback: no persistent kernel)"]
         self.read_status = _abi.take_rnn_status      # (a test substitutes its own)

@@ -21,6 +21,7 @@ import torch.nn as nn
 
 from .. import debug, ops, recurrent
 from ..common.rgb_mapping import RGBMapping
+from ..config import text_attention_option
 from .encoders.instruction_encoder import InstructionEncoder
 from .encoders.map_encoder import MapDecoder, MapEncoder
 from .encoders.resnet_encoders import VlnResnetDepthEncoder
@@ -113,6 +114,9 @@ class MGMapNet(nn.Module):
         if want not in ("f32", "fp32", "float32", "bf16", "bfloat16"):
             raise ValueError(f"MODEL.COMPUTE_DTYPE must be 'f32', 'bf16' or 'bf16+f32grad', got {want!r}")
         self.compute_dtype = torch.bfloat16 if want in ("bf16", "bfloat16") else torch.float32
+        # instruction attention: "f32" (ops.attention_shared) or "fp8" (opt-in: ops.attention_fp8_shared, e4m3 storage on the matrix
+        # cores in both directions, rollout and update alike; the update then takes the staged route — recurrent.usable)
+        self.text_attention = text_attention_option(mc)
         if self.f32grad:
             for conv in (self.map_encoder.cnn[0], self.map_decoder.base_model.conv1, self.map_decoder.conv_original_size0[0]):
                 conv._wsmg_f32grad = True
@@ -376,10 +380,14 @@ class MGMapNet(nn.Module):
                     t.record_stream(side)
         with torch.cuda.stream(side):
             after = getattr(self, "_encoder_done", None)
+            if dd is None and self.text_attention == "fp8":
+                dd = self.instruction_encoder.dedup(tok)
             instr_u, mask_u, inverse = self.instruction_encoder.encode_unique(tok, dedup=dd, lstm_after=after)
             text_k_u = self._key_projection(self.state_text_k_layer, instr_u)
             # the B rows attend over the U unique sets in place (ops.attention_shared): no per-row copies
             text = (text_k_u.contiguous(), instr_u.contiguous(), mask_u.to(torch.uint8).contiguous(), inverse.contiguous())
+            if self.text_attention == "fp8":      # + the valid-token counts of the unique instructions, as the dedup left them on the device
+                text = text + (dd[3].to(torch.int32),)
         return text, side
 
     def forward(self, observations, rnn_hidden_states, prev_actions, masks):
@@ -496,7 +504,7 @@ class MGMapNet(nn.Module):
         if (self.recurrent_chunks > 0 and not ops.ranks_share_gpu() and torch.is_grad_enabled() and not rows and "map" in self._inputs
                 and ((cell == "GRU" and n1 == 1 and rnn_hidden_states.size(0) == 2)
                      or (cell == "LSTM" and rnn_hidden_states.size(0) == 2 * n1))
-                and recurrent.usable(state_in, map_tokens, n_env, text)):
+                and recurrent.usable(state_in, map_tokens, n_env, text, text_attention=self.text_attention)):
             # GRU 1 -> text attention -> map attention -> compress -> GRU 2 as one autograd node, pipelined over time chunks on three
             # streams, parameter gradients off the chain (wsmgmap/recurrent.py); same kernels, same arithmetic row for row
             text_ready = torch.cuda.Event()
@@ -519,11 +527,16 @@ class MGMapNet(nn.Module):
 
         # instruction attention: keys projected once per unique instruction, gathered per row
         torch.cuda.current_stream().wait_stream(side)
-        text_k_u, text_v_u, text_mask_u, inverse = text
+        text_k_u, text_v_u, text_mask_u, inverse = text[:4]
         for t in text:
             t.record_stream(torch.cuda.current_stream())
-        text_embedding, _ = ops.attention_shared(lin(self.state_text_q_layer, state).contiguous(), text_k_u, text_v_u, text_mask_u,
-                                                 inverse, self._scale_f)
+        text_q = lin(self.state_text_q_layer, state).contiguous()
+        if (self.text_attention == "fp8" and text_q.is_cuda and text_k_u.shape[1] <= 224 and text_k_u.shape[2] == 256
+                and text_q.shape[1] == 256):
+            # MODEL.TEXT_ATTENTION = "fp8": the same arithmetic with and without autograd (rollout and update)
+            text_embedding, _ = ops.attention_fp8_shared(text_q, text_k_u.float(), text_v_u.float(), text[4], inverse, self._scale_f)
+        else:
+            text_embedding, _ = ops.attention_shared(text_q, text_k_u, text_v_u, text_mask_u, inverse, self._scale_f)
 
         # map attention
         # text_map_k_layer is folded into the query (ops._AttnFolded): the 576 map tokens are read once, as

@@ -275,26 +275,99 @@ def _fp8_fused_state(dev):
     return st
 
 
-@torch.no_grad()
-def attention_fp8_shared(q, k_sets, v_sets, lengths, inverse, scale=1.0 / 16, scales=None):
-    """BASELINE configs[4] on the matrix cores (csrc/wsmg_attn_fp8_mfma.hip): `_attn` (mg_map_policy.py:173-178) of B rows over U
-    shared instruction sets with e4m3 storage — S = Q K^T on v_mfma_f32_32x32x16_fp8_fp8, float32 softmax, O = P V on the bf16
-    matrix pipe.  q [B,256] float32; k_sets, v_sets [U,L,256] float32 (token-major keys and values of each unique instruction);
-    lengths [U] int (valid tokens; the rest are masked) or None; inverse [B] int64 (row b uses set inverse[b]).
-    scales: (q_scale, k_scale, v_scale) Python floats for the quantisation; None: amax / 448 per tensor, computed on the device.
-    Forward only (rollout / evaluation); -> (context [B,256], weights [B,L])."""
+def _fp8_shared_args(q, k_sets, v_sets, lengths, inverse, scales):
+    """Checked, contiguous operands of the shared-set fp8 attention: (q, k_sets, v_sets, lens int32 or None, inverse int64, s3)."""
     _req(q, k_sets, v_sets, lengths, inverse)
     _f32(q, k_sets, v_sets)
     B, C = q.shape
     U, L, _ = k_sets.shape
     if C != 256 or k_sets.shape != v_sets.shape or k_sets.shape[2] != C or inverse.numel() != B or L > 224:
         raise _abi.WsmgError("attention_fp8_shared: q [B,256], k / v sets [U,L<=224,256], inverse [B]")
-    dev = q.device
     if inverse.dtype != torch.int64:
         inverse = inverse.long()
-    q, k_sets, v_sets, inverse = q.contiguous(), k_sets.contiguous(), v_sets.contiguous(), inverse.contiguous()
     s3 = [float(x) if x is not None else 0.0 for x in (scales or (None, None, None))]
     lens = None if lengths is None else lengths.to(torch.int32).contiguous()
+    return q.contiguous(), k_sets.contiguous(), v_sets.contiguous(), lens, inverse.contiguous(), s3
+
+
+def _fp8_shared_staged(q, k_sets, v_sets, lens, inverse, s3, scale):
+    """Scales, codes and the row grouping in two launches (wsmg_attn_fp8_prep) instead of ~25 stock ones, then the attention
+    (wsmg_attn_fp8_mfma_fwd): -> (out, attn, (q codes, k codes, v codes, scales [3], row_ids, set_start))."""
+    B, C = q.shape
+    U, L, _ = k_sets.shape
+    dev = q.device
+    qc = torch.empty(B, C, device=dev, dtype=torch.uint8)
+    kc = torch.empty(U, L, C, device=dev, dtype=torch.uint8)
+    vc = torch.empty(U, L, C, device=dev, dtype=torch.uint8)
+    sc = torch.empty(3, device=dev, dtype=torch.float32)
+    order = torch.empty(B, device=dev, dtype=torch.int32)
+    start = torch.empty(U + 1, device=dev, dtype=torch.int32)
+    ws = torch.zeros(4, device=dev, dtype=torch.int32)
+    _abi.call("wsmg_attn_fp8_prep", _p(q), _p(k_sets), _p(v_sets), _p(inverse), B, U, L, C, s3[0], s3[1], s3[2], _p(qc), _p(kc), _p(vc),
+              _p(sc), _p(order), _p(start), _p(ws), _stream())
+    qs, ks, vs = sc[0:1], sc[1:2], sc[2:3]
+    out = torch.empty(B, C, device=dev, dtype=torch.float32)
+    attn = torch.empty(B, L, device=dev, dtype=torch.float32)
+    _abi.call("wsmg_attn_fp8_mfma_fwd", _p(qc), _p(qs), _p(kc), _p(ks), _p(vc), _p(vs), _p(lens), _p(order), _p(start), float(scale),
+              B, U, L, C, _p(out), _p(attn), _stream())
+    return out, attn, (qc, kc, vc, sc, order, start)
+
+
+class _AttnFp8Shared(torch.autograd.Function):
+    """Trainable form of the shared-set fp8 attention.  The forward takes the route that leaves codes, scales and grouping in
+    tensors (wsmg_attn_fp8_prep + wsmg_attn_fp8_mfma_fwd) and saves them; the backward (wsmg_attn_fp8_mfma_bwd, two launches) reads
+    the BYTES and runs its four contractions on the bf16 matrix pipe.  The gradients are straight-through: those of the
+    de-quantised q, k_sets, v_sets, returned for the float32 tensors (the convention of _AttnFp8 for x).  dK_u / dV_u are reduced in
+    one workgroup per (set, 32 tokens), rows in ascending index: bit-reproducible; no [B, L, 256] or [U, B, L] tensor exists."""
+
+    @staticmethod
+    def forward(ctx, q, k_sets, v_sets, lens, inverse, scale, s3):
+        out, attn, (qc, kc, vc, sc, order, start) = _fp8_shared_staged(q, k_sets, v_sets, lens, inverse, s3, scale)
+        ctx.save_for_backward(qc, kc, vc, sc, order, start, inverse, attn)
+        ctx.scale = float(scale)
+        ctx.set_materialize_grads(False)
+        return out, attn
+
+    @staticmethod
+    def backward(ctx, dout, dattn):
+        qc, kc, vc, sc, order, start, inverse, attn = ctx.saved_tensors
+        B, C = qc.shape
+        U, L, _ = kc.shape
+        dev = qc.device
+        dout = None if dout is None else dout.contiguous().float()
+        dattn = None if dattn is None else dattn.contiguous().float()
+        dq = torch.empty(B, C, device=dev, dtype=torch.float32)
+        dk = torch.empty(U, L, C, device=dev, dtype=torch.float32)
+        dv = torch.empty(U, L, C, device=dev, dtype=torch.float32)
+        dl = torch.empty(B, L, device=dev, dtype=torch.float32)
+        _abi.call("wsmg_attn_fp8_mfma_bwd", _p(qc), _p(sc[0:1]), _p(kc), _p(sc[1:2]), _p(vc), _p(sc[2:3]), _p(order), _p(start),
+                  _p(inverse), _p(attn), _p(dout), _p(dattn), ctx.scale, B, U, L, C, _p(dq), _p(dk), _p(dv), _p(dl), _stream())
+        return dq, dk, dv, None, None, None, None
+
+
+def attention_fp8_shared(q, k_sets, v_sets, lengths, inverse, scale=1.0 / 16, scales=None):
+    """BASELINE configs[4] on the matrix cores (csrc/wsmg_attn_fp8_mfma.hip): `_attn` (mg_map_policy.py:173-178) of B rows over U
+    shared instruction sets with e4m3 storage — S = Q K^T on v_mfma_f32_32x32x16_fp8_fp8, float32 softmax, O = P V on the bf16
+    matrix pipe.  q [B,256] float32; k_sets, v_sets [U,L,256] float32 (token-major keys and values of each unique instruction);
+    lengths [U] int (valid tokens; the rest are masked) or None; inverse [B] int64 (row b uses set inverse[b]).
+    scales: (q_scale, k_scale, v_scale) Python floats for the quantisation; None: amax / 448 per tensor, computed on the device.
+    -> (context [B,256], weights [B,L]).  Differentiable in q, k_sets and v_sets when gradients are enabled and one of them
+    requires grad (_AttnFp8Shared: straight-through gradients of the de-quantised operands, wsmg_attn_fp8_mfma_bwd); lengths, inverse
+    and scales get no gradient.  Without autograd: one launch where the fused kernel applies (`last_fp8_shared_launches`)."""
+    if torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (q, k_sets, v_sets)):
+        q, k_sets, v_sets, lens, inverse, s3 = _fp8_shared_args(q, k_sets, v_sets, lengths, inverse, scales)
+        global last_fp8_shared_launches
+        last_fp8_shared_launches = 2 if all(x > 0.0 for x in s3) else 3
+        return _AttnFp8Shared.apply(q, k_sets, v_sets, lens, inverse, scale, s3)
+    return _attention_fp8_shared_nograd(q, k_sets, v_sets, lengths, inverse, scale, scales)
+
+
+@torch.no_grad()
+def _attention_fp8_shared_nograd(q, k_sets, v_sets, lengths, inverse, scale, scales):
+    q, k_sets, v_sets, lens, inverse, s3 = _fp8_shared_args(q, k_sets, v_sets, lengths, inverse, scales)
+    B, C = q.shape
+    U, L, _ = k_sets.shape
+    dev = q.device
     global last_fp8_shared_launches
     # round 5: ONE launch (scales, codes, row grouping and the attention: wsmg_attn_fp8_mfma_fused) whenever the maxima pass's grid
     # barrier is safe (<= 128 attention workgroups) or the caller fixed the scales; not under a HIP-graph capture (the arrival target
@@ -313,19 +386,5 @@ def attention_fp8_shared(q, k_sets, v_sets, lengths, inverse, scale=1.0 / 16, sc
         last_fp8_shared_launches = 1
         return out, attn
     last_fp8_shared_launches = 3 if need else 2
-    # scales, codes and the row grouping in two launches (wsmg_attn_fp8_prep) instead of ~25 stock ones
-    qc = torch.empty(B, C, device=dev, dtype=torch.uint8)
-    kc = torch.empty(U, L, C, device=dev, dtype=torch.uint8)
-    vc = torch.empty(U, L, C, device=dev, dtype=torch.uint8)
-    sc = torch.empty(3, device=dev, dtype=torch.float32)
-    order = torch.empty(B, device=dev, dtype=torch.int32)
-    start = torch.empty(U + 1, device=dev, dtype=torch.int32)
-    ws = torch.zeros(4, device=dev, dtype=torch.int32)
-    _abi.call("wsmg_attn_fp8_prep", _p(q), _p(k_sets), _p(v_sets), _p(inverse), B, U, L, C, s3[0], s3[1], s3[2], _p(qc), _p(kc), _p(vc),
-              _p(sc), _p(order), _p(start), _p(ws), _stream())
-    qs, ks, vs = sc[0:1], sc[1:2], sc[2:3]
-    out = torch.empty(B, C, device=dev, dtype=torch.float32)
-    attn = torch.empty(B, L, device=dev, dtype=torch.float32)
-    _abi.call("wsmg_attn_fp8_mfma_fwd", _p(qc), _p(qs), _p(kc), _p(ks), _p(vc), _p(vs), _p(lens), _p(order), _p(start), float(scale),
-              B, U, L, C, _p(out), _p(attn), _stream())
+    out, attn, _ = _fp8_shared_staged(q, k_sets, v_sets, lens, inverse, s3, scale)
     return out, attn

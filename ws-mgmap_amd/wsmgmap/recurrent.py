@@ -145,11 +145,12 @@ def _roles(streams, main):
     return sa, sg, sa
 
 
-def usable(state_in, tokens, n_env, text, capturing_ok=True):
+def usable(state_in, tokens, n_env, text, capturing_ok=True, text_attention="f32"):
     """Can the pipelined block take this call?  Training-size sequences (more than one step) of at most 8 environments on the GPU,
-    float32 state / text tensors, map tokens [B, I, 256]."""
+    float32 state / text tensors, map tokens [B, I, 256], the float32 instruction attention (MODEL.TEXT_ATTENTION = "fp8" is not
+    wired into the block: the update takes the staged route)."""
     B = state_in.shape[0]
-    return (state_in.is_cuda and state_in.dtype == torch.float32 and n_env <= MAX_BATCH and B % n_env == 0 and B // n_env > 1
+    return (text_attention == "f32" and state_in.is_cuda and state_in.dtype == torch.float32 and n_env <= MAX_BATCH and B % n_env == 0 and B // n_env > 1
             and tokens.dim() == 3 and tokens.shape[2] == 256 and all(t.dtype in (torch.float32, torch.bfloat16) for t in text[:2]))
 
 
