@@ -118,10 +118,12 @@ def channel_maxpool(feat: torch.Tensor, map_depth: int) -> torch.Tensor:
     return x.reshape(bs, h, w, -1).permute(0, 3, 1, 2)
 
 
-def rotate(x: torch.Tensor, heading: torch.Tensor) -> torch.Tensor:
-    """RotateTensor.forward (rgb_mapping.py:239-250): A = [[c, s, 0], [-s, c, 0]]."""
-    t = heading.reshape(-1)
-    A = torch.zeros(x.size(0), 2, 3)
+def rotate(x: torch.Tensor, heading: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
+    """RotateTensor.forward (rgb_mapping.py:239-250): A = [[c, s, 0], [-s, c, 0]].
+    dtype=torch.float64: the same float32 heading and input, matrix / grid / sampling evaluated in double."""
+    t = heading.reshape(-1).to(dtype)
+    x = x.to(dtype)
+    A = torch.zeros(x.size(0), 2, 3, dtype=dtype)
     A[:, 0, 0] = torch.cos(t)
     A[:, 0, 1] = torch.sin(t)
     A[:, 1, 0] = -torch.sin(t)
@@ -140,36 +142,58 @@ def grid_cell(gps: torch.Tensor, G: int, resolution: float = 0.12):
     return gx, gy
 
 
-def translate(x: torch.Tensor, tx: torch.Tensor, ty: torch.Tensor) -> torch.Tensor:
+def translate(x: torch.Tensor, tx: torch.Tensor, ty: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
     """get_grid's trans_grid + grid_sample (rgb_mapping.py:127-139,52-53)."""
+    x, tx, ty = x.to(dtype), tx.to(dtype), ty.to(dtype)
     one, zero = torch.ones_like(tx), torch.zeros_like(tx)
     theta = torch.stack([torch.stack([one, -zero, tx], 1), torch.stack([zero, one, ty], 1)], 1)
     grid = F.affine_grid(theta, list(x.shape), align_corners=False)
     return F.grid_sample(x, grid, mode="bilinear", padding_mode="zeros", align_corners=False)
 
 
-class MapperRef:
-    """State + step of Mapping.project_feat_to_map / RGBMapping.forward (rgb_mapping.py:32-90)."""
+def paste_bounds(G: int, E: int):
+    """Rows / columns [lo, hi) of the centre E x E of a G x G map (rgb_mapping.py:46-50)."""
+    return G // 2 - math.floor(E / 2), G // 2 + math.ceil(E / 2)
 
-    def __init__(self, num_proc, G=240, E=100, C=64, resolution=0.12):
-        self.G, self.E, self.C, self.res = G, E, C, resolution
-        self.full_global_map = torch.zeros(num_proc, G, G, C)
+
+def retrieve(global_map: torch.Tensor, gps: torch.Tensor, compass: torch.Tensor, E: int, resolution: float = 0.12,
+             dtype=torch.float32) -> torch.Tensor:
+    """The retrieving half of Mapping.project_feat_to_map alone (rgb_mapping.py:57-70): global_map [B,G,G,C] translated back to
+    the agent, centre E x E cropped, rotated by the compass -> [B,C,E,E].  The cell (`grid_cell`) is float32 in both modes;
+    the cell -> shift division and everything after it is evaluated in `dtype`."""
+    G = global_map.shape[1]
+    gx, gy = grid_cell(gps, G, resolution)
+    gx, gy = gx.to(dtype), gy.to(dtype)
+    lo, hi = paste_bounds(G, E)
+    half = G // 2
+    back = translate(global_map.permute(0, 3, 1, 2).contiguous(), (gy - half) / half, (gx - half) / half, dtype)
+    crop = back[:, :, lo:hi, lo:hi]
+    return rotate(crop, compass, dtype)
+
+
+class MapperRef:
+    """State + step of Mapping.project_feat_to_map / RGBMapping.forward (rgb_mapping.py:32-90).
+    dtype=torch.float64 evaluates the float part (rotation, translation, sampling, the global map) in double on the same float32
+    inputs; the integer gate and the agent's cell stay float32 — they decide cells, they are not sampling arithmetic."""
+
+    def __init__(self, num_proc, G=240, E=100, C=64, resolution=0.12, dtype=torch.float32):
+        self.G, self.E, self.C, self.res, self.dtype = G, E, C, resolution, dtype
+        self.full_global_map = torch.zeros(num_proc, G, G, C, dtype=dtype)
 
     def step(self, feat, depth_raw, gps, compass, masks):
         """feat [B,Cf,Hf,Wf] torch f32; returns final_retrieval [B,C,E,E]."""
-        G, E = self.G, self.E
+        G, E, dt = self.G, self.E, self.dtype
         bs = feat.shape[0]
         feat = channel_maxpool(feat, self.C)
         gx, gy = grid_cell(gps, G, self.res)
-        self.full_global_map[:bs] = self.full_global_map[:bs] * masks.view(bs, 1, 1, 1)
+        gx, gy = gx.to(dt), gy.to(dt)
+        self.full_global_map[:bs] = self.full_global_map[:bs] * masks.view(bs, 1, 1, 1).to(dt)
         proj, *_ = project_to_ground(feat.numpy(), depth_raw.numpy(), E)
-        proj = rotate(torch.from_numpy(proj), -compass)
-        lo, hi = G // 2 - math.floor(E / 2), G // 2 + math.ceil(E / 2)
-        agent_view = torch.zeros(bs, self.C, G, G)
+        proj = rotate(torch.from_numpy(proj), -compass, dt)
+        lo, hi = paste_bounds(G, E)
+        agent_view = torch.zeros(bs, self.C, G, G, dtype=dt)
         agent_view[:, :, lo:hi, lo:hi] = proj
         half = G // 2
-        translated = translate(agent_view, -(gy - half) / half, -(gx - half) / half)
+        translated = translate(agent_view, -(gy - half) / half, -(gx - half) / half, dt)
         self.full_global_map[:bs] = torch.maximum(self.full_global_map[:bs], translated.permute(0, 2, 3, 1))
-        back = translate(self.full_global_map[:bs].permute(0, 3, 1, 2).contiguous(), (gy - half) / half, (gx - half) / half)
-        crop = back[:, :, lo:hi, lo:hi]
-        return rotate(crop, compass)
+        return retrieve(self.full_global_map[:bs], gps, compass, E, self.res, dt)

@@ -27,13 +27,21 @@ def bev_inputs(name):
     feat [B,C,Hf,Hf] with negative values.  Sample 0: random; sample 1: structured depth
     (zero rows, depths on multiples of the 0.12 m cell => .5 ties before round());
     sample B-1: all-zero depth (every source invalid)."""
-    E, C, Hf, B = BEV_CASES[name]
+    return bev_inputs_at(name, *BEV_CASES[name])
+
+
+def bev_inputs_at(name, E, C, Hf, B):
+    """`bev_inputs` at any geometry (the fill is seeded by `name`).  With an odd E, `half = (E - 1) / 2` is an integer and the
+    .5 ties sit at depths on ODD multiples of half a cell: sample 1 carries those too, in rows 100:128 — rows no golden case has
+    (their E is even, the rows keep the random fill there)."""
     depth = df.uniform(f"g1.{name}.depth", (B, 256, 256, 1)) + np.float32(0.5)
     depth[:, :8] = 0.0
     k = (np.arange(256, dtype=np.float32) % 97).astype(np.float32)
     depth[1, 128:200, :, 0] = (np.float32(0.012) * k)[None, :]
     depth[1, 200:230, ::3, 0] = 0.0
     depth[1, 230:, :, 0] = np.float32(0.3)
+    if E % 2:
+        depth[1, 100:128, :, 0] = (np.float32(0.006) * (np.float32(2) * k + np.float32(1)))[None, :]
     depth[B - 1] = 0.0
     feat = df.uniform(f"g1.{name}.feat", (B, C, Hf, Hf), 4.0)
     return dict(E=E, C=C, Hf=Hf, B=B, depth=depth, feat=feat)

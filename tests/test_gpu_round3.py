@@ -728,7 +728,9 @@ def test_mean_last_matches_torch(shape):
 def test_bev_scatter_rotate_and_plane_fuse_equal_the_separate_launches(B, E, C, G):
     """wsmg_bev_scatter_rotate + wsmg_map_fuse_planes + wsmg_map_retrieve_fused (round 3: what Mapping.project_feat_to_map runs)
     against the launches they replace (wsmg_bev_scatter_max, wsmg_bev_rotate, wsmg_map_fuse, wsmg_map_retrieve;
-    rgb_mapping.py:34-70,81-84,206-250), which the oracle tests pin: the rotated map, the global map and the retrieved map bit for bit, over several steps so the max-fuse meets a non-empty map,
+    rgb_mapping.py:34-70,81-84,206-250) — those base launches are pinned to the oracle by test_map_sequence_vs_oracle (the G2 geometry,
+    agents near the centre) and, at these edges (window off the map, axis headings, odd E, odd G, G == E, cfg4), by
+    tests/test_gpu_map_edges.py: the rotated map, the global map and the retrieved map bit for bit, over several steps so the max-fuse meets a non-empty map,
     with agents near the border of the global map (window partly outside), a mid-sequence episode reset and every heading sign."""
     from wsmgmap import ops
     Hf = 64

@@ -474,7 +474,9 @@ def test_sparse_ego_map_collates_bit_identically_to_the_dense_record():
                          ids=["e100_c64", "e200_c40", "e33_c8", "e50_c128", "e24_c168_g_eq_e"])
 def test_map_retrieve_lds_tiles_equal_crop_then_rotate(B, E, C, G):
     """wsmg_map_retrieve_tiled (round 5: ops.map_retrieve's default) against wsmg_map_retrieve — map_crop_kernel then
-    rotate_nhwc_kernel, the launches the oracle tests pin (rgb_mapping.py:57-70) — bit for bit on a DENSE global map (every tap
+    rotate_nhwc_kernel (rgb_mapping.py:57-70), the launches which test_map_sequence_vs_oracle pins to the oracle at the G2 geometry and
+    tests/test_gpu_map_edges.py at these edges (dense map, axis headings, agents beyond the border, odd E, odd G, G == E, cfg4; all
+    three forms of the retrieve against float64) — bit for bit on a DENSE global map (every tap
     carries weight): headings on and between the axes (0, +-pi/4, +-pi/2, pi, random), agents in the centre, at and beyond the map
     border (taps outside the global map), ego sizes that are not multiples of the 8-pixel tile, G == E; one map holds an infinity
     and a NaN (a tap with weight 0 still propagates them the same way), one trial has an infinite gps (the tile geometry does not fit

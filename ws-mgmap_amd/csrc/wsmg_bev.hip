@@ -968,6 +968,13 @@ int scatter_window(int Cf, int C) {
   return m > 4 ? 4 : m;
 }
 
+// Shapes whose (source << 16) | cell entries the compacted list can hold: both ids in 16 bits, and never both products at the limit
+// together — source 65 535 on cell 65 535 would be 0xffffffff, the list's "no entry" word.
+bool compact_fits(int Hf, int Wf, int E) {
+  const int64_t HW = (int64_t)Hf * Wf, E2 = (int64_t)E * E;
+  return HW <= 65536 && E2 <= 65536 && !(HW == 65536 && E2 == 65536);
+}
+
 int sgrid(int64_t n, int cap = 4096) {
   int64_t g = wsmg_cdiv(n, 256);
   if (g > cap) g = cap;
@@ -997,11 +1004,11 @@ extern "C" int wsmg_bev_index(const float* depth, int B, int Hd, int Wd, float d
 }
 
 // wsmg_bev_index + the compacted list of valid sources (round 6): clist [B][Hf*Wf] uint32, cnt [B][ceil(Hf*Wf / 8192)] int32, both
-// written in full by this launch (nothing to zero); needs Hf*Wf <= 65536 and E*E <= 65536.
+// written in full by this launch (nothing to zero); needs Hf*Wf <= 65536 and E*E <= 65536, not both at 65536 (compact_fits).
 extern "C" int wsmg_bev_index_compact(const float* depth, int B, int Hd, int Wd, float depth_scale, int Hf, int Wf, int E,
                                       float local_scale, int32_t* lin_idx, uint32_t* clist, int32_t* cnt, wsmg_stream_t stream) {
   if (B <= 0 || Hd <= 0 || Wd <= 0 || Hf <= 0 || Wf <= 0 || E <= 0 || Hf > Hd || Wf > Wd || B > 65535) return WSMG_EINVAL;
-  if ((int64_t)Hf * Wf > 65536 || (int64_t)E * E > 65536 || !clist || !cnt || !lin_idx) return WSMG_EINVAL;
+  if (!compact_fits(Hf, Wf, E) || !clist || !cnt || !lin_idx) return WSMG_EINVAL;
   IndexArgs a;
   a.depth = depth; a.lin = lin_idx;
   a.B = B; a.Hd = Hd; a.Wd = Wd; a.Hf = Hf; a.Wf = Wf; a.E = E;
@@ -1067,7 +1074,7 @@ extern "C" int wsmg_map_fuse(const float* ego_rot, float* global_map, const floa
 static int bev_scatter_rotate_impl(const float* feat, const int32_t* lin_idx, const uint32_t* clist, const int32_t* cnt, const float* heading,
                                    float sign, int B, int Cf, int Hf, int Wf, int C, int E, float* out_planes, wsmg_stream_t stream) {
   if (B <= 0 || Cf <= 0 || C <= 0 || C > Cf || E <= 1 || B > 65535) return WSMG_EINVAL;
-  if (clist && (!cnt || (int64_t)Hf * Wf > 65536 || (int64_t)E * E > 65536)) return WSMG_EINVAL;
+  if (clist && (!cnt || !compact_fits(Hf, Wf, E))) return WSMG_EINVAL;
   const int nblk = (int)wsmg_cdiv((int64_t)Hf * Wf, CB);
   const int E2 = E * E;
   const size_t plane = (size_t)E2 * sizeof(unsigned);
