@@ -100,6 +100,25 @@ int wsmg_map_retrieve_fused(const float* global_map, const float* gps, const flo
 int wsmg_map_retrieve_tiled(const float* global_map, const float* gps, const float* compass, int B, int C, int E, int G,
                             float resolution, float* out, wsmg_stream_t stream);
 
+/* Index, scatter-max and first rotation in ONE launch, for batches below 4 where the operator is launch latency: every plane
+ * workgroup derives the cells from the depth image itself (256 KB per sample, re-read out of L2) instead of waiting for the index
+ * launch.  Operands of wsmg_bev_index and wsmg_bev_scatter_rotate; lin_idx [B][Hf*Wf] is written when it is not NULL.  lin_idx
+ * and out_planes [B][C][E][E] are bit-identical to wsmg_bev_index followed by wsmg_bev_scatter_rotate (rgb_mapping.py:153-232,
+ * 239-250).  C <= Cf, E*E*4 <= 160 KiB. */
+int wsmg_bev_project(const float* depth, const float* feat, const float* heading, float sign, int B, int Hd, int Wd, float depth_scale,
+                     int Cf, int Hf, int Wf, int C, int E, float local_scale, int32_t* lin_idx /* may be NULL */, float* out_planes,
+                     wsmg_stream_t stream);
+/* Mapping.project_feat_to_map's global-map half and its retrieval (rgb_mapping.py:34-35,40-70) in ONE launch.  Operands of
+ * wsmg_map_fuse_planes (ego_rot_planes [B][C][E][E], global_map [P][G][G][C] in/out, gps [B][2], masks [B]) and of
+ * wsmg_map_retrieve_tiled (compass [B], out [B][E][E][C] NHWC); C % 4 == 0, C <= 64, E*E*4 <= 160 KiB.  After the call global_map
+ * and out are bit-identical to wsmg_map_fuse_planes followed by wsmg_map_retrieve_tiled — the episode reset of the sample's whole
+ * G x G map, windows that leave the map, odd E, odd G and G == E included — for masks in {0, 1} and finite features.  Every map
+ * element has one writer; a retrieval workgroup fuses what it reads itself, before or after that writer's store, which is exact
+ * because the fuse is idempotent per element under those masks (csrc/wsmg_bev.hip, map_fuse_retrieve_kernel).  No workgroup
+ * waits for another: capturable, no residency requirement. */
+int wsmg_map_fuse_retrieve(const float* ego_rot_planes, float* global_map, const float* gps, const float* compass,
+                           const float* masks, int B, int C, int E, int G, float resolution, float* out, wsmg_stream_t stream);
+
 /* ============================ operator 2: map conv / UNet decoder engine ============================ */
 /* cuDNN conv2d forward / backward at map_encoder.py:19-29,94-112, mg_map_policy.py:78-100,127,130.
  * Implicit GEMM on the f32 MFMA (v_mfma_f32_32x32x2_f32): exact float32 products, k-ordered

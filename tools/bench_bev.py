@@ -12,6 +12,15 @@ sys.path.insert(0, os.path.join(ROOT, "ws-mgmap_amd"))
 import torch
 from wsmgmap import ops
 
+def ab_rounds(pairs, rounds=7):
+    """Interleaved A/B in this process: every round times each form once (20 launches each), forms alternating; -> per form the
+    median over the rounds and the (min, max) of its round values — the spread between rounds is the margin of a comparison."""
+    vals = {k: [] for k, _ in pairs}
+    for _ in range(rounds):
+        for k, fn in pairs:
+            vals[k].append(timeit(fn))
+    return {k: (sorted(v)[len(v) // 2], min(v), max(v)) for k, v in vals.items()}
+
 def timeit(fn, reps=20):
     fn(); torch.cuda.synchronize()
     s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -70,3 +79,21 @@ for name, B, Hf, E, C, G in [("cfg1 B=1 256^2 E100 C64", 1, 256, 100, 64, 240), 
         fb = sum(nb for _, _, nb in frows)
         print(f"{name:26s} {'ALL fused, own B':19s} {f_us:9.1f} {fb / 1e6:9.2f} {fb / f_us / 1e3:9.1f} {fb / f_us / 1e3 / 8000 * 100:10.1f}%")
         print(f"{name:26s} {'ALL fused, 5-stage B':19s} {f_us:9.1f} {tot_b / 1e6:9.2f} {tot_b / f_us / 1e3:9.1f} {tot_b / f_us / 1e3 / 8000 * 100:10.1f}%")
+        # one-launch forms against the launches they replace, interleaved (profiles/bev_fuse_retrieve.txt): fuse (planes) + retrieve
+        # (LDS tiles) against map_fuse_retrieve; index + scatter+rotate against bev_project.  Medians of 7 rounds, [min, max].
+        gm_a, gm_b = torch.zeros(B, G, G, C, device="cuda"), torch.zeros(B, G, G, C, device="cuda")
+        def two_fr():
+            ops.map_fuse(rotp, gm_a, gps, masks, 0.12, planes=True)
+            return ops.map_retrieve(gm_a, gps, compass, E, 0.12)
+        def two_pr():
+            return ops.bev_scatter_rotate(feat, ops.bev_index(depth, Hf, Hf, E), compass, -1.0, C, E)
+        ab = ab_rounds([("fuse+retrieve, 2 calls", two_fr), ("map_fuse_retrieve", lambda: ops.map_fuse_retrieve(rotp, gm_b, gps, compass, masks, E, 0.12)),
+                        ("index+scatter_rotate", two_pr), ("bev_project", lambda: ops.bev_project(depth, feat, compass, -1.0, C, E, want_index=False))])
+        assert torch.equal(gm_a, gm_b)
+        fr_b = by["fuse"][1] + B * 2 * C * E * E * 4
+        for k, (med, lo, hi) in ab.items():
+            nb = fr_b if "retrieve" in k else by["scatter_max"][1] + by["index"][1]
+            print(f"{name:26s} A/B {k:24s} {med:9.1f} [{lo:7.1f}, {hi:7.1f}] {nb / med / 1e3 / 8000 * 100:6.1f}% of 8 TB/s")
+        op_old = ab["index+scatter_rotate"][0] + ab["fuse+retrieve, 2 calls"][0]
+        op_new = (ab["bev_project"][0] if B < 4 else ab["index+scatter_rotate"][0]) + ab["map_fuse_retrieve"][0]
+        print(f"{name:26s} A/B operator: launches replaced {op_old:9.1f} us, one-launch forms {op_new:9.1f} us")

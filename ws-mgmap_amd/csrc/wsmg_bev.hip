@@ -79,6 +79,12 @@ __device__ __forceinline__ int index_of(const IndexArgs& a, int b, unsigned p) {
   bool inr = (yg < Ef) && (yg >= 0.f) && (xg < Ef) && (xg >= 0.f);
   return (valid && inr) ? (int)yg * a.E + (int)xg : -1;
 }
+// the index row of sample b, computed where it is read (bev_project_kernel: no index launch in front of the scatter)
+struct DepthCells {
+  IndexArgs a;
+  int b;
+  __device__ __forceinline__ int operator[](int s) const { return index_of(a, b, (unsigned)s); }
+};
 __global__ __launch_bounds__(1024) void bev_index_compact_kernel(IndexArgs a, unsigned* __restrict__ clist, int* __restrict__ cnt) {
   __shared__ int lcount;
   const unsigned per = (unsigned)(a.Hf * a.Wf);
@@ -128,8 +134,12 @@ __device__ __forceinline__ float key2f(unsigned k) {
 // features are used, so that an index round trip is never exposed.
 // WU: window channels fetched together (the launcher picks the widest window of the geometry, up to 4; at Cf == C it is 1, and
 // the 40 VGPRs of that form keep two workgroups per CU at E = 100, which the 78 of WU = 4 do not).
-template <int WU>
-__device__ __forceinline__ void scatter_plane(const float* __restrict__ feat, const int32_t* __restrict__ lb, int b, int c, int Cf,
+// CELLS: lb[s] = cell of source s or -1 — the index launch's row (const int32_t*, passed __restrict__ as before) or DepthCells,
+// which derives it from the depth.
+template <class T> struct CellArg { using type = const T; };
+template <class T> struct CellArg<T*> { using type = T* __restrict__; };
+template <int WU, class CELLS>
+__device__ __forceinline__ void scatter_plane(const float* __restrict__ feat, typename CellArg<CELLS>::type lb, int b, int c, int Cf,
                                               int HW, int C, unsigned* tg, int tid) {
   const int ws = (int)(((int64_t)c * Cf) / C);
   const int we = (int)((((int64_t)(c + 1)) * Cf + C - 1) / C);
@@ -271,7 +281,7 @@ __global__ __launch_bounds__(1024) void bev_scatter_kernel(const float* __restri
   for (int g = 0; g < CG; ++g) {
     int c = c0 + g;
     if (c >= C) break;
-    scatter_plane<WU>(feat, lb, b, c, Cf, HW, C, tile + (size_t)g * E2, tid);
+    scatter_plane<WU, const int32_t*>(feat, lb, b, c, Cf, HW, C, tile + (size_t)g * E2, tid);
   }
   __syncthreads();
   for (int i = tid; i < CG * E2; i += 1024) {
@@ -313,11 +323,11 @@ struct Rot { float c, s; };
 
 // Block order of the gather kernels: hardware block b runs on XCD b % 8; logical block = a contiguous eighth of the grid per XCD,
 // so that output rows that share source rows (the +1 taps) meet in one L2 instead of fetching them into several.
-__device__ __forceinline__ int bev_block() {
-  const int nb = gridDim.x, bid = blockIdx.x;
+__device__ __forceinline__ int bev_block(int nb, int bid) {
   const int q = nb >> 3, r = nb & 7, x = bid & 7;
   return x * q + (x < r ? x : r) + (bid >> 3);
 }
+__device__ __forceinline__ int bev_block() { return bev_block((int)gridDim.x, (int)blockIdx.x); }
 
 // rotation of an E x E map: gx = bx*c + by*s ; gy = -bx*s + by*c
 __device__ __forceinline__ Taps rot_taps(int x, int y, int E, Rot r) {
@@ -335,12 +345,12 @@ __device__ __forceinline__ Taps rot_taps(int x, int y, int E, Rot r) {
 // not LDS or HBM time — every (pixel, channel) item recomputed the tap geometry with four IEEE divisions (base_coord: 2 / (W - 1)
 // and / W, twice) and an integer division p / E): the two base coordinates come from a table in the LDS left over beside the
 // plane (E floats, the same function's values: bit-identical), y = p / E is a multiply-high by a host-computed magic number.
-template <int WU>
-__global__ __launch_bounds__(1024) void bev_scatter_rotate_kernel(const float* __restrict__ feat, const int32_t* __restrict__ lin,
-                                                                  const float* __restrict__ heading, float sign, int Cf, int HW,
-                                                                  int C, int E, int CG, unsigned magicE, int table,
-                                                                  float* __restrict__ out, const unsigned* __restrict__ clist,
-                                                                  const int* __restrict__ cnt, int nblk) {
+template <int WU, class CELLS>
+__device__ __forceinline__ void scatter_rotate_block(const float* __restrict__ feat, typename CellArg<CELLS>::type lb,
+                                                     const float* __restrict__ heading,
+                                                     float sign, int Cf, int HW, int C, int E, int CG, unsigned magicE, int table,
+                                                     float* __restrict__ out, const unsigned* __restrict__ clist,
+                                                     const int* __restrict__ cnt, int nblk) {
   extern __shared__ unsigned tile[];
   const int b = blockIdx.y;
   const int c0 = blockIdx.x * CG;
@@ -351,12 +361,11 @@ __global__ __launch_bounds__(1024) void bev_scatter_rotate_kernel(const float* _
   if (table)
     for (int i = tid; i < E; i += 1024) bc[i] = base_coord(i, E);
   __syncthreads();
-  const int32_t* lb = lin + (size_t)b * HW;
   for (int g = 0; g < CG; ++g) {
     int c = c0 + g;
     if (c >= C) break;
     if (clist) scatter_plane_compact<WU>(feat, clist + (size_t)b * HW, cnt + (size_t)b * nblk, nblk, b, c, Cf, HW, C, tile + (size_t)g * E2, tid);
-    else scatter_plane<WU>(feat, lb, b, c, Cf, HW, C, tile + (size_t)g * E2, tid);
+    else scatter_plane<WU, CELLS>(feat, lb, b, c, Cf, HW, C, tile + (size_t)g * E2, tid);
   }
   __syncthreads();
   for (int i = tid; i < CG * E2; i += 1024) {   // keys -> the values bev_scatter_kernel writes, in place
@@ -392,6 +401,28 @@ __global__ __launch_bounds__(1024) void bev_scatter_rotate_kernel(const float* _
       ob[p] = v;
     }
   }
+}
+template <int WU>
+__global__ __launch_bounds__(1024) void bev_scatter_rotate_kernel(const float* __restrict__ feat, const int32_t* __restrict__ lin,
+                                                                  const float* __restrict__ heading, float sign, int Cf, int HW,
+                                                                  int C, int E, int CG, unsigned magicE, int table,
+                                                                  float* __restrict__ out, const unsigned* __restrict__ clist,
+                                                                  const int* __restrict__ cnt, int nblk) {
+  scatter_rotate_block<WU, const int32_t*>(feat, lin + (size_t)blockIdx.y * HW, heading, sign, Cf, HW, C, E, CG, magicE, table, out, clist, cnt, nblk);
+}
+
+// bev_index_kernel + bev_scatter_rotate_kernel in ONE launch, for the batches below 4 where the operator is launch latency and not
+// bandwidth: a plane workgroup derives every source's cell from the depth image itself (index_of: the index kernel's expressions) —
+// 256 KB per sample, re-read by the C / CG workgroups of the sample out of L2 — instead of waiting for an index launch.  The first
+// workgroup of a sample also writes the index row when the caller wants it.  Same cells, same scatter, same rotation: same bits.
+template <int WU>
+__global__ __launch_bounds__(1024) void bev_project_kernel(const float* __restrict__ feat, IndexArgs ia, const float* __restrict__ heading,
+                                                           float sign, int Cf, int C, int CG, unsigned magicE, int table,
+                                                           float* __restrict__ out) {
+  const int b = blockIdx.y, HW = ia.Hf * ia.Wf;
+  if (ia.lin && blockIdx.x == 0)
+    for (int s = threadIdx.x; s < HW; s += 1024) ia.lin[(size_t)b * HW + s] = index_of(ia, b, (unsigned)s);
+  scatter_rotate_block<WU, DepthCells>(feat, DepthCells{ia, b}, heading, sign, Cf, HW, C, ia.E, CG, magicE, table, out, nullptr, nullptr, 0);
 }
 
 // first rotation: NCHW planes in (scatter output), NHWC out through an LDS transpose
@@ -544,21 +575,49 @@ __global__ __launch_bounds__(256) void map_fuse_kernel(const float* __restrict__
 // then gathers out of it — 65 KB per workgroup, two workgroups per CU, load and compute phases that could not overlap: 334 us at
 // cfg4 against 144 us of map_fuse_kernel.)
 constexpr int FP = 64;
-__global__ __launch_bounds__(256) void map_fuse_planes_kernel(const float* __restrict__ ego, float* __restrict__ gm,
-                                                              const float* __restrict__ gps, MapArgs a, int tiles_x) {
+// where the paste of a sample lands: the translation of the fuse and the origin of its (E+4)^2 window in the global map
+struct FuseGeo { float tx, ty; int wy0, wx0; };
+__device__ __forceinline__ FuseGeo fuse_geo(Pose ps, const MapArgs& a) {
+  FuseGeo f;
+  f.tx = -(ps.gy - a.halfG) / a.halfG;
+  f.ty = -(ps.gx - a.halfG) / a.halfG;
+  f.wy0 = a.lo + (int)(ps.gx - a.halfG) - 2;
+  f.wx0 = a.lo + (int)(ps.gy - a.halfG) - 2;
+  return f;
+}
+// the four taps of the translated paste at global-map pixel (Y, X): offset into an E x E plane (-1: zero padding of grid_sample or
+// the zero border of the agent view around the paste) and weight, in k order
+struct PasteTaps { int off[4]; float w[4]; };
+__device__ __forceinline__ PasteTaps paste_taps(int X, int Y, bool pok, float tx, float ty, const MapArgs& a) {
+  const int hi = a.lo + a.E;
+  float gx = base_coord(pok ? X : 0, a.G) + tx;
+  float gy = base_coord(Y, a.G) + ty;
+  Taps tp = make_taps(unnorm(gx, a.G), unnorm(gy, a.G));
+  PasteTaps r;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int yy = tp.y0 + (k >> 1), xx = tp.x0 + (k & 1);
+    r.w[k] = k == 0 ? tp.w00 : k == 1 ? tp.w01 : k == 2 ? tp.w10 : tp.w11;
+    const bool ok = pok && yy >= a.lo && yy < hi && xx >= a.lo && xx < hi && yy < a.G && xx < a.G;
+    r.off[k] = ok ? (yy - a.lo) * a.E + (xx - a.lo) : -1;
+  }
+  return r;
+}
+// RESET: the episode reset of the window's pixels rides in the read-modify-write (g * m before the max, as map_reset_kernel then
+// this kernel leave it) — map_fuse_retrieve_kernel, where no reset launch runs in front
+template <bool RESET>
+__device__ __forceinline__ void fuse_planes_block(const float* __restrict__ ego, float* __restrict__ gm, const float* __restrict__ gps,
+                                                  const MapArgs& a, int tiles_x, int blk, int b, float m) {
   extern __shared__ float tl[];           // [FP][C + 1]... pitch C + 4 keeps the 16-byte reads aligned
-  const int b = blockIdx.y;
-  const int wy = blockIdx.x / tiles_x, tx_ = blockIdx.x - wy * tiles_x;
+  const int wy = blk / tiles_x, tx_ = blk - wy * tiles_x;
   const int WN = a.E + 4;
   Pose ps = grid_cell(gps, b, a.G, a.cmax, a.cmin, a.gsz);
-  const float tx = -(ps.gy - a.halfG) / a.halfG;
-  const float ty = -(ps.gx - a.halfG) / a.halfG;
-  const int wy0 = a.lo + (int)(ps.gx - a.halfG) - 2;
-  const int wx0 = a.lo + (int)(ps.gy - a.halfG) - 2;
+  const FuseGeo fg = fuse_geo(ps, a);
+  const float tx = fg.tx, ty = fg.ty;
+  const int wy0 = fg.wy0, wx0 = fg.wx0;
   const int C4 = a.C >> 2;
   const int E2 = a.E * a.E;
   const int pitch = a.C + 4;
-  const int hi = a.lo + a.E;
   const int Y = wy0 + wy;
   if (Y < 0 || Y >= a.G) return;          // (whole workgroup: the row is outside the global map)
   const float* eb = ego + (size_t)b * a.C * E2;
@@ -567,19 +626,9 @@ __global__ __launch_bounds__(256) void map_fuse_planes_kernel(const float* __res
     const int p = threadIdx.x & (FP - 1), cq = threadIdx.x >> 6;     // pixel of the tile, channel phase (256 / FP = 4)
     const int wx = tx_ * FP + p, X = wx0 + wx;
     const bool pok = wx < WN && X >= 0 && X < a.G;
-    float gx = base_coord(pok ? X : 0, a.G) + tx;
-    float gy = base_coord(Y, a.G) + ty;
-    Taps tp = make_taps(unnorm(gx, a.G), unnorm(gy, a.G));
-    int off[4];
-    float w[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int yy = tp.y0 + (k >> 1), xx = tp.x0 + (k & 1);
-      w[k] = k == 0 ? tp.w00 : k == 1 ? tp.w01 : k == 2 ? tp.w10 : tp.w11;
-      // zero padding of grid_sample, then the zero border of the agent view around the paste
-      const bool ok = pok && yy >= a.lo && yy < hi && xx >= a.lo && xx < hi && yy < a.G && xx < a.G;
-      off[k] = ok ? (yy - a.lo) * a.E + (xx - a.lo) : -1;
-    }
+    const PasteTaps pt = paste_taps(X, Y, pok, tx, ty, a);
+    const int* off = pt.off;
+    const float* w = pt.w;
     constexpr int U = 4;
     for (int c0 = cq; c0 < a.C; c0 += 4 * U) {
       float q[U][4];
@@ -626,11 +675,19 @@ __global__ __launch_bounds__(256) void map_fuse_planes_kernel(const float* __res
       if (!ok[u]) continue;
       const f32x4 v = *reinterpret_cast<const f32x4*>(tl + li[u]);
       f32x4 gg = g[u];
+      if (RESET && m != 1.0f) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) gg[j] *= m;
+      }
 #pragma unroll
       for (int j = 0; j < 4; ++j) gg[j] = v[j] > gg[j] ? v[j] : gg[j];
       gb[o[u]] = gg;
     }
   }
+}
+__global__ __launch_bounds__(256) void map_fuse_planes_kernel(const float* __restrict__ ego, float* __restrict__ gm,
+                                                              const float* __restrict__ gps, MapArgs a, int tiles_x) {
+  fuse_planes_block<false>(ego, gm, gps, a, tiles_x, (int)blockIdx.x, (int)blockIdx.y, 1.0f);
 }
 
 // translate the global map back to the agent and crop the centre E x E (NHWC scratch)
@@ -711,9 +768,48 @@ __device__ __forceinline__ f32x4 retrieve_item_regs(const f32x4* __restrict__ gb
   return v;
 }
 
+// One f32x4 of the global map as this step's fuse leaves it, from the value `g` read before or after the fuse stored it (see
+// map_fuse_retrieve_kernel): reset, then max with the translated paste inside the sample's window — the expressions of
+// map_reset_kernel and map_fuse_planes_kernel.  The rare route's form: 16 plane loads per call.  A tile takes that route only when a
+// gps coordinate is not finite (a finite pose's box always fits RBOX): an infinite one puts every tap outside the map and this is not
+// called; a NaN one lands the taps on rows / columns 0 and 1 with NaN weights, so this runs (inside the window when G - E < 8) but the
+// ego map is NaN whatever it returns.  Its values are therefore not observable through the ego map; the test
+// (test_fuse_retrieve_rare_route_with_a_non_finite_gps) holds the route to the two launches' NaN pattern, zeros and global map.
+__device__ __noinline__ f32x4 fuse_quad(f32x4 g, const float* __restrict__ eb, const MapArgs& a, const FuseGeo& fg, float m, int Y, int X,
+                                        int c) {
+  if (m != 1.0f) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) g[j] *= m;
+  }
+  const unsigned WN = (unsigned)(a.E + 4);
+  if ((unsigned)Y - (unsigned)fg.wy0 >= WN || (unsigned)X - (unsigned)fg.wx0 >= WN) return g;
+  const PasteTaps pt = paste_taps(X, Y, true, fg.tx, fg.ty, a);
+  const int E2 = a.E * a.E;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    float v = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (pt.off[k] >= 0) v += eb[(size_t)(4 * c + j) * E2 + pt.off[k]] * pt.w[k];
+    g[j] = v > g[j] ? v : g[j];
+  }
+  return g;
+}
+
 // the same value, one rotation tap at a time (4 loads in flight instead of 16: the tiled kernel's rare route, few registers)
+// MAPV: what a loaded global-map value stands for — itself (AsStored: no state, no argument registers) or this step's fuse of it
+struct AsStored {
+  __device__ __forceinline__ f32x4 operator()(f32x4 q, const MapArgs&, int, int, int) const { return q; }
+};
+struct AsFused {
+  const float* eb;      // the sample's rotated planes
+  FuseGeo fg;
+  float m;
+  __device__ __forceinline__ f32x4 operator()(f32x4 q, const MapArgs& a, int Y, int X, int c) const { return fuse_quad(q, eb, a, fg, m, Y, X, c); }
+};
+template <class MAPV>
 __device__ __noinline__ f32x4 retrieve_item_seq(const f32x4* __restrict__ gb, const MapArgs& a, float tx, float ty, Rot r, int x, int y,
-                                                int c) {
+                                                int c, MAPV mapv) {
   const int C4 = a.C >> 2, E = a.E;
   const Taps rt = rot_taps(x, y, E, r);
   f32x4 v = {0.f, 0.f, 0.f, 0.f};
@@ -730,7 +826,7 @@ __device__ __noinline__ f32x4 retrieve_item_seq(const f32x4* __restrict__ gb, co
       const int yy = tp.y0 + (m >> 1), xx = tp.x0 + (m & 1);
       const float w = m == 0 ? tp.w00 : m == 1 ? tp.w01 : m == 2 ? tp.w10 : tp.w11;
       if (yy >= 0 && yy < a.G && xx >= 0 && xx < a.G) {
-        const f32x4 q = gb[((size_t)yy * a.G + xx) * C4 + c];
+        const f32x4 q = mapv(gb[((size_t)yy * a.G + xx) * C4 + c], a, yy, xx, c);
 #pragma unroll
         for (int j = 0; j < 4; ++j) cv[j] += q[j] * w;
       }
@@ -809,10 +905,15 @@ __device__ __forceinline__ int quad_get(int v) { return __builtin_amdgcn_update_
 template <int K>
 __device__ __forceinline__ float quad_getf(float v) { return __int_as_float(quad_get<K>(__float_as_int(v))); }
 
-__global__ __launch_bounds__(256, 4) void map_retrieve_tiled_kernel(const float* __restrict__ gm, const float* __restrict__ gps,
-                                                                 const float* __restrict__ heading, MapArgs a, int tiles_x,
-                                                                 int nsplit, int S4, unsigned magicS4, float* __restrict__ out,
-                                                                 unsigned* __restrict__ trace) {
+// FUSE (map_fuse_retrieve_kernel): the box holds the map AS THIS STEP'S FUSE LEAVES IT — every staged value is reset (g * m) on
+// its way into LDS, and box pixel p < 196 then belongs to thread p, which max-fuses the translated paste of its pixel into the
+// slice's channels in place (the taps once per pixel; per channel four 4-byte plane loads that run along a plane row across the
+// lanes of a box row) when the pixel lies inside the sample's window.  gm is only read.  `blk`: the tile-and-slice number.
+template <bool FUSE>
+__device__ __forceinline__ void retrieve_tile(const float* __restrict__ gm, const float* __restrict__ gps,
+                                              const float* __restrict__ heading, const MapArgs& a, int tiles_x, int nsplit, int S4,
+                                              unsigned magicS4, float* __restrict__ out, unsigned* __restrict__ trace, int blk, int b,
+                                              const float* __restrict__ ego, float m) {
   extern __shared__ float boxf[];  // [bh][bw][4 S4] floats: the box; then bw + 2 pixels of zeros
   __shared__ int s_ext[16][4];
   // diagnostic build (`tracing` in the launcher): cycles of every 64th workgroup at its phase boundaries
@@ -820,14 +921,15 @@ __global__ __launch_bounds__(256, 4) void map_retrieve_tiled_kernel(const float*
   unsigned* const trw = trace + (blockIdx.x >> 6) * 8;
   const unsigned long long t00 = tr ? __builtin_readcyclecounter() : 0;
 #define RTRACE(i) if (tr) trw[i] = (unsigned)(__builtin_readcyclecounter() - t00)
-  const int b = blockIdx.y, tid = threadIdx.x;
-  const int blk = bev_block();
+  const int tid = threadIdx.x;
   const int tile = blk / nsplit, cs0 = (blk - tile * nsplit) * S4;   // first f32x4 of this workgroup's channel slice
   const int tyi = tile / tiles_x, txi = tile - tyi * tiles_x;
   Pose ps = grid_cell(gps, b, a.G, a.cmax, a.cmin, a.gsz);
   const float tx = (ps.gy - a.halfG) / a.halfG;
   const float ty = (ps.gx - a.halfG) / a.halfG;
   const int C4 = a.C >> 2, E = a.E, G = a.G;
+  const FuseGeo fg = FUSE ? fuse_geo(ps, a) : FuseGeo{0.f, 0.f, 0, 0};
+  const float* eb = FUSE ? ego + (size_t)b * a.C * E * E : nullptr;
   const f32x4* gb = reinterpret_cast<const f32x4*>(gm + (size_t)b * G * G * a.C);
   f32x4* ob = reinterpret_cast<f32x4*>(out + (size_t)b * E * E * a.C);
   f32x4* box = reinterpret_cast<f32x4*>(boxf);
@@ -876,7 +978,10 @@ __global__ __launch_bounds__(256, 4) void map_retrieve_tiled_kernel(const float*
     for (int i = tid; i < RT * RT * S4; i += 256) {
       const int pl = (int)__umulhi((unsigned)i, magicS4), c = cs0 + i - pl * S4;
       const int qy = tyi * RT + (pl >> 3), qx = txi * RT + (pl & 7);
-      if (qy < E && qx < E) ob[((size_t)qy * E + qx) * C4 + c] = retrieve_item_seq(gb, a, tx, ty, r, qx, qy, c);
+      if (qy < E && qx < E) {
+        if constexpr (FUSE) ob[((size_t)qy * E + qx) * C4 + c] = retrieve_item_seq(gb, a, tx, ty, r, qx, qy, c, AsFused{eb, fg, m});
+        else ob[((size_t)qy * E + qx) * C4 + c] = retrieve_item_seq(gb, a, tx, ty, r, qx, qy, c, AsStored{});
+      }
     }
     return;
   }
@@ -907,6 +1012,12 @@ __global__ __launch_bounds__(256, 4) void map_retrieve_tiled_kernel(const float*
         ok[u] = i < nbox && yy >= 0 && yy < G && xx >= 0 && xx < G;
         q[u] = gb[ok[u] ? ((size_t)yy * G + xx) * C4 + cs0 + c : (size_t)0];
       }
+      if (FUSE && m != 1.0f) {
+#pragma unroll
+        for (int u = 0; u < UB; ++u)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) q[u][j] *= m;
+      }
 #pragma unroll
       for (int u = 0; u < UB; ++u) {
         const f32x4 z = {0.f, 0.f, 0.f, 0.f};
@@ -917,6 +1028,39 @@ __global__ __launch_bounds__(256, 4) void map_retrieve_tiled_kernel(const float*
   RTRACE(2);
   __syncthreads();
   RTRACE(3);
+  if constexpr (FUSE) {
+    if (tid < bh * bw) {
+      const int row = tid / bw, px = tid - row * bw;
+      const int Y = gy_lo + row, X = gx_lo + px;
+      const unsigned WN = (unsigned)(E + 4);
+      // a pixel outside the window is not the fuse's: its map value stays (a paste value of 0 there would still beat a negative one)
+      const bool inw = Y >= 0 && Y < G && X >= 0 && X < G && (unsigned)Y - (unsigned)fg.wy0 < WN && (unsigned)X - (unsigned)fg.wx0 < WN;
+      if (inw) {
+        const PasteTaps pt = paste_taps(X, Y, true, fg.tx, fg.ty, a);
+        const float* ep = eb + (size_t)(4 * cs0) * (E * E);
+        f32x4* const bp = box + tid * S4;
+#pragma unroll 2
+        for (int c = 0; c < S4; ++c) {
+          float pq[4][4];
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) pq[j][k] = pt.off[k] >= 0 ? ep[(size_t)(4 * c + j) * (E * E) + pt.off[k]] : 0.f;
+          f32x4 g = bp[c];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            float v = 0.f;
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+              if (pt.off[k] >= 0) v += pq[j][k] * pt.w[k];
+            g[j] = v > g[j] ? v : g[j];
+          }
+          bp[c] = g;
+        }
+      }
+    }
+    __syncthreads();
+  }
   // ---- thread = (its record's pixel, channel groups tid % 4, + 4, ...): the pixel's four records come from the quad (DPP, as
   // they are used: held for the whole loop they cost 24 registers and the kernel its fourth workgroup per CU)
   const int dn = bw * S4;
@@ -944,6 +1088,84 @@ __global__ __launch_bounds__(256, 4) void map_retrieve_tiled_kernel(const float*
   }
   RTRACE(4);
 #undef RTRACE
+}
+__global__ __launch_bounds__(256, 4) void map_retrieve_tiled_kernel(const float* __restrict__ gm, const float* __restrict__ gps,
+                                                                 const float* __restrict__ heading, MapArgs a, int tiles_x,
+                                                                 int nsplit, int S4, unsigned magicS4, float* __restrict__ out,
+                                                                 unsigned* __restrict__ trace) {
+  retrieve_tile<false>(gm, gps, heading, a, tiles_x, nsplit, S4, magicS4, out, trace, bev_block(), (int)blockIdx.y, nullptr, 1.0f);
+}
+
+// Episode reset of what the fuse window does not cover: global[b] *= m outside the sample's (E+4)^2 window (whose pixels the fuse
+// workgroups reset as they read-modify-write them).  Nothing to do for m == 1.
+constexpr int ZU = 4;
+__device__ __forceinline__ void reset_rest_block(float* __restrict__ gm, const float* __restrict__ gps, const MapArgs& a, int blk, int nblk,
+                                                 int b, float m) {
+  if (m == 1.0f) return;
+  const FuseGeo fg = fuse_geo(grid_cell(gps, b, a.G, a.cmax, a.cmin, a.gsz), a);
+  const int C4 = a.C >> 2;
+  const unsigned WN = (unsigned)(a.E + 4);
+  const int64_t n4 = (int64_t)a.G * a.G * C4;
+  f32x4* g = reinterpret_cast<f32x4*>(gm) + (size_t)b * n4;
+  // ZU elements a stride apart per trip, their loads all before their stores: a quarter of the workgroups (which every sample
+  // launches and a sample that is not reset only exits) keeps the loads in flight of four times as many
+  const int64_t stride = (int64_t)nblk * 256;
+  for (int64_t i0 = (int64_t)blk * 256 + threadIdx.x; i0 < n4; i0 += ZU * stride) {
+    f32x4 v[ZU];
+    bool own[ZU];
+#pragma unroll
+    for (int u = 0; u < ZU; ++u) {
+      const int64_t i = i0 + u * stride;
+      own[u] = false;
+      if (i < n4) {
+        const int p = (int)(i / C4), Y = p / a.G, X = p - Y * a.G;
+        own[u] = !((unsigned)Y - (unsigned)fg.wy0 < WN && (unsigned)X - (unsigned)fg.wx0 < WN);
+      }
+      if (own[u]) v[u] = g[i];
+    }
+#pragma unroll
+    for (int u = 0; u < ZU; ++u) {
+      if (!own[u]) continue;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[u][j] *= m;
+      g[i0 + u * stride] = v[u];
+    }
+  }
+}
+
+// map_reset_kernel + map_fuse_planes_kernel + map_retrieve_tiled_kernel in ONE launch: three kinds of workgroup by blockIdx.x.
+//   [0, nR)            retrieve_tile<true>: the retrieval.  They only READ the global map, and fuse what they read on the way into
+//                      LDS, so that the values under the taps are this step's whatever the stores of the others have done yet.
+//   [nR, nR + nF)      fuse_planes_block<true>: the fuse, with the reset of the window's pixels in its read-modify-write.
+//   [nR + nF, ...)     reset_rest_block: the reset of the rest of the sample's map (only for a sample whose mask is not 1).
+// OWNERSHIP.  Every element of the global map has ONE writer in this launch, and it is written at most once: an element inside
+// the sample's window by the fuse workgroup of its window row and 64-pixel run, an element outside it by the reset workgroup whose
+// grid-stride loop reaches it; retrieval workgroups never write the map.  No workgroup waits for another (no barrier across
+// workgroups, no spin): the launch cannot hang on residency.
+// THE HAZARD.  A retrieval workgroup may read an element before or after its owner's store.  Every read of the map is an aligned
+// vector load whose dwords are each read once and whole, so each float it sees is either the value g before the step or the
+// owner's result F(g) — and the reader applies F itself:  F(x) = max'(x * m, p), with x * m skipped when m == 1 (as
+// map_reset_kernel skips it), p the translated paste (the same expressions and plane loads as the owner's, so the same bits) and
+// max'(x, p) = p > x ? p : x; outside the window F(x) = x * m.  It needs F(F(g)) == F(g) bit for bit, which holds for masks in
+// {0, 1} and a finite paste:
+//   m == 1:  F(g) is g or p.  p > p is false and p > g was false where g stayed: F(F(g)) == F(g).  NaN: p > NaN and NaN > x are
+//            false, so a NaN in the map stays and a NaN paste never enters — both times.
+//   m == 0:  x * 0 is +0, -0 (x negative or -0) or NaN (x infinite / NaN).  F(g) is p (then p > +-0, so p > 0 is finite and
+//            p * 0 == +0, p > +0: p again) or g * 0 (a zero keeps its sign under * 0, NaN stays NaN, and the comparison with p
+//            comes out as before: +0 == -0 compare equal).  The -0 case: g = -3, m = 0, p = +0 gives -0 both times, never +0.
+// A mask that is neither 0 nor 1 scales twice where a reader comes second, and an infinite paste turns to NaN under * 0: both are
+// outside the contract (masks are the reference's not-done flags; features are finite).  tests: test_gpu_map_fuse_retrieve.py (signed
+// zeros, negative features), test_map_fuse_retrieve_cpu.py (the same property on the oracle).
+__global__ __launch_bounds__(256, 4) void map_fuse_retrieve_kernel(const float* __restrict__ ego, float* __restrict__ gm,
+                                                                 const float* __restrict__ gps, const float* __restrict__ heading,
+                                                                 const float* __restrict__ masks, MapArgs a, int tiles_x, int nsplit,
+                                                                 int S4, unsigned magicS4, int nR, int ftiles_x, int nF, int nZ,
+                                                                 float* __restrict__ out) {
+  const int b = blockIdx.y, bid = blockIdx.x;
+  const float m = masks[b];
+  if (bid < nR) retrieve_tile<true>(gm, gps, heading, a, tiles_x, nsplit, S4, magicS4, out, nullptr, bev_block(nR, bid), b, ego, m);
+  else if (bid < nR + nF) fuse_planes_block<true>(ego, gm, gps, a, ftiles_x, bid - nR, b, m);
+  else reset_rest_block(gm, gps, a, bid - nR - nF, nZ, b, m);
 }
 
 MapArgs map_args(int B, int C, int E, int G, float resolution) {
@@ -982,11 +1204,9 @@ int sgrid(int64_t n, int cap = 4096) {
   return (int)g;
 }
 
-}  // namespace
-
-extern "C" int wsmg_bev_index(const float* depth, int B, int Hd, int Wd, float depth_scale, int Hf, int Wf, int E,
-                              float local_scale, int32_t* lin_idx, wsmg_stream_t stream) {
-  if (B <= 0 || Hd <= 0 || Wd <= 0 || Hf <= 0 || Wf <= 0 || E <= 0 || Hf > Hd || Wf > Wd) return WSMG_EINVAL;
+// the index kernels' arguments (wsmg_bev_index, wsmg_bev_index_compact, wsmg_bev_project: one set of camera constants)
+IndexArgs index_args(const float* depth, int B, int Hd, int Wd, float depth_scale, int Hf, int Wf, int E, float local_scale,
+                     int32_t* lin_idx) {
   IndexArgs a;
   a.depth = depth; a.lin = lin_idx;
   a.B = B; a.Hd = Hd; a.Wd = Wd; a.Hf = Hf; a.Wf = Wf; a.E = E;
@@ -998,6 +1218,29 @@ extern "C" int wsmg_bev_index(const float* depth, int B, int Hd, int Wd, float d
   a.cx = (float)(Hd / 2.0); a.cy = (float)(Wd / 2.0);
   a.fx = (float)((Hd / 2.0) / tn); a.fy = (float)((Wd / 2.0) / tn);
   a.K = (float)((double)Wd / (double)Wf);
+  return a;
+}
+
+// how the scatter + rotation launches lay out their planes (bev_scatter_rotate_impl, wsmg_bev_project: the same grouping, table and
+// magic number, or the two would not give the same bits)
+struct PlaneLaunch { int CG, table; size_t lds; unsigned magicE; };
+PlaneLaunch plane_launch(int B, int C, int E) {
+  const size_t plane = (size_t)E * E * sizeof(unsigned);
+  PlaneLaunch p;
+  p.CG = (2 * plane <= 80 * 1024 && (int64_t)B * C >= 1024) ? 2 : 1;
+  // the base-coordinate table rides in whatever LDS the planes leave (E = 200: 3 840 spare bytes of the 160 KB, 800 needed)
+  p.table = plane * p.CG + (size_t)E * sizeof(float) <= 160 * 1024 ? 1 : 0;
+  p.lds = plane * p.CG + (p.table ? (size_t)E * sizeof(float) : 0);
+  p.magicE = (unsigned)((1ull << 32) / (unsigned)E + 1);      // p / E == umulhi(p, magicE) for p < E * E <= 40 960
+  return p;
+}
+
+}  // namespace
+
+extern "C" int wsmg_bev_index(const float* depth, int B, int Hd, int Wd, float depth_scale, int Hf, int Wf, int E,
+                              float local_scale, int32_t* lin_idx, wsmg_stream_t stream) {
+  if (B <= 0 || Hd <= 0 || Wd <= 0 || Hf <= 0 || Wf <= 0 || E <= 0 || Hf > Hd || Wf > Wd) return WSMG_EINVAL;
+  const IndexArgs a = index_args(depth, B, Hd, Wd, depth_scale, Hf, Wf, E, local_scale, lin_idx);
   if (B > 65535 || (int64_t)Hf * Wf >= (1ll << 31)) return WSMG_EINVAL;
   hipLaunchKernelGGL(bev_index_kernel, dim3(sgrid((int64_t)Hf * Wf, 1024), (unsigned)B), dim3(256), 0, wsmg_s(stream), a);
   WSMG_RETURN_LAUNCH();
@@ -1009,16 +1252,7 @@ extern "C" int wsmg_bev_index_compact(const float* depth, int B, int Hd, int Wd,
                                       float local_scale, int32_t* lin_idx, uint32_t* clist, int32_t* cnt, wsmg_stream_t stream) {
   if (B <= 0 || Hd <= 0 || Wd <= 0 || Hf <= 0 || Wf <= 0 || E <= 0 || Hf > Hd || Wf > Wd || B > 65535) return WSMG_EINVAL;
   if (!compact_fits(Hf, Wf, E) || !clist || !cnt || !lin_idx) return WSMG_EINVAL;
-  IndexArgs a;
-  a.depth = depth; a.lin = lin_idx;
-  a.B = B; a.Hd = Hd; a.Wd = Wd; a.Hf = Hf; a.Wf = Wf; a.E = E;
-  a.depth_scale = depth_scale;
-  a.local_scale = local_scale;
-  a.half = (float)((E - 1) / 2.0);
-  const double tn = tan(45.0 * 3.14159265358979323846 / 180.0);
-  a.cx = (float)(Hd / 2.0); a.cy = (float)(Wd / 2.0);
-  a.fx = (float)((Hd / 2.0) / tn); a.fy = (float)((Wd / 2.0) / tn);
-  a.K = (float)((double)Wd / (double)Wf);
+  const IndexArgs a = index_args(depth, B, Hd, Wd, depth_scale, Hf, Wf, E, local_scale, lin_idx);
   hipLaunchKernelGGL(bev_index_compact_kernel, dim3((unsigned)wsmg_cdiv((int64_t)Hf * Wf, CB), (unsigned)B), dim3(1024), 0, wsmg_s(stream), a,
                      clist, cnt);
   WSMG_RETURN_LAUNCH();
@@ -1079,13 +1313,12 @@ static int bev_scatter_rotate_impl(const float* feat, const int32_t* lin_idx, co
   const int E2 = E * E;
   const size_t plane = (size_t)E2 * sizeof(unsigned);
   if (plane > 160 * 1024) return WSMG_EINVAL;
-  int CG = (2 * plane <= 80 * 1024 && (int64_t)B * C >= 1024) ? 2 : 1;
+  const PlaneLaunch pl = plane_launch(B, C, E);
+  const int CG = pl.CG, table = pl.table;
+  const size_t lds = pl.lds;
+  const unsigned magicE = pl.magicE;
   dim3 grid((unsigned)wsmg_cdiv(C, CG), (unsigned)B);
   const int wu = scatter_window(Cf, C);
-  // the base-coordinate table rides in whatever LDS the planes leave (E = 200: 3 840 spare bytes of the 160 KB, 800 needed)
-  const int table = plane * CG + (size_t)E * sizeof(float) <= 160 * 1024 ? 1 : 0;
-  const size_t lds = plane * CG + (table ? (size_t)E * sizeof(float) : 0);
-  const unsigned magicE = (unsigned)((1ull << 32) / (unsigned)E + 1);      // p / E == umulhi(p, magicE) for p < E * E <= 40 960
 #define WSMG_SCATTER(WU_)                                                                                                          \
   {                                                                                                                                \
     static bool attr_set = false;                                                                                                  \
@@ -1112,6 +1345,38 @@ extern "C" int wsmg_bev_scatter_rotate_compact(const float* feat, const uint32_t
                                                int B, int Cf, int Hf, int Wf, int C, int E, float* out_planes, wsmg_stream_t stream) {
   if (!clist || !cnt) return WSMG_EINVAL;
   return bev_scatter_rotate_impl(feat, nullptr, clist, cnt, heading, sign, B, Cf, Hf, Wf, C, E, out_planes, stream);
+}
+
+// wsmg_bev_index + wsmg_bev_scatter_rotate in one launch (bev_project_kernel); lin_idx may be NULL
+extern "C" int wsmg_bev_project(const float* depth, const float* feat, const float* heading, float sign, int B, int Hd, int Wd,
+                                float depth_scale, int Cf, int Hf, int Wf, int C, int E, float local_scale, int32_t* lin_idx,
+                                float* out_planes, wsmg_stream_t stream) {
+  if (B <= 0 || Hd <= 0 || Wd <= 0 || Hf <= 0 || Wf <= 0 || Hf > Hd || Wf > Wd || (int64_t)Hf * Wf >= (1ll << 31)) return WSMG_EINVAL;
+  if (Cf <= 0 || C <= 0 || C > Cf || E <= 1 || B > 65535) return WSMG_EINVAL;
+  const size_t plane = (size_t)E * E * sizeof(unsigned);
+  if (plane > 160 * 1024) return WSMG_EINVAL;
+  const IndexArgs a = index_args(depth, B, Hd, Wd, depth_scale, Hf, Wf, E, local_scale, lin_idx);
+  const PlaneLaunch pl = plane_launch(B, C, E);
+  const int CG = pl.CG, table = pl.table;
+  const size_t lds = pl.lds;
+  const unsigned magicE = pl.magicE;
+  dim3 grid((unsigned)wsmg_cdiv(C, CG), (unsigned)B);
+  const int wu = scatter_window(Cf, C);
+#define WSMG_PROJECT(WU_)                                                                                                          \
+  {                                                                                                                                \
+    static bool attr_set = false;                                                                                                  \
+    if (!attr_set) {                                                                                                               \
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(bev_project_kernel<WU_>),                                    \
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                                  \
+      if (e != hipSuccess) return (int)e;                                                                                          \
+      attr_set = true;                                                                                                             \
+    }                                                                                                                              \
+    hipLaunchKernelGGL(bev_project_kernel<WU_>, grid, dim3(1024), lds, wsmg_s(stream), feat, a, heading, sign, Cf, C, CG, magicE,   \
+                       table, out_planes);                                                                                         \
+  }
+  if (wu == 1) WSMG_PROJECT(1) else if (wu == 2) WSMG_PROJECT(2) else if (wu == 3) WSMG_PROJECT(3) else WSMG_PROJECT(4)
+#undef WSMG_PROJECT
+  WSMG_RETURN_LAUNCH();
 }
 
 extern "C" int wsmg_map_fuse_planes(const float* ego_rot_planes, float* global_map, const float* gps, const float* masks, int B,
@@ -1174,6 +1439,28 @@ extern "C" int wsmg_map_retrieve_tiled(const float* global_map, const float* gps
                       "issued %.0f, box in LDS %.0f, end %.0f\n", n, m[0], m[1], m[2], m[3], m[4]);
     }
   }
+  WSMG_RETURN_LAUNCH();
+}
+
+// wsmg_map_fuse_planes + wsmg_map_retrieve_tiled in one launch (map_fuse_retrieve_kernel has the ownership rule and why a read
+// that races its owner's store is admissible); bit-identical to the two for masks in {0, 1} and finite features
+extern "C" int wsmg_map_fuse_retrieve(const float* ego_rot_planes, float* global_map, const float* gps, const float* compass,
+                                      const float* masks, int B, int C, int E, int G, float resolution, float* out,
+                                      wsmg_stream_t stream) {
+  if (B <= 0 || C <= 0 || C % 4 || C > 64 || E <= 1 || G < E || B > 65535 || (size_t)E * E * 4 > 160 * 1024) return WSMG_EINVAL;
+  const int nsplit = retrieve_slices(C);
+  if (nsplit <= 0) return WSMG_EINVAL;
+  const int S4 = C / 4 / nsplit;
+  const size_t lds_r = (size_t)(RBOX * RBOX + RBOX + 2) * S4 * 16, lds_f = (size_t)FP * (C + 4) * sizeof(float);
+  MapArgs a = map_args(B, C, E, G, resolution);
+  const int tiles = (E + RT - 1) / RT;
+  const unsigned magic = 0xFFFFFFFFu / (unsigned)S4 + 1u;
+  const int nR = tiles * tiles * nsplit;                       // E <= 202: < 2^31
+  const int ftiles_x = wsmg_cdiv(E + 4, FP), nF = ftiles_x * (E + 4);
+  const int nZ = sgrid(wsmg_cdiv((int64_t)G * G * C / 4, ZU), 64);         // reset workgroups: ZU elements per thread and trip
+  hipLaunchKernelGGL(map_fuse_retrieve_kernel, dim3((unsigned)(nR + nF + nZ), (unsigned)B), dim3(256), lds_r > lds_f ? lds_r : lds_f,
+                     wsmg_s(stream), ego_rot_planes, global_map, gps, compass, masks, a, tiles, nsplit, S4, magic, nR, ftiles_x, nF, nZ,
+                     out);
   WSMG_RETURN_LAUNCH();
 }
 

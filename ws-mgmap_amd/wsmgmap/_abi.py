@@ -182,6 +182,8 @@ _SIG["wsmg_conv2d_fwd_bf16_ex"] = [c_p] * 4 + [c_i, c_p, c_i, c_i] + [c_i] * 11 
 _SIG["wsmg_bev_index_compact"] = [c_p, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p]
 _SIG["wsmg_bev_scatter_rotate_compact"] = [c_p, c_p, c_p, c_p, c_f] + [c_i] * 6 + [c_p, c_p]
 _SIG["wsmg_colsum_multi"] = [c_p, c_i, c_p]
+_SIG["wsmg_map_fuse_retrieve"] = [c_p] * 5 + [c_i] * 4 + [c_f, c_p, c_p]
+_SIG["wsmg_bev_project"] = [c_p, c_p, c_p, c_f, c_i, c_i, c_i, c_f] + [c_i] * 5 + [c_f, c_p, c_p, c_p]
 _SIG["wsmg_attn_fp8_row_fwd"] = [c_p] * 5 + [c_f, c_i, c_i, c_i] + [c_p] * 4
 _RESTYPE = {"wsmg_cls_tail_workspace_floats": c_l, "wsmg_attn_fp8_workspace_bytes": c_l, "wsmg_lstm_workspace_bytes": c_l, "wsmg_build_info": ctypes.c_char_p, "wsmg_channel_reduce_workspace_bytes": c_l, "wsmg_gru_workspace_bytes": c_l, "wsmg_lstm_state_workspace_bytes": c_l,
             "wsmg_instr_rnn_workspace_bytes": c_l}

@@ -55,8 +55,11 @@ class Mapping(nn.Module):
             raise ops._abi.WsmgError("full_global_map must be a contiguous [num_proc,G,G,C] tensor")
         local_scale = float(self.global_map_size * self.resolution) / float(self.global_map_size)
         fused = ops.bev_planes_ok(C, E) and debug.sw.bev_fused
+        project, fuse_retrieve = ops.bev_one_launch_routes(bs, C, E, self.global_map_size) if fused else (False, False)
         compact = None
-        if fused and ops.bev_compact_ok(Hf, Wf, E, bs):      # round 6: the index launch also packs the valid sources (20-25 % of a frame)
+        if project:                                          # below 4 frames: the scatter launch derives the cells from the depth itself
+            lin = None
+        elif fused and ops.bev_compact_ok(Hf, Wf, E, bs):    # round 6: the index launch also packs the valid sources (20-25 % of a frame)
             lin, compact = ops.bev_index_compact(depth, Hf, Wf, E, depth_scale=10.0, local_scale=local_scale)
         else:
             lin = ops.bev_index(depth, Hf, Wf, E, depth_scale=10.0, local_scale=local_scale)
@@ -64,7 +67,14 @@ class Mapping(nn.Module):
         gps = observations["gps"].reshape(bs, 2).float().contiguous()
         if fused:
             # scatter-max + rotation in one launch (the channel plane is rotated out of LDS); the fuse reads the rotated planes
-            rotated = ops.bev_scatter_rotate(features.float().contiguous(), lin, compass, -1.0, C, E, compact=compact)
+            if project:
+                rotated, _ = ops.bev_project(depth, features.float().contiguous(), compass, -1.0, C, E, depth_scale=10.0,
+                                             local_scale=local_scale, want_index=False)
+            else:
+                rotated = ops.bev_scatter_rotate(features.float().contiguous(), lin, compass, -1.0, C, E, compact=compact)
+            if fuse_retrieve:                                # fuse and retrieval in one launch
+                ego_nhwc = ops.map_fuse_retrieve(rotated, gm, gps, compass, masks.reshape(bs).float().contiguous(), E, self.resolution)
+                return ego_nhwc.permute(0, 3, 1, 2), gm
             ops.map_fuse(rotated, gm, gps, masks.reshape(bs).float().contiguous(), self.resolution, planes=True)
         else:
             planes = ops.bev_scatter_max(features.float().contiguous(), lin, C, E)

@@ -33,6 +33,7 @@ _TABLE = [
     ("rows_linear", "WSMG_ROWS_LINEAR", True, bool, "one-launch dense layers for <= 16 rows"),
     ("bev_fused", "WSMG_BEV_FUSED", True, bool, "scatter + rotation in one launch, plane-consuming fuse"),
     ("bev_compact", "WSMG_BEV_COMPACT", True, bool, "BEV: the index launch packs the valid sources and the scatter walks only those (round 6)"),
+    ("bev_one_launch", "WSMG_BEV_ONE_LAUNCH", -1, int, "BEV: index + scatter + rotation as one launch (wsmg_bev_project) and fuse + retrieve as one (wsmg_map_fuse_retrieve); -1: where profiles/bev_fuse_retrieve.txt has them measured and not slower (fuse + retrieve at B = 1 of E = 100, C = 64, G = 240), 0: never, 1: wherever the shapes allow"),
     ("rnn_stock", "WSMG_RNN_STOCK", False, bool, "the three recurrences on the stock (MIOpen) GRU / LSTM: no persistent kernel at all (bench.py's last fallback; needs recurrent_chunks = 0)"),
     ("rnn_poison", "WSMG_RNN_POISON", False, bool, "NaN-fill the persistent kernels' workspaces first (stress tool)"),
     ("feeder_pin", "WSMG_FEEDER_PIN", True, bool, "register the feeder's shared-memory ring as pinned memory"),

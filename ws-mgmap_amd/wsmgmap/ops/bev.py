@@ -141,6 +141,82 @@ def map_retrieve(global_map, gps, compass, E, resolution=0.12, fused=None):
     return out
 
 
+def bev_one_launch_routes(B, C, E, G):
+    """(project, fuse_retrieve): which of the two one-launch forms Mapping.project_feat_to_map takes for a batch of B frames of a
+    [C,E,E] ego map in a G x G global map.  debug.sw.bev_one_launch = 0 / 1 forces neither / both wherever the shapes allow; -1
+    follows the interleaved A/B of profiles/bev_fuse_retrieve.txt: a form is the default only at a configuration where it was
+    measured and its median was not slower than the launches it replaces.  bev_project is a small-batch form: from 4 frames on the
+    compacted index route stays."""
+    if not bev_planes_ok(C, E) or sw.bev_one_launch == 0:
+        return False, False
+    small = B < 4
+    if sw.bev_one_launch > 0:
+        return small, True
+    return small and _PROJECT_DEFAULT, _fuse_retrieve_default(B, C, E, G)
+
+
+# profiles/bev_fuse_retrieve.txt: bev_project is slower than index + scatter_rotate at every measured configuration (B = 1: every
+# plane workgroup pays the index arithmetic of all sources), so no batch takes it by default; map_fuse_retrieve wins where the step is
+# launch latency (B = 1 at E = 100, C = 64, G = 240: cfg1 and the native configuration) and loses once the tiles' recomputed paste
+# is real work (B = 8 and cfg4).  Nothing else was measured — batches of 2 and 3, B = 1 at another geometry — and what was not
+# measured keeps the two launches.
+_PROJECT_DEFAULT = False
+_FUSE_RETRIEVE_MEASURED_FASTER = {(1, 64, 100, 240)}          # (B, C, E, G)
+
+
+def _fuse_retrieve_default(B, C, E, G):
+    return (B, C, E, G) in _FUSE_RETRIEVE_MEASURED_FASTER
+
+
+@torch.no_grad()
+def map_fuse_retrieve(ego_rot_planes, global_map, gps, compass, masks, E, resolution=0.12):
+    """map_fuse(planes=True) + map_retrieve (the tiled form) in ONE launch (wsmg_map_fuse_retrieve): global_map [P,G,G,C] is updated
+    in place, -> ego map NHWC [B,E,E,C]; both bit for bit what the two calls leave, for masks in {0, 1} and finite features (finite
+    ego_rot_planes).  Outside that contract — a mask that is neither 0 nor 1, an infinite plane value on a reset step — the result
+    depends on the order in which workgroups run and is not repeatable; the two calls are.  ego_rot_planes [B,C,E,E] is
+    bev_scatter_rotate's / bev_project's output."""
+    if ego_rot_planes.dim() != 4 or ego_rot_planes.shape[2] != E or ego_rot_planes.shape[3] != E:
+        raise _abi.WsmgError(f"map_fuse_retrieve: rotated planes [B,C,{E},{E}] expected, got {tuple(ego_rot_planes.shape)}")
+    B, C = ego_rot_planes.shape[:2]
+    _check_global_map(global_map, B, C, ego_rot_planes, gps, compass, masks)
+    if gps.shape[0] != B or masks.numel() != B or compass.numel() != B:
+        raise _abi.WsmgError("map_fuse_retrieve: gps [B,2], compass [B] and masks [B] must match the ego maps' batch")
+    if not bev_planes_ok(C, E):
+        raise _abi.WsmgError(f"map_fuse_retrieve: needs C % 4 == 0, C <= 64 and E * E * 4 <= 160 KiB (bev_planes_ok), got C = {C}, E = {E}")
+    G = global_map.shape[1]
+    if G < E:
+        raise _abi.WsmgError(f"map_fuse_retrieve: the global map ({G}) is smaller than the ego map ({E})")
+    _req(ego_rot_planes, global_map, gps, compass, masks)
+    out = torch.empty(B, E, E, C, device=gps.device, dtype=torch.float32)
+    _abi.call("wsmg_map_fuse_retrieve", _p(ego_rot_planes), _p(global_map), _p(gps), _p(compass), _p(masks), B, C, E, G, float(resolution),
+              _p(out), _stream())
+    return out
+
+
+@torch.no_grad()
+def bev_project(depth, feat, heading, sign, C, E, depth_scale=10.0, local_scale=0.12, want_index=True):
+    """bev_index + bev_scatter_rotate in ONE launch (wsmg_bev_project; meant for batches below 4): depth [B,Hd,Wd], feat
+    [B,Cf,Hf,Wf] NCHW, heading [B] -> (rotated planes [B,C,E,E], lin_idx int32 [B,Hf*Wf] or None without want_index), both bit for
+    bit what the two calls give."""
+    _f32(depth, feat, heading)
+    if depth.dim() != 3 or feat.dim() != 4:
+        raise _abi.WsmgError(f"bev_project: depth [B,Hd,Wd] and feat [B,Cf,Hf,Wf] expected, got {tuple(depth.shape)}, {tuple(feat.shape)}")
+    B, Hd, Wd = depth.shape
+    _, Cf, Hf, Wf = feat.shape
+    if feat.shape[0] != B or heading.numel() != B:
+        raise _abi.WsmgError("bev_project: depth, feat and heading must have the same batch")
+    if not bev_planes_ok(C, E):
+        raise _abi.WsmgError(f"bev_project: needs C % 4 == 0, C <= 64 and E * E * 4 <= 160 KiB (bev_planes_ok), got C = {C}, E = {E}")
+    if C > Cf or Hf > Hd or Wf > Wd:
+        raise _abi.WsmgError(f"bev_project: C <= Cf and a feature map no larger than the depth image expected, got C = {C}, feat {tuple(feat.shape)}, depth {tuple(depth.shape)}")
+    _req(depth, feat, heading)
+    lin = torch.empty(B, Hf * Wf, device=depth.device, dtype=torch.int32) if want_index else None
+    out = torch.empty(B, C, E, E, device=feat.device, dtype=torch.float32)
+    _abi.call("wsmg_bev_project", _p(depth), _p(feat), _p(heading), float(sign), B, Hd, Wd, float(depth_scale), Cf, Hf, Wf, C, E,
+              float(local_scale), _p(lin) if want_index else None, _p(out), _stream())
+    return out, lin
+
+
 def ego_channels_last_dims(ego):
     """(B, H, W, C) of an ego map that is channels-last in memory: `observations['rgb_ego_map']` as the mapping module leaves it
     ([B,C,H,W]: map_retrieve's NHWC tensor, permuted) or a plain contiguous NHWC tensor [B,H,W,C]; anything else raises."""
