@@ -320,6 +320,20 @@ int wsmg_adam_step_multi(const WsmgAdamDesc* descs, int n, float lr, float beta1
  * in the kernel: the form a captured HIP graph can replay (torch.optim.Adam(capturable=True) is the stock counterpart). */
 int wsmg_adam_step_multi_dev(const WsmgAdamDesc* descs, int n, float lr, float beta1, float beta2, float eps, float weight_decay,
                              const float* step_dev, wsmg_stream_t stream);
+/* The guarded step: global gradient norm, clip and skip-on-non-finite on the device, with no host synchronisation (what
+ * torch.nn.utils.clip_grad_norm_ and a host-side isfinite check do around the reference's optimizer.step()).
+ * wsmg_grad_norm_multi: L2 norm over the gradients of descs (only grad and n are read) — one float64 partial per 4 096-element
+ * workgroup into partials[0 .. total), summed in a fixed order (deterministic, no atomics) — then the guard record, four float32:
+ *   guard[0] norm = (float)sqrt(sum);  guard[1] coef = max_norm > 0 ? min(1, max_norm / (norm + 1e-6f)) : 1 (NaN stays NaN);
+ *   guard[2] skip = skip_nonfinite && !isfinite(norm);  guard[3] += skip (the caller zeroes the record once).
+ * step_dev (or NULL) is advanced by 1 - skip.  WSMG_EINVAL for null / negative / misaligned arguments and WSMG_ENOMEM when
+ * partials_cap < total = sum over descs of ceil(n / 4096), both before anything is launched.
+ * wsmg_adam_step_multi_guarded: wsmg_adam_step_multi_dev reading that record: nothing at all is written when skip is set,
+ * otherwise the step uses grad * coef (the gradients themselves are not modified). */
+int wsmg_grad_norm_multi(const WsmgAdamDesc* descs, int n, double* partials, long long partials_cap, float max_norm,
+                         int skip_nonfinite, float* guard, float* step_dev, wsmg_stream_t stream);
+int wsmg_adam_step_multi_guarded(const WsmgAdamDesc* descs, int n, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                 const float* step_dev, const float* guard, wsmg_stream_t stream);
 
 /* Tests / tools: tile of the LDS-window kernel that serves 3x3 stride-1 pad-1 layers with Cout % 128 == 0, Cin % 32 == 0, Cin >= 64 and
  * B*H*W >= 65536 (0 = off -> implicit-GEMM kernel, 1 = tile chosen by shape, 256 or 512 pixels per workgroup; default 1 or

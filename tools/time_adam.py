@@ -1,7 +1,16 @@
 #!/usr/bin/env python3
-"""GPU-box tool: GPU time of one optimizer step over the policy's live parameters: torch.optim.Adam multi-tensor
-(default) vs fused=True."""
+"""GPU-box tool: one optimizer step over the policy's live parameters (102 tensors), GPU time between HIP events and host time
+per step, arms interleaved over --rounds rounds of --steps steps:
+
+    torch-foreach, torch-fused   torch.optim.Adam (multi-tensor default / fused=True)
+    wsmg                         wsmgmap.optim.Adam, the unguarded step (3 launches)
+    wsmg-guarded                 wsmgmap.optim.Adam(max_grad_norm=..., skip_nonfinite=True): norm launches + finalize + guarded step
+    clip+wsmg                    torch.nn.utils.clip_grad_norm_ in front of the unguarded step (what the guard replaces)
+
+WSMG_LIB=<another build of libwsmgmap.so> times that library's unguarded step (an older build has no guarded arm: --arms wsmg)."""
+import argparse
 import os, sys
+import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "ws-mgmap_amd"))
 import torch
@@ -9,6 +18,12 @@ import bench
 from wsmgmap.common.aux_losses import AuxLosses
 from wsmgmap.config import default_model_config
 from wsmgmap.models.policy import BasePolicy
+from wsmgmap.optim import Adam as WsmgAdam
+ap = argparse.ArgumentParser()
+ap.add_argument("--arms", default="torch-foreach,torch-fused,wsmg,wsmg-guarded,clip+wsmg")
+ap.add_argument("--rounds", type=int, default=3)
+ap.add_argument("--steps", type=int, default=20)
+args = ap.parse_args()
 T, N = 8, 8
 dev = torch.device("cuda:0")
 torch.manual_seed(0)
@@ -21,13 +36,40 @@ o = dict(obs)
 pred, aux = policy(o, torch.zeros(policy.net.num_recurrent_layers, N, 512, device=dev), prev, masks, weights)
 bench.dagger_loss(pred, aux, o["waypoint"], weights).backward()
 live = [p for p in policy.parameters() if p.grad is not None]
-print("live parameter tensors:", len(live), "floats:", sum(p.numel() for p in live))
-for name, kw in (("foreach (default)", {}), ("fused", {"fused": True})):
-    opt = torch.optim.Adam(policy.parameters(), lr=1e-6, **kw)
-    for _ in range(3): opt.step()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(20): opt.step()
-    b.record(); torch.cuda.synchronize()
-    print(f"Adam {name}: {a.elapsed_time(b) / 20 * 1e3:.0f} us per step")
+print("live parameter tensors:", len(live), "floats:", sum(p.numel() for p in live), "library:", os.environ.get("WSMG_LIB", "(built)"))
+norm = float(torch.linalg.vector_norm(torch.stack([p.grad.norm() for p in live])))     # the clip arms clip at half of it
+arms = {}
+for name in args.arms.split(","):
+    if name == "torch-foreach":
+        opt = torch.optim.Adam(policy.parameters(), lr=1e-6)
+    elif name == "torch-fused":
+        opt = torch.optim.Adam(policy.parameters(), lr=1e-6, fused=True)
+    elif name in ("wsmg", "clip+wsmg"):
+        opt = WsmgAdam(policy.parameters(), lr=1e-6)
+    elif name == "wsmg-guarded":
+        opt = WsmgAdam(policy.parameters(), lr=1e-6, max_grad_norm=0.5 * norm, skip_nonfinite=True)
+    else:
+        raise SystemExit("unknown arm " + name)
+    if name == "clip+wsmg":
+        saved = [p.grad.clone() for p in live]
+
+        def step(opt=opt, saved=saved):
+            torch.nn.utils.clip_grad_norm_(live, 0.5 * norm)
+            opt.step()
+            torch._foreach_copy_([p.grad for p in live], saved)      # clip_grad_norm_ scaled them in place (this copy is timed too)
+    else:
+        step = opt.step
+    for _ in range(3): step()
+    arms[name] = step
+torch.cuda.synchronize()
+for r in range(args.rounds):
+    for name, step in arms.items():
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        t0 = time.perf_counter()
+        for _ in range(args.steps): step()
+        host = time.perf_counter() - t0
+        b.record(); torch.cuda.synchronize()
+        print(f"round {r} Adam {name}: {a.elapsed_time(b) / args.steps * 1e3:.0f} us per step between events, "
+              f"host {host / args.steps * 1e6:.0f} us per step")

@@ -7,6 +7,12 @@
 // of one tensor (16-byte accesses when all four pointers are 16-byte aligned) and finds its tensor by a search over the
 // table's block prefix.  Arithmetic as torch.optim.Adam (amsgrad = False, maximize = False), in its order:
 //     g' = g + wd p;  m += (1 - b1) (g' - m);  v = b2 v + (1 - b2) g' g';  p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)
+//
+// The GUARDED step (wsmg_grad_norm_multi + wsmg_adam_step_multi_guarded) puts the global gradient norm in front of it, on the
+// device: grad_sumsq_multi_kernel writes one float64 sum of squares per workgroup (same table, same 4 096-element ownership, no
+// atomics), grad_guard_finalize_kernel adds them in a fixed order and writes the guard record {norm, coef, skip, skipped} and
+// the step count, and adam_multi_guarded_kernel returns before its first load when `skip` is set and reads g * coef otherwise
+// (torch.nn.utils.clip_grad_norm_'s arithmetic, without writing the gradients).  No host synchronisation anywhere.
 #include "wsmg_common.h"
 
 namespace {
@@ -25,9 +31,15 @@ struct AdamBatch {
   float lr_bc1, beta1c, beta2, beta2c, sqrt_bc2, eps, wd;
   const float* step_dev;   // or null: the step count lives on the device (HIP-graph replay: the arguments are frozen at capture) and
   float lr, beta1;         //          the bias corrections are computed from it here
+  const float* guard;      // or null: the guard record of grad_guard_finalize_kernel (read by adam_multi_guarded_kernel only)
 };
 
-__device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, const AdamBatch& b, float lr_bc1, float sqrt_bc2) {
+enum { GUARD_NORM = 0, GUARD_COEF = 1, GUARD_SKIP = 2, GUARD_SKIPPED = 3 };   // the guard record: four float32
+
+template <bool GUARD>
+__device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, const AdamBatch& b, float lr_bc1, float sqrt_bc2,
+                                      float coef) {
+  if (GUARD) g *= coef;
   if (b.wd != 0.f) g = fmaf(b.wd, p, g);
   m = m + b.beta1c * (g - m);
   v = v * b.beta2 + b.beta2c * g * g;
@@ -35,7 +47,15 @@ __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, con
   p = p - lr_bc1 * (m / denom);
 }
 
-__global__ __launch_bounds__(256) void adam_multi_kernel(AdamBatch b) {
+// GUARD = false is the unguarded step, the code it was before the guard existed (the guard pointer is not read); GUARD = true
+// reads skip and coef once, before anything else.
+template <bool GUARD>
+__device__ __forceinline__ void adam_multi(const AdamBatch& b) {
+  float coef = 1.f;
+  if (GUARD) {
+    if (b.guard[GUARD_SKIP] != 0.f) return;     // a skipped step: no load of p / m / v, nothing written
+    coef = b.guard[GUARD_COEF];
+  }
   float lr_bc1 = b.lr_bc1, sqrt_bc2 = b.sqrt_bc2;
   if (b.step_dev) {   // 1 - beta^step in double, as the host path does
     const double st = (double)*b.step_dev;
@@ -63,21 +83,96 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(AdamBatch b) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         float pj = pp[j], mj = mm[j], vj = vv[j];
-        adam1(pj, gg[j], mj, vj, b, lr_bc1, sqrt_bc2);
+        adam1<GUARD>(pj, gg[j], mj, vj, b, lr_bc1, sqrt_bc2, coef);
         pp[j] = pj; mm[j] = mj; vv[j] = vj;
       }
       st4(p + i, pp); st4(m + i, mm); st4(v + i, vv);
     }
-    for (long long i = nv + threadIdx.x; i < i1; i += 256) adam1(p[i], g[i], m[i], v[i], b, lr_bc1, sqrt_bc2);
+    for (long long i = nv + threadIdx.x; i < i1; i += 256) adam1<GUARD>(p[i], g[i], m[i], v[i], b, lr_bc1, sqrt_bc2, coef);
   } else {
-    for (long long i = i0 + threadIdx.x; i < i1; i += 256) adam1(p[i], g[i], m[i], v[i], b, lr_bc1, sqrt_bc2);
+    for (long long i = i0 + threadIdx.x; i < i1; i += 256) adam1<GUARD>(p[i], g[i], m[i], v[i], b, lr_bc1, sqrt_bc2, coef);
+  }
+}
+
+__global__ __launch_bounds__(256) void adam_multi_kernel(AdamBatch b) { adam_multi<false>(b); }
+__global__ __launch_bounds__(256) void adam_multi_guarded_kernel(AdamBatch b) { adam_multi<true>(b); }
+
+// ---- the guard: global gradient norm -> {norm, coef, skip, skipped}
+
+struct GradBatch {         // adam_multi_kernel's table, the gradients' half
+  const float* g[ADAM_MAX];
+  int first_block[ADAM_MAX + 1];
+  long long n[ADAM_MAX];
+  int count;
+  double* partials;        // this launch's slice: one float64 per workgroup
+};
+
+// fixed order: the wave's xor tree, then the four waves in index order (thread 0 returns the sum)
+__device__ __forceinline__ double block_sum_d(double acc, double* red) {
+  acc = wave_sum_d(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  return red[0] + red[1] + red[2] + red[3];
+}
+
+__global__ __launch_bounds__(256) void grad_sumsq_multi_kernel(GradBatch b) {
+  __shared__ double red[4];
+  int lo = 0, hi = b.count;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if ((int)blockIdx.x >= b.first_block[mid]) lo = mid; else hi = mid;
+  }
+  const float* __restrict__ g = b.g[lo];
+  const long long n = b.n[lo];
+  const long long i0 = (long long)((int)blockIdx.x - b.first_block[lo]) * ADAM_CHUNK;
+  const long long i1 = i0 + ADAM_CHUNK < n ? i0 + ADAM_CHUNK : n;
+  double acc = 0.0;        // float64: gradients of 1e30 square to 1e60, and the sum's order then costs nothing visible in float32
+  if (((uintptr_t)g & 15) == 0) {
+    const long long nv = i0 + ((i1 - i0) & ~3ll);
+    for (long long i = i0 + 4 * (long long)threadIdx.x; i < nv; i += 4 * 256) {
+      const f32x4 gg = ld4(g + i);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc += (double)gg[j] * (double)gg[j];
+    }
+    for (long long i = nv + threadIdx.x; i < i1; i += 256) acc += (double)g[i] * (double)g[i];
+  } else {
+    for (long long i = i0 + threadIdx.x; i < i1; i += 256) acc += (double)g[i] * (double)g[i];
+  }
+  const double sum = block_sum_d(acc, red);
+  if (threadIdx.x == 0) b.partials[blockIdx.x] = sum;
+}
+
+// One workgroup: every partial of every launch, strided per thread, then the fixed tree.  Finiteness is judged on the float32 norm
+// and the clip coefficient is clip_grad_norm_'s (max_norm / (norm + 1e-6), clamped to 1; a NaN norm gives a NaN coefficient there
+// too).  The step count advances here, by 1 - skip: a skipped step does not advance the bias corrections.
+__global__ __launch_bounds__(256) void grad_guard_finalize_kernel(const double* __restrict__ partials, int total, float max_norm,
+                                                                   int skip_nonfinite, float* __restrict__ guard,
+                                                                   float* __restrict__ step_dev) {
+  __shared__ double red[4];
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < total; i += 256) acc += partials[i];
+  const double sum = block_sum_d(acc, red);
+  if (threadIdx.x == 0) {
+    const float norm = (float)sqrt(sum);
+    float coef = 1.f;
+    if (max_norm > 0.f) {
+      const float c = max_norm / (norm + 1e-6f);
+      coef = c > 1.f ? 1.f : c;
+    }
+    const float skip = (skip_nonfinite && !isfinite(norm)) ? 1.f : 0.f;
+    guard[GUARD_NORM] = norm;
+    guard[GUARD_COEF] = coef;
+    guard[GUARD_SKIP] = skip;
+    guard[GUARD_SKIPPED] += skip;
+    if (step_dev) *step_dev += 1.f - skip;
   }
 }
 
 }  // namespace
 
 static int adam_launch(const WsmgAdamDesc* descs, int n, float lr, float beta1, float beta2, float eps, float weight_decay,
-                       double bias_correction1, double bias_correction2, const float* step_dev, wsmg_stream_t s) {
+                       double bias_correction1, double bias_correction2, const float* step_dev, const float* guard,
+                       wsmg_stream_t s) {
   if (n < 0 || (n > 0 && !descs)) return WSMG_EINVAL;
   if (!step_dev && (!(bias_correction1 > 0.0) || !(bias_correction2 > 0.0))) return WSMG_EINVAL;
   for (int i = 0; i < n;) {
@@ -107,14 +202,16 @@ static int adam_launch(const WsmgAdamDesc* descs, int n, float lr, float beta1, 
     b.step_dev = step_dev;
     b.lr = lr;
     b.beta1 = beta1;
-    hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, wsmg_s(s), b);
+    b.guard = guard;
+    if (guard) hipLaunchKernelGGL(adam_multi_guarded_kernel, dim3((unsigned)blocks), dim3(256), 0, wsmg_s(s), b);
+    else hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, wsmg_s(s), b);
   }
   WSMG_RETURN_LAUNCH();
 }
 
 extern "C" int wsmg_adam_step_multi(const WsmgAdamDesc* descs, int n, float lr, float beta1, float beta2, float eps, float weight_decay,
                                     double bias_correction1, double bias_correction2, wsmg_stream_t s) {
-  return adam_launch(descs, n, lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2, nullptr, s);
+  return adam_launch(descs, n, lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2, nullptr, nullptr, s);
 }
 
 // The same step with the step COUNT read from device memory (one float32, already incremented for this step): what a captured
@@ -122,5 +219,49 @@ extern "C" int wsmg_adam_step_multi(const WsmgAdamDesc* descs, int n, float lr, 
 extern "C" int wsmg_adam_step_multi_dev(const WsmgAdamDesc* descs, int n, float lr, float beta1, float beta2, float eps,
                                         float weight_decay, const float* step_dev, wsmg_stream_t s) {
   if (!step_dev) return WSMG_EINVAL;
-  return adam_launch(descs, n, lr, beta1, beta2, eps, weight_decay, 0.0, 0.0, step_dev, s);
+  return adam_launch(descs, n, lr, beta1, beta2, eps, weight_decay, 0.0, 0.0, step_dev, nullptr, s);
+}
+
+// The _dev form behind a guard record (wsmg_grad_norm_multi on the same stream, before it): nothing is written when the record's
+// `skip` is set, g * coef is read otherwise.  step_dev is the count that call advanced.
+extern "C" int wsmg_adam_step_multi_guarded(const WsmgAdamDesc* descs, int n, float lr, float beta1, float beta2, float eps,
+                                            float weight_decay, const float* step_dev, const float* guard, wsmg_stream_t s) {
+  if (!step_dev || !guard) return WSMG_EINVAL;
+  return adam_launch(descs, n, lr, beta1, beta2, eps, weight_decay, 0.0, 0.0, step_dev, guard, s);
+}
+
+// Global L2 norm of the descs' gradients (param / exp_avg / exp_avg_sq are not read) into the guard record.  Every argument is
+// checked, and the partials' capacity against the total workgroup count, before the first launch.
+extern "C" int wsmg_grad_norm_multi(const WsmgAdamDesc* descs, int n, double* partials, long long partials_cap, float max_norm,
+                                    int skip_nonfinite, float* guard, float* step_dev, wsmg_stream_t s) {
+  if (n < 0 || (n > 0 && !descs) || !guard || !partials || partials_cap < 0 || !(max_norm >= 0.f)) return WSMG_EINVAL;
+  if (((uintptr_t)partials & 7) || ((uintptr_t)guard & 3) || ((uintptr_t)step_dev & 3)) return WSMG_EINVAL;
+  long long total = 0;
+  for (int i = 0; i < n; ++i) {
+    if (descs[i].n < 0 || (descs[i].n > 0 && !descs[i].grad)) return WSMG_EINVAL;
+    total += (descs[i].n + ADAM_CHUNK - 1) / ADAM_CHUNK;
+    if (total > (1ll << 30)) return WSMG_EINVAL;
+  }
+  if (total > partials_cap) return WSMG_ENOMEM;
+  int base = 0;
+  for (int i = 0; i < n;) {
+    GradBatch b;
+    b.count = 0;
+    int blocks = 0;
+    for (; i < n && b.count < ADAM_MAX; ++i) {
+      if (descs[i].n == 0) continue;
+      const int k = b.count++;
+      b.g[k] = descs[i].grad; b.n[k] = descs[i].n;
+      b.first_block[k] = blocks;
+      blocks += (int)((descs[i].n + ADAM_CHUNK - 1) / ADAM_CHUNK);
+    }
+    if (!b.count) continue;
+    b.first_block[b.count] = blocks;
+    b.partials = partials + base;
+    hipLaunchKernelGGL(grad_sumsq_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, wsmg_s(s), b);
+    base += blocks;
+  }
+  hipLaunchKernelGGL(grad_guard_finalize_kernel, dim3(1), dim3(256), 0, wsmg_s(s), (const double*)partials, base, max_norm,
+                     skip_nonfinite, guard, step_dev);
+  WSMG_RETURN_LAUNCH();
 }

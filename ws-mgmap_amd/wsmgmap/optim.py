@@ -4,8 +4,13 @@ The reference builds `torch.optim.Adam(self.actor_critic.parameters(), lr=...)` 
 `loss.backward()` (dagger_trainer.py:540-541).  This class is that optimizer — same constructor arguments, same arithmetic
 in the same order, `state_dict()` interchangeable with torch.optim.Adam's (`step`, `exp_avg`, `exp_avg_sq`) — with the step
 issued as 3 kernel launches for the policy's 102 live tensors instead of the stock multi-tensor path's 15 (0.25 ms of GPU time
-per update -> 0.06 ms).  float32 CUDA parameters only: anything else raises (there is no fallback path)."""
+per update -> 0.06 ms).  float32 CUDA parameters only: anything else raises (there is no fallback path).
+
+`Adam(max_grad_norm=..., skip_nonfinite=True)` guards the step on the device: the global gradient norm (deterministic float64
+sums, wsmg_grad_norm_multi), `clip_grad_norm_`'s coefficient and a skip flag go into a small guard record that the Adam kernel
+reads — no host synchronisation, capturable in a HIP graph.  `global_grad_norm(params)` is the norm alone."""
 import ctypes
+import math
 
 import torch
 
@@ -17,19 +22,84 @@ class _AdamDesc(ctypes.Structure):
                 ("n", ctypes.c_longlong)]
 
 
+ADAM_CHUNK = 4096         # elements per workgroup (csrc/wsmg_optim.hip): one float64 partial each in the norm's workspace
+
+
+def _norm_blocks(descs):
+    return sum((d.n + ADAM_CHUNK - 1) // ADAM_CHUNK for d in descs)
+
+
+def global_grad_norm(params):
+    """L2 norm over the `.grad` of every parameter that has one (as `clip_grad_norm_` over them computes it, but accumulated in
+    float64 in a fixed order: two calls return the same bits): a 0-dim float32 tensor on the gradients' device.  A few launches per
+    48 tensors and no host synchronisation; nothing is scaled.  Dense float32 CUDA gradients on one device only."""
+    grads = [p.grad for p in params if p.grad is not None]
+    if not grads:
+        raise _abi.WsmgError("wsmgmap.optim.global_grad_norm: no parameter has a gradient")
+    dev = grads[0].device
+    for g in grads:
+        if g.is_sparse or not (g.is_cuda and g.dtype == torch.float32 and g.device == dev):
+            raise _abi.WsmgError("wsmgmap.optim.global_grad_norm: gradients must be dense float32 CUDA tensors on one device")
+    grads = [g if g.is_contiguous() else g.contiguous() for g in grads]      # (copies live until the launches are queued)
+    descs = (_AdamDesc * len(grads))()
+    for d, g in zip(descs, grads):
+        d.grad, d.n = g.data_ptr(), g.numel()
+    with torch.cuda.device(dev):
+        guard = torch.zeros(4, device=dev, dtype=torch.float32)
+        cap = max(1, _norm_blocks(descs))
+        partials = torch.empty(cap, device=dev, dtype=torch.float64)
+        _abi.call("wsmg_grad_norm_multi", descs, len(grads), ctypes.c_void_p(partials.data_ptr()), cap, 0.0, 0,
+                  ctypes.c_void_p(guard.data_ptr()), None, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    return guard[0]
+
+
 class Adam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, maximize=False,
-                 capturable=False):
+                 capturable=False, max_grad_norm=None, skip_nonfinite=False):
         """capturable=True: the step count also lives in a device scalar (one per parameter group, incremented on the device)
         and the kernel computes the bias corrections from it — the form `wsmgmap.graph.GraphedUpdate` captures into a HIP graph
-        (kernel arguments are frozen at capture).  All stepped parameters of a group must then share one step count."""
+        (kernel arguments are frozen at capture).  All stepped parameters of a group must then share one step count.
+
+        max_grad_norm / skip_nonfinite (either one turns the GUARDED step on): before the step, the L2 norm over the gradients of
+        every stepped tensor of every group is computed on the device; with max_grad_norm the step reads g * min(1, max_grad_norm /
+        (norm + 1e-6)) — `clip_grad_norm_`'s arithmetic, but `p.grad` itself is NOT modified, the factor is applied where the Adam
+        kernel reads it; with skip_nonfinite a NaN / Inf norm makes the step write nothing (parameters, moments and the step count
+        stay as they were).  The step count lives on the device (one for the whole optimizer: all stepped parameters must share
+        it and one device), `step()` never synchronises with the host and can be captured in a HIP graph whether or not
+        capturable=True was passed.  `grad_norm`, `skipped_steps` and `state_dict()` report what happened."""
         self._capturable = bool(capturable)
         self._step_dev = {}
+        if max_grad_norm is not None and not (math.isfinite(max_grad_norm) and max_grad_norm > 0.0):
+            raise ValueError(f"invalid max_grad_norm: {max_grad_norm} (a finite positive number, or None for no clipping)")
+        self._max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self._skip_nonfinite = bool(skip_nonfinite)
+        self._guarded = self._max_grad_norm is not None or self._skip_nonfinite
+        self._guard = None        # device tensors of the guarded step: the record {norm, coef, skip, skipped}, the step count
+        self._guard_step = None   # and the norm's float64 workspace (allocated below, never by a default construction)
+        self._partials = None
         if amsgrad or maximize:
             raise ValueError("wsmgmap.optim.Adam implements amsgrad=False, maximize=False (what the reference trains with)")
         if lr < 0.0 or eps < 0.0 or weight_decay < 0.0 or not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
             raise ValueError(f"invalid Adam hyper-parameters: lr={lr} betas={betas} eps={eps} weight_decay={weight_decay}")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False))
+        if self._guarded:
+            self._reset_guard()
+
+    def _reset_guard(self):
+        """(Re-)create the guard's device tensors from the host-side step counts: at construction and after load_state_dict, so
+        that step() itself allocates and fills nothing — a fill captured into a HIP graph would reset the record at every replay."""
+        self._guard = self._guard_step = self._partials = None
+        params = [p for group in self.param_groups for p in group["params"]]
+        if not params or not all(p.is_cuda for p in params):
+            return                 # step() refuses such parameters
+        steps = {st["step"] for st in self.state.values() if "step" in st}
+        if len(steps) > 1:
+            return                 # step() refuses stepped parameters that do not share one count
+        dev = params[0].device
+        self._guard = torch.zeros(4, device=dev, dtype=torch.float32)
+        self._guard_step = torch.full((), float(steps.pop() if steps else 0), device=dev, dtype=torch.float32)
+        blocks = sum((p.numel() + ADAM_CHUNK - 1) // ADAM_CHUNK for p in params)
+        self._partials = torch.empty(max(1, blocks), device=dev, dtype=torch.float64)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -37,6 +107,9 @@ class Adam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        if self._guarded:
+            self._guarded_step()
+            return loss
         for group in self.param_groups:
             by_step = {}
             for p in group["params"]:
@@ -84,9 +157,79 @@ class Adam(torch.optim.Optimizer):
                 torch.autograd.graph.increment_version([it[0] for it in items])
         return loss
 
+    def _guarded_step(self):
+        groups, steps, dev = [], set(), None
+        for group in self.param_groups:
+            items = []
+            for p in group["params"]:
+                g = p.grad
+                if g is None:
+                    continue
+                if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
+                    raise _abi.WsmgError("wsmgmap.optim.Adam: parameters must be contiguous float32 CUDA tensors")
+                if g.is_sparse or g.dtype != torch.float32 or g.device != p.device:
+                    raise _abi.WsmgError("wsmgmap.optim.Adam: gradients must be dense float32 tensors on the parameter's device")
+                if dev is None:
+                    dev = p.device
+                if p.device != dev:
+                    raise _abi.WsmgError("wsmgmap.optim.Adam: the guarded step takes one norm over all parameters: they must share a device")
+                if not g.is_contiguous():
+                    g = g.contiguous()
+                    g.record_stream(torch.cuda.current_stream(p.device))
+                st = self.state[p]
+                if not st:
+                    if torch.cuda.is_current_stream_capturing():      # the zero fills would be replayed: moments reset every time
+                        raise _abi.WsmgError("wsmgmap.optim.Adam: the moments do not exist yet; take a step (or load_state_dict) "
+                                             "before capturing step() into a graph")
+                    st["step"] = 0
+                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st["step"] += 1     # ATTEMPTED steps; the device count (attempted - skipped) is what the kernel uses
+                steps.add(st["step"])
+                items.append((p, g, st["exp_avg"], st["exp_avg_sq"]))
+            if items:
+                groups.append((group, items))
+        if not groups:
+            return
+        if len(steps) > 1:
+            raise _abi.WsmgError("wsmgmap.optim.Adam: the guarded step keeps one step count on the device: all stepped parameters "
+                                 "must share it")
+        every = [it for _, items in groups for it in items]
+        descs = (_AdamDesc * len(every))()
+        for d, (p, g, m, v) in zip(descs, every):
+            d.param, d.grad, d.exp_avg, d.exp_avg_sq, d.n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        with torch.cuda.device(dev):
+            if self._guard is None or self._guard.device != dev or self._partials.numel() < _norm_blocks(descs):
+                raise _abi.WsmgError("wsmgmap.optim.Adam: the guard's device state does not fit the stepped parameters (construct the "
+                                     "optimizer over the CUDA parameters it steps)")
+            guard, sd = ctypes.c_void_p(self._guard.data_ptr()), ctypes.c_void_p(self._guard_step.data_ptr())
+            # the finalize advances the step count by 1 - skip: a skipped step does not advance the bias corrections
+            _abi.call("wsmg_grad_norm_multi", descs, len(every), ctypes.c_void_p(self._partials.data_ptr()), self._partials.numel(),
+                      self._max_grad_norm or 0.0, int(self._skip_nonfinite), guard, sd, stream)
+            at = 0
+            for group, items in groups:
+                b1, b2 = group["betas"]
+                _abi.call("wsmg_adam_step_multi_guarded", ctypes.byref(descs, at * ctypes.sizeof(_AdamDesc)), len(items),
+                          float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), sd, guard, stream)
+                at += len(items)
+        torch.autograd.graph.increment_version([it[0] for it in every])
+
+    @property
+    def grad_norm(self):
+        """The last guarded step's gradient norm before clipping: a 0-dim device tensor, a view of the guard record (reading it is
+        the caller's synchronisation, holding it costs nothing).  None before the first guarded step."""
+        return None if self._guard is None else self._guard[0]
+
+    @property
+    def skipped_steps(self):
+        """How many guarded steps found a non-finite norm and wrote nothing (since construction or load_state_dict): one readback."""
+        return 0 if self._guard is None else int(self._guard[3].item())
+
     def note_replayed_steps(self, n=1):
         """A captured graph that contains this optimizer's step was replayed n times: advance the host-side step counts (the
-        device counters advanced inside the graph)."""
+        device counters advanced inside the graph).  With the guard on the host count is the ATTEMPTED steps; the device count,
+        which skipped steps do not advance, is the one the kernel uses."""
         stepped = []
         for p, st in self.state.items():
             if "step" in st:
@@ -97,7 +240,8 @@ class Adam(torch.optim.Optimizer):
 
     def state_dict(self):
         sd = super().state_dict()
-        sd["state"] = {k: {**v, "step": torch.tensor(float(v["step"]), dtype=torch.float32)} if "step" in v else v
+        skipped = self.skipped_steps        # guarded: `step` = attempted - skipped, the steps that were taken
+        sd["state"] = {k: {**v, "step": torch.tensor(float(v["step"] - skipped), dtype=torch.float32)} if "step" in v else v
                        for k, v in sd["state"].items()}
         return sd
 
@@ -107,3 +251,5 @@ class Adam(torch.optim.Optimizer):
             if "step" in st:
                 st["step"] = int(round(float(st["step"])))
         self._step_dev = {}       # re-created from the loaded step counts at the next capturable step
+        if self._guarded:
+            self._reset_guard()   # the guard record (skipped = 0) and its step count, from the loaded step counts
