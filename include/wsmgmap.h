@@ -283,6 +283,14 @@ typedef struct {
   long long bytes;
 } WsmgCopyDesc;
 int wsmg_copy_multi(const WsmgCopyDesc* descs, int n, wsmg_stream_t stream);
+/* wsmg_copy_multi, performed only if the guard record of wsmg_grad_norm_multi says the step is skipped (guard[2] != 0);
+ * otherwise nothing is written.  Any alignment, any byte count, non-overlapping.  descs is a HOST array.
+ * The roll-back of what a forward pass wrote before the guard could judge its gradients: the running_mean / running_var /
+ * num_batches_tracked that the train-mode BatchNorm layers of map_encoder.py:19-29,94-112 and mg_map_policy.py:78-100 update in
+ * forward() (the reference has no counterpart: it trains without a guard).  Bytes are copied (int64 counters, NaN payloads); 48
+ * descriptors per launch; the record is only read.  WSMG_EINVAL before anything is enqueued: NULL descs or guard (or a guard
+ * that is not 4-byte aligned), n <= 0, a NULL pointer in a descriptor with bytes > 0, negative bytes. */
+int wsmg_copy_multi_guarded(const WsmgCopyDesc* descs, int n, const float* guard, wsmg_stream_t stream);
 /* Rollout-size dense layers, one row per environment (the nn.Linear calls of mg_map_policy.py:150-197 at 1-16 rows):
  * y[r][o] = act(sum_k x[r][k] w[o][k] + bias[o]) in ONE launch (a GEMM library call is bias copy + GEMM + activation);
  * x [B][K] (pool = 1) or [B][K][pool] whose mean over the last axis is the layer's input (rgb_linear's AdaptiveAvgPool1d(1) +

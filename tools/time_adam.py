@@ -5,6 +5,8 @@ per step, arms interleaved over --rounds rounds of --steps steps:
     torch-foreach, torch-fused   torch.optim.Adam (multi-tensor default / fused=True)
     wsmg                         wsmgmap.optim.Adam, the unguarded step (3 launches)
     wsmg-guarded                 wsmgmap.optim.Adam(max_grad_norm=..., skip_nonfinite=True): norm launches + finalize + guarded step
+    wsmg-guarded-buffers         the same with guard_buffers=policy: snapshot_buffers() (what zero_grad() adds) + the step with the
+                                 conditional roll-back of the BatchNorm statistics behind it (steps taken: the roll-back returns at once)
     clip+wsmg                    torch.nn.utils.clip_grad_norm_ in front of the unguarded step (what the guard replaces)
 
 WSMG_LIB=<another build of libwsmgmap.so> times that library's unguarded step (an older build has no guarded arm: --arms wsmg)."""
@@ -48,6 +50,8 @@ for name in args.arms.split(","):
         opt = WsmgAdam(policy.parameters(), lr=1e-6)
     elif name == "wsmg-guarded":
         opt = WsmgAdam(policy.parameters(), lr=1e-6, max_grad_norm=0.5 * norm, skip_nonfinite=True)
+    elif name == "wsmg-guarded-buffers":
+        opt = WsmgAdam(policy.parameters(), lr=1e-6, max_grad_norm=0.5 * norm, skip_nonfinite=True, guard_buffers=policy)
     else:
         raise SystemExit("unknown arm " + name)
     if name == "clip+wsmg":
@@ -57,6 +61,10 @@ for name in args.arms.split(","):
             torch.nn.utils.clip_grad_norm_(live, 0.5 * norm)
             opt.step()
             torch._foreach_copy_([p.grad for p in live], saved)      # clip_grad_norm_ scaled them in place (this copy is timed too)
+    elif name == "wsmg-guarded-buffers":
+        def step(opt=opt):
+            opt.snapshot_buffers()
+            opt.step()
     else:
         step = opt.step
     for _ in range(3): step()

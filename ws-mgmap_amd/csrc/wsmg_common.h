@@ -58,6 +58,11 @@ static inline int wsmg_tune_read(const char* name, int dflt) {
 
 static inline int64_t wsmg_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Multi-tensor launches (wsmg_optim.hip's Adam / norm kernels, wsmg_small.hip's guarded copy): tensors per launch — the table lives
+// in the kernel arguments, a longer list is cut into several launches — and the guard record of wsmg_grad_norm_multi, four float32.
+constexpr int ADAM_MAX = 48;
+enum { GUARD_NORM = 0, GUARD_COEF = 1, GUARD_SKIP = 2, GUARD_SKIPPED = 3 };
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -17,7 +17,7 @@
 
 namespace {
 
-constexpr int ADAM_MAX = 48;      // tensors per launch (kernel-argument table)
+// ADAM_MAX = 48 tensors per launch (kernel-argument table): wsmg_common.h
 constexpr int ADAM_CHUNK = 4096;  // elements per workgroup
 
 struct AdamBatch {
@@ -33,8 +33,6 @@ struct AdamBatch {
   float lr, beta1;         //          the bias corrections are computed from it here
   const float* guard;      // or null: the guard record of grad_guard_finalize_kernel (read by adam_multi_guarded_kernel only)
 };
-
-enum { GUARD_NORM = 0, GUARD_COEF = 1, GUARD_SKIP = 2, GUARD_SKIPPED = 3 };   // the guard record: four float32
 
 template <bool GUARD>
 __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, const AdamBatch& b, float lr_bc1, float sqrt_bc2,

@@ -146,7 +146,76 @@ __global__ __launch_bounds__(256) void copy_multi_kernel(CopyBatch b) {
   }
 }
 
+// ---- the same list, copied only when a guarded optimizer step was skipped (the BatchNorm statistics a poisoned forward pass wrote,
+// rolled back from their snapshot).  The table is the Adam kernels' size (ADAM_MAX); every workgroup reads the guard record's skip
+// word first and returns on 0 — the common case: nothing of any descriptor is loaded or stored.  Otherwise a workgroup owns 16 KB
+// of one copy: 16-byte accesses over the part where dst and src are both 16-byte aligned (they may share a misalignment: byte head
+// up to the first aligned address), bytes for head, tail and pairs whose misalignments differ.  Bytes, not floats: int64 counters
+// and NaN payloads pass unchanged.
+struct GuardedCopyBatch {
+  unsigned char* dst[ADAM_MAX];
+  const unsigned char* src[ADAM_MAX];
+  long long bytes[ADAM_MAX];
+  int first_block[ADAM_MAX + 1];
+  int count;
+  const float* guard;
+};
+__global__ __launch_bounds__(256) void copy_multi_guarded_kernel(GuardedCopyBatch b) {
+  if (b.guard[GUARD_SKIP] == 0.f) return;       // the step was taken: the snapshot is not needed
+  int lo = 0, hi = b.count;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if ((int)blockIdx.x >= b.first_block[mid]) lo = mid; else hi = mid;
+  }
+  unsigned char* __restrict__ d = b.dst[lo];
+  const unsigned char* __restrict__ s = b.src[lo];
+  const long long i0 = (long long)((int)blockIdx.x - b.first_block[lo]) * COPY_CHUNK;
+  const long long i1 = i0 + COPY_CHUNK < b.bytes[lo] ? i0 + COPY_CHUNK : b.bytes[lo];
+  typedef unsigned int u32x4c __attribute__((ext_vector_type(4)));
+  long long v0 = i1, v1 = i1;                   // [v0, v1): the 16-byte part of [i0, i1); empty when the two misalignments differ
+  if ((((uintptr_t)d ^ (uintptr_t)s) & 15) == 0) {
+    const long long head = (long long)((0 - ((uintptr_t)d + (uintptr_t)i0)) & 15);
+    v0 = i0 + head < i1 ? i0 + head : i1;
+    v1 = v0 + ((i1 - v0) & ~15ll);
+  }
+  for (long long i = i0 + threadIdx.x; i < v0; i += 256) d[i] = s[i];
+  for (long long i = v0 + 16 * (long long)threadIdx.x; i < v1; i += 16 * 256)
+    *reinterpret_cast<u32x4c*>(d + i) = *reinterpret_cast<const u32x4c*>(s + i);
+  for (long long i = v1 + threadIdx.x; i < i1; i += 256) d[i] = s[i];
+}
+
 }  // namespace
+
+extern "C" int wsmg_copy_multi_guarded(const WsmgCopyDesc* descs, int n, const float* guard, wsmg_stream_t stream) {
+  if (!descs || !guard || n <= 0 || ((uintptr_t)guard & 3)) return WSMG_EINVAL;
+  for (int i = 0, k = 0, blocks = 0; i < n; ++i) {      // every descriptor of every launch, before the first launch
+    const WsmgCopyDesc& c = descs[i];
+    if (c.bytes < 0 || (c.bytes > 0 && (!c.dst || !c.src))) return WSMG_EINVAL;
+    if (c.bytes == 0) continue;
+    if (k++ % ADAM_MAX == 0) blocks = 0;
+    const long long nb = (c.bytes + COPY_CHUNK - 1) / COPY_CHUNK;
+    if (nb > (1ll << 30) - blocks) return WSMG_EINVAL;
+    blocks += (int)nb;
+  }
+  for (int i = 0; i < n;) {
+    GuardedCopyBatch b;
+    b.count = 0;
+    b.guard = guard;
+    int blocks = 0;
+    for (; i < n && b.count < ADAM_MAX; ++i) {
+      const WsmgCopyDesc& c = descs[i];
+      if (c.bytes == 0) continue;
+      const int k = b.count++;
+      b.dst[k] = (unsigned char*)c.dst; b.src[k] = (const unsigned char*)c.src; b.bytes[k] = c.bytes;
+      b.first_block[k] = blocks;
+      blocks += (int)((c.bytes + COPY_CHUNK - 1) / COPY_CHUNK);
+    }
+    if (!b.count) continue;
+    b.first_block[b.count] = blocks;
+    hipLaunchKernelGGL(copy_multi_guarded_kernel, dim3((unsigned)blocks), dim3(256), 0, wsmg_s(stream), b);
+  }
+  WSMG_RETURN_LAUNCH();
+}
 
 extern "C" int wsmg_copy_multi(const WsmgCopyDesc* descs, int n, wsmg_stream_t stream) {
   if (n < 0 || (n > 0 && !descs)) return WSMG_EINVAL;

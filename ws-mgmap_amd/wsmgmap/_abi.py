@@ -155,6 +155,7 @@ _SIG["wsmg_rnn_debug_inject"] = [ctypes.c_uint]
 _SIG["wsmg_instruction_dedup"] = [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p]
 _SIG["wsmg_conv_debug_win3_tile"] = [c_i]
 _SIG["wsmg_copy_multi"] = [c_p, c_i, c_p]
+_SIG["wsmg_copy_multi_guarded"] = [c_p, c_i, c_p, c_p]
 _SIG["wsmg_linear_rows"] = [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]
 _SIG["wsmg_act_heads"] = [c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]
 _SIG["wsmg_path_kl_fwd"] = [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p]

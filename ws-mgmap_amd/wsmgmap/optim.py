@@ -8,7 +8,11 @@ per update -> 0.06 ms).  float32 CUDA parameters only: anything else raises (the
 
 `Adam(max_grad_norm=..., skip_nonfinite=True)` guards the step on the device: the global gradient norm (deterministic float64
 sums, wsmg_grad_norm_multi), `clip_grad_norm_`'s coefficient and a skip flag go into a small guard record that the Adam kernel
-reads — no host synchronisation, capturable in a HIP graph.  `global_grad_norm(params)` is the norm alone."""
+reads — no host synchronisation, capturable in a HIP graph.  `global_grad_norm(params)` is the norm alone.
+
+`Adam(skip_nonfinite=True, guard_buffers=module)` extends the skip to what the forward pass already wrote: `zero_grad()` snapshots the
+BatchNorm running statistics below `module` on the device (wsmg_copy_multi), and a skipped step copies them back
+(wsmg_copy_multi_guarded, which reads the same guard record and writes nothing after a step that was taken)."""
 import ctypes
 import math
 
@@ -23,6 +27,7 @@ class _AdamDesc(ctypes.Structure):
 
 
 ADAM_CHUNK = 4096         # elements per workgroup (csrc/wsmg_optim.hip): one float64 partial each in the norm's workspace
+ADAM_MAX = 48             # tensors (or copies) per launch (csrc/wsmg_common.h): longer lists are cut into several launches
 
 
 def _norm_blocks(descs):
@@ -55,7 +60,7 @@ def global_grad_norm(params):
 
 class Adam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, maximize=False,
-                 capturable=False, max_grad_norm=None, skip_nonfinite=False):
+                 capturable=False, max_grad_norm=None, skip_nonfinite=False, guard_buffers=None):
         """capturable=True: the step count also lives in a device scalar (one per parameter group, incremented on the device)
         and the kernel computes the bias corrections from it — the form `wsmgmap.graph.GraphedUpdate` captures into a HIP graph
         (kernel arguments are frozen at capture).  All stepped parameters of a group must then share one step count.
@@ -66,7 +71,15 @@ class Adam(torch.optim.Optimizer):
         kernel reads it; with skip_nonfinite a NaN / Inf norm makes the step write nothing (parameters, moments and the step count
         stay as they were).  The step count lives on the device (one for the whole optimizer: all stepped parameters must share
         it and one device), `step()` never synchronises with the host and can be captured in a HIP graph whether or not
-        capturable=True was passed.  `grad_norm`, `skipped_steps` and `state_dict()` report what happened."""
+        capturable=True was passed.  `grad_norm`, `skipped_steps` and `state_dict()` report what happened.
+
+        guard_buffers=module (needs skip_nonfinite=True): a skipped step also rolls back `running_mean`, `running_var` and
+        `num_batches_tracked` of every BatchNorm layer below `module` that tracks running statistics — a poisoned forward pass has
+        written them before any gradient exists.  `zero_grad()` (or `snapshot_buffers()`) copies them into one flat device
+        allocation, on the current stream; the guarded step copies them back when, and only when, the guard record says the step
+        was skipped.  Both are device launches behind the same record: no host synchronisation, capturable together with the
+        step (after one eager snapshot: the allocation is never made under capture).  A `step()` with no snapshot since the
+        previous one raises.  The snapshot is not optimizer state: `state_dict()` does not hold it."""
         self._capturable = bool(capturable)
         self._step_dev = {}
         if max_grad_norm is not None and not (math.isfinite(max_grad_norm) and max_grad_norm > 0.0):
@@ -77,6 +90,16 @@ class Adam(torch.optim.Optimizer):
         self._guard = None        # device tensors of the guarded step: the record {norm, coef, skip, skipped}, the step count
         self._guard_step = None   # and the norm's float64 workspace (allocated below, never by a default construction)
         self._partials = None
+        if guard_buffers is not None and not self._skip_nonfinite:
+            raise ValueError("guard_buffers needs skip_nonfinite=True: nothing else ever triggers the roll-back")
+        self._guard_buffers = guard_buffers
+        self._snap = None          # guard_buffers only, all created by the first snapshot: the flat device allocation,
+        self._snap_save = None     # the copy lists buffers -> snapshot and snapshot -> buffers (CopyDesc arrays),
+        self._snap_restore = None
+        self._snap_slots = None    # (name, the layer's buffer table, key) per protected buffer: the module tree is walked once
+        self._snap_bufs = None     # the protected buffers (and the addresses the lists were built for)
+        self._snap_ptrs = None
+        self._snap_fresh = False   # a snapshot was taken since the previous step()
         if amsgrad or maximize:
             raise ValueError("wsmgmap.optim.Adam implements amsgrad=False, maximize=False (what the reference trains with)")
         if lr < 0.0 or eps < 0.0 or weight_decay < 0.0 or not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
@@ -100,6 +123,72 @@ class Adam(torch.optim.Optimizer):
         self._guard_step = torch.full((), float(steps.pop() if steps else 0), device=dev, dtype=torch.float32)
         blocks = sum((p.numel() + ADAM_CHUNK - 1) // ADAM_CHUNK for p in params)
         self._partials = torch.empty(max(1, blocks), device=dev, dtype=torch.float64)
+
+    def _protected_buffers(self):
+        """[(qualified name, tensor)]: running_mean, running_var and num_batches_tracked of every BatchNorm layer below the
+        guarded module that tracks running statistics, in module order.  The module tree is walked ONCE (0.9 ms of host time for
+        the policy's 63 layers); afterwards the layers' buffer tables are read directly, which still sees a buffer that was
+        replaced (`module.to(...)`, `load_state_dict(assign=True)`)."""
+        if self._snap_slots is None:
+            self._snap_slots = [(f"{mname}.{bname}" if mname else bname, m._buffers, bname)
+                                for mname, m in self._guard_buffers.named_modules()
+                                if isinstance(m, torch.nn.modules.batchnorm._BatchNorm) and m.track_running_stats
+                                for bname in ("running_mean", "running_var", "num_batches_tracked")
+                                if m._buffers.get(bname) is not None]
+        return [(name, table[bname]) for name, table, bname in self._snap_slots]
+
+    def _build_snapshot(self, named):
+        """Check the protected buffers, lay them out in the flat allocation (16-byte slots: the copies take the vector path) and
+        write the two copy lists.  The allocation is made once; under stream capture it must already exist."""
+        what = "wsmgmap.optim.Adam(guard_buffers=...)"
+        if not named:
+            raise _abi.WsmgError(f"{what}: the module has no BatchNorm layer that tracks running statistics")
+        params = [p for group in self.param_groups for p in group["params"]]
+        dev = params[0].device
+        for name, b in named:
+            if not (b.is_cuda and b.device == dev and b.is_contiguous()):
+                raise _abi.WsmgError(f"{what}: buffer {name} must be a contiguous CUDA tensor on the parameters' device ({dev})")
+        offsets, total = [], 0
+        for _, b in named:
+            offsets.append(total)
+            total += (b.numel() * b.element_size() + 15) // 16 * 16
+        if self._snap is None or self._snap.numel() < total or self._snap.device != dev:
+            if torch.cuda.is_current_stream_capturing():
+                raise _abi.WsmgError(f"{what}: the snapshot storage does not exist yet; take a snapshot (zero_grad() or "
+                                     "snapshot_buffers()) before capturing into a graph")
+            with torch.cuda.device(dev):
+                self._snap = torch.empty(max(16, total), device=dev, dtype=torch.uint8)
+        base = self._snap.data_ptr()
+        save, restore = (_abi.CopyDesc * len(named))(), (_abi.CopyDesc * len(named))()
+        for sv, rs, off, (_, b) in zip(save, restore, offsets, named):
+            nbytes = b.numel() * b.element_size()
+            sv.dst, sv.src, sv.bytes = base + off, b.data_ptr(), nbytes
+            rs.dst, rs.src, rs.bytes = b.data_ptr(), base + off, nbytes
+        self._snap_save, self._snap_restore = save, restore
+        self._snap_bufs = [b for _, b in named]
+        self._snap_ptrs = [b.data_ptr() for b in self._snap_bufs]
+
+    @torch.no_grad()
+    def snapshot_buffers(self):
+        """Copy the protected buffers into the snapshot, on the current stream (one wsmg_copy_multi call: a launch per 32 buffers).
+        `zero_grad()` does this; call it directly in a loop that zeroes the gradients some other way, before the forward pass."""
+        if self._guard_buffers is None:
+            raise _abi.WsmgError("wsmgmap.optim.Adam.snapshot_buffers: the optimizer was constructed without guard_buffers")
+        if (self._snap_bufs is None or any(table[bname] is not b for (_, table, bname), b in zip(self._snap_slots, self._snap_bufs))
+                or [b.data_ptr() for b in self._snap_bufs] != self._snap_ptrs):
+            self._build_snapshot(self._protected_buffers())
+        dev = self._snap.device
+        with torch.cuda.device(dev):
+            _abi.call("wsmg_copy_multi", ctypes.cast(self._snap_save, ctypes.c_void_p), len(self._snap_save),
+                      ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        self._snap_fresh = True
+
+    def zero_grad(self, set_to_none=True):
+        """torch.optim.Optimizer.zero_grad; with guard_buffers it also takes the snapshot — the reference's update and
+        GraphedUpdate both call it in front of the forward pass, which is where the snapshot belongs."""
+        super().zero_grad(set_to_none=set_to_none)
+        if self._guard_buffers is not None:
+            self.snapshot_buffers()
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -158,6 +247,10 @@ class Adam(torch.optim.Optimizer):
         return loss
 
     def _guarded_step(self):
+        if self._guard_buffers is not None and not self._snap_fresh:
+            raise _abi.WsmgError("wsmgmap.optim.Adam(guard_buffers=...): no snapshot was taken since the previous step() — call "
+                                 "zero_grad() or snapshot_buffers() before the forward pass (an older snapshot would roll the "
+                                 "statistics back by more than one update)")
         groups, steps, dev = [], set(), None
         for group in self.param_groups:
             items = []
@@ -203,6 +296,8 @@ class Adam(torch.optim.Optimizer):
             if self._guard is None or self._guard.device != dev or self._partials.numel() < _norm_blocks(descs):
                 raise _abi.WsmgError("wsmgmap.optim.Adam: the guard's device state does not fit the stepped parameters (construct the "
                                      "optimizer over the CUDA parameters it steps)")
+            if self._guard_buffers is not None and self._snap.device != dev:
+                raise _abi.WsmgError("wsmgmap.optim.Adam(guard_buffers=...): the snapshot is not on the stepped parameters' device")
             guard, sd = ctypes.c_void_p(self._guard.data_ptr()), ctypes.c_void_p(self._guard_step.data_ptr())
             # the finalize advances the step count by 1 - skip: a skipped step does not advance the bias corrections
             _abi.call("wsmg_grad_norm_multi", descs, len(every), ctypes.c_void_p(self._partials.data_ptr()), self._partials.numel(),
@@ -213,7 +308,13 @@ class Adam(torch.optim.Optimizer):
                 _abi.call("wsmg_adam_step_multi_guarded", ctypes.byref(descs, at * ctypes.sizeof(_AdamDesc)), len(items),
                           float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), sd, guard, stream)
                 at += len(items)
-        torch.autograd.graph.increment_version([it[0] for it in every])
+            written = [it[0] for it in every]
+            if self._guard_buffers is not None:
+                _abi.call("wsmg_copy_multi_guarded", ctypes.cast(self._snap_restore, ctypes.c_void_p), len(self._snap_restore), guard,
+                          stream)
+                self._snap_fresh = False
+                written = written + self._snap_bufs
+        torch.autograd.graph.increment_version(written)
 
     @property
     def grad_norm(self):
