@@ -518,7 +518,8 @@ int wsmg_upsample2x_cat_bf16(const void* a, const void* b, void* y, int B, int H
 /* per-pixel cross-entropy of the semantic-hallucination head straight from the NHWC logits (policy.py:61-66:
  * F.cross_entropy(pred_sem_map, target, reduction='none')): logits [rows][32] (classes <= 32 valid channels, the rest
  * padding), target int64 [rows]; loss [rows] = logsumexp - logit[target].  bwd: dlogits [rows][32] =
- * (softmax - onehot) * gloss[row], padded channels 0. */
+ * (softmax - onehot) * gloss[row], padded channels 0.  A label outside [0, classes) (the int64 value itself; -100 is no
+ * ignore_index) makes loss[row] and all 32 channels of dlogits[row] NaN, as the fused classifier tail does. */
 int wsmg_ce_nhwc_fwd(const float* logits, const int64_t* target, int64_t rows, int classes, float* loss, wsmg_stream_t stream);
 int wsmg_ce_nhwc_bwd(const float* logits, const int64_t* target, const float* gloss, int64_t rows, int classes,
                      float* dlogits, wsmg_stream_t stream);

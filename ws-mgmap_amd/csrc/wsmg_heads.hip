@@ -125,7 +125,7 @@ __global__ __launch_bounds__(256) void dagger_loss_fwd_kernel(DaggerLoss a) {
   __shared__ float red[4];
   __shared__ float term[DL_CHUNK], wrow[DL_CHUNK];
   const int rows = a.T * a.N;
-  // chunks hold whole steps: tpc steps of N rows (N <= DL_CHUNK is checked by the host)
+  // chunks hold whole steps: tpc >= 8 steps of N rows (the entry point refuses N > 256: phase 2 gives every episode a thread)
   const int tpc = DL_CHUNK / a.N;
   float num = 0.f, den = 0.f;        // thread n < N: its episode
   for (int t0 = 0; t0 < a.T; t0 += tpc) {

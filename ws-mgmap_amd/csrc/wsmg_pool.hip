@@ -332,6 +332,9 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc64_kernel(const float* __rest
 // ---- fused per-pixel cross-entropy over NHWC logits (policy.py:61-66: F.cross_entropy(pred_sem_map, target,
 // reduction='none')): the 27 classes of a pixel are one 64/128-byte run of the 32-channel-padded conv output, so the
 // loss needs no NHWC->NCHW transpose and no materialised log-softmax.  One thread per pixel row.
+// A label outside [0, classes) — F.cross_entropy of the reference faults on it — makes that row's loss and its whole 32-wide
+// gradient row NaN, as the fused classifier tail does (wsmg_cls_tail.hip): loud, not a finite wrong number.  The int64 label
+// itself is compared (2^40 truncates to 0); -100 is not an ignore_index.
 template <class T>
 __global__ __launch_bounds__(256) void ce_nhwc_fwd_kernel(const T* __restrict__ logits, const int64_t* __restrict__ target,
                                                           int64_t rows, int classes, float* __restrict__ loss) {
@@ -349,14 +352,17 @@ __global__ __launch_bounds__(256) void ce_nhwc_fwd_kernel(const T* __restrict__ 
   float sum = 0.f;
 #pragma unroll
   for (int c = 0; c < 32; ++c) if (c < classes) sum += expf(v[c] - mx);
-  const int t = (int)target[r];
+  const int64_t lab = target[r];
+  const bool in_range = (uint64_t)lab < (uint64_t)classes;
+  const int t = in_range ? (int)lab : -1;
   float vt = 0.f;
 #pragma unroll
   for (int c = 0; c < 32; ++c) if (c == t) vt = v[c];
-  loss[r] = (mx + logf(sum)) - vt;
+  loss[r] = in_range ? (mx + logf(sum)) - vt : __builtin_nanf("");
 }
 
-// dlogits[r][c] = (softmax(logits[r])[c] - [c == target[r]]) * gscale[r / rows_per_sample]; padded channels get 0
+// dlogits[r][c] = (softmax(logits[r])[c] - [c == target[r]]) * gloss[r]; padded channels get 0; a row whose label is outside
+// [0, classes) gets NaN in all 32 channels
 template <class T>
 __global__ __launch_bounds__(256) void ce_nhwc_bwd_kernel(const T* __restrict__ logits, const int64_t* __restrict__ target,
                                                           const float* __restrict__ gloss, int64_t rows, int classes,
@@ -376,12 +382,19 @@ __global__ __launch_bounds__(256) void ce_nhwc_bwd_kernel(const T* __restrict__ 
 #pragma unroll
   for (int c = 0; c < 32; ++c) { v[c] = c < classes ? expf(v[c] - mx) : 0.f; sum += v[c]; }
   const float g = gloss[r], inv = 1.f / sum;
-  const int t = (int)target[r];
+  const int64_t lab = target[r];
+  const bool in_range = (uint64_t)lab < (uint64_t)classes;
+  const int t = in_range ? (int)lab : -1;
+  const float nan = __builtin_nanf("");
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     f32x4 q;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) { const int c = 4 * j + e; q[e] = c < classes ? (v[c] * inv - (c == t ? 1.f : 0.f)) * g : 0.f; }
+    for (int e = 0; e < 4; ++e) {
+      const int c = 4 * j + e;
+      const float d = c < classes ? (v[c] * inv - (c == t ? 1.f : 0.f)) * g : 0.f;
+      q[e] = in_range ? d : nan;
+    }
     st4(dlogits + r * 32 + 4 * j, q);
   }
 }

@@ -34,7 +34,11 @@ class _CrossEntropyNHWC(torch.autograd.Function):
 
 
 def cross_entropy_nhwc(logits, target, classes):
-    """F.cross_entropy(logits_nchw[:, :classes], target, reduction='none') computed from NHWC logits [..., 32]."""
+    """F.cross_entropy(logits_nchw[:, :classes], target, reduction='none') computed from NHWC logits [..., 32].
+    The contract for a label outside [0, classes), shared with `cls_tail`: `F.cross_entropy` of the reference faults on it; here
+    that row's loss is NaN and so is its whole 32-wide gradient row — loud, not a finite wrong number.  The int64 label itself is
+    compared, not a truncation of it.  -100 is NOT treated as `ignore_index`: the reference never produces it, and it poisons
+    its row like any other out-of-range label.  Rows with a label in range are unaffected; their padded channels get gradient 0."""
     return _CrossEntropyNHWC.apply(logits.contiguous(), target.contiguous(), classes)
 
 
