@@ -342,6 +342,25 @@ int wsmg_grad_norm_multi(const WsmgAdamDesc* descs, int n, double* partials, lon
                          int skip_nonfinite, float* guard, float* step_dev, wsmg_stream_t stream);
 int wsmg_adam_step_multi_guarded(const WsmgAdamDesc* descs, int n, float lr, float beta1, float beta2, float eps, float weight_decay,
                                  const float* step_dev, const float* guard, wsmg_stream_t stream);
+/* The same two steps with the HYPER-PARAMETERS read from device memory: a captured HIP graph freezes kernel arguments, so a
+ * learning-rate schedule, a warm-up or a new clip threshold applied to the torch.optim.Adam of common_trainer.py:67-69 between
+ * updates (the reference steps it eagerly at dagger_trainer.py:536, where `param_groups` edits simply take effect) would otherwise
+ * never reach a replayed step.  The hyper record is a float32 device array of 8-float rows that the CALLER writes (outside the
+ * graph) and no kernel ever writes:
+ *   row g, one per parameter group:  {lr, beta1, beta2, eps, weight_decay, 0, 0, 0}
+ *   one more row, for the guard:     {max_grad_norm, or 0 for "no clipping", 0, 0, 0, 0, 0, 0, 0}
+ * wsmg_adam_step_multi_hyper: wsmg_adam_step_multi_dev (guard NULL) or wsmg_adam_step_multi_guarded (guard = the guard record) with
+ * lr, beta1, beta2, eps, weight_decay taken from hyper_row, the group's row; 1 - beta in float and the bias corrections in double
+ * from *step_dev, as the by-value forms compute them: equal values give bit-identical results.
+ * wsmg_grad_norm_multi_hyper: wsmg_grad_norm_multi with max_norm taken from hyper_guard_row[0], the guard's row.
+ * Both: WSMG_EINVAL for a NULL or not 4-byte aligned row / step_dev / guard (the guard of the step may be NULL), a negative count,
+ * a NULL or not 4-byte aligned tensor of a non-empty descriptor; WSMG_ENOMEM for a short partials buffer — every descriptor of every
+ * launch is checked before the first launch, a rejected call launches nothing. */
+int wsmg_adam_step_multi_hyper(const WsmgAdamDesc* descs, int n, const float* hyper_row, const float* step_dev, const float* guard,
+                               wsmg_stream_t stream);
+int wsmg_grad_norm_multi_hyper(const WsmgAdamDesc* descs, int n, double* partials, long long partials_cap,
+                               const float* hyper_guard_row, int skip_nonfinite, float* guard, float* step_dev,
+                               wsmg_stream_t stream);
 
 /* Tests / tools: tile of the LDS-window kernel that serves 3x3 stride-1 pad-1 layers with Cout % 128 == 0, Cin % 32 == 0, Cin >= 64 and
  * B*H*W >= 65536 (0 = off -> implicit-GEMM kernel, 1 = tile chosen by shape, 256 or 512 pixels per workgroup; default 1 or

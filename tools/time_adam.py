@@ -4,6 +4,9 @@ per step, arms interleaved over --rounds rounds of --steps steps:
 
     torch-foreach, torch-fused   torch.optim.Adam (multi-tensor default / fused=True)
     wsmg                         wsmgmap.optim.Adam, the unguarded step (3 launches)
+    wsmg-dev                     wsmgmap.optim.Adam(capturable=True): the step count on the device (the form a HIP graph captures)
+    wsmg-dev-hyper               the same with hyper_on_device=True: lr, betas, eps, weight_decay read from the device record
+    wsmg-guarded-hyper           wsmg-guarded with hyper_on_device=True (max_grad_norm read from the record too)
     wsmg-guarded                 wsmgmap.optim.Adam(max_grad_norm=..., skip_nonfinite=True): norm launches + finalize + guarded step
     wsmg-guarded-buffers         the same with guard_buffers=policy: snapshot_buffers() (what zero_grad() adds) + the step with the
                                  conditional roll-back of the BatchNorm statistics behind it (steps taken: the roll-back returns at once)
@@ -48,8 +51,12 @@ for name in args.arms.split(","):
         opt = torch.optim.Adam(policy.parameters(), lr=1e-6, fused=True)
     elif name in ("wsmg", "clip+wsmg"):
         opt = WsmgAdam(policy.parameters(), lr=1e-6)
+    elif name in ("wsmg-dev", "wsmg-dev-hyper"):
+        opt = WsmgAdam(policy.parameters(), lr=1e-6, capturable=True, **({"hyper_on_device": True} if name.endswith("-hyper") else {}))
     elif name == "wsmg-guarded":
         opt = WsmgAdam(policy.parameters(), lr=1e-6, max_grad_norm=0.5 * norm, skip_nonfinite=True)
+    elif name == "wsmg-guarded-hyper":
+        opt = WsmgAdam(policy.parameters(), lr=1e-6, max_grad_norm=0.5 * norm, skip_nonfinite=True, hyper_on_device=True)
     elif name == "wsmg-guarded-buffers":
         opt = WsmgAdam(policy.parameters(), lr=1e-6, max_grad_norm=0.5 * norm, skip_nonfinite=True, guard_buffers=policy)
     else:

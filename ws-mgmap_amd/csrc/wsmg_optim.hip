@@ -13,12 +13,18 @@
 // atomics), grad_guard_finalize_kernel adds them in a fixed order and writes the guard record {norm, coef, skip, skipped} and
 // the step count, and adam_multi_guarded_kernel returns before its first load when `skip` is set and reads g * coef otherwise
 // (torch.nn.utils.clip_grad_norm_'s arithmetic, without writing the gradients).  No host synchronisation anywhere.
+//
+// The HYPER forms (wsmg_adam_step_multi_hyper, wsmg_grad_norm_multi_hyper) read lr, betas, eps, weight_decay and max_grad_norm from
+// a float32 record in device memory instead of their kernel arguments, which a captured HIP graph freezes: the host refreshes the
+// record between replays (wsmgmap.optim.Adam(hyper_on_device=True).sync_hyper()).  No kernel writes the record.
 #include "wsmg_common.h"
 
 namespace {
 
 // ADAM_MAX = 48 tensors per launch (kernel-argument table): wsmg_common.h
 constexpr int ADAM_CHUNK = 4096;  // elements per workgroup
+// The hyper record (include/wsmgmap.h): one 8-float row per parameter group, then the guard's row.
+enum { HYPER_LR = 0, HYPER_BETA1 = 1, HYPER_BETA2 = 2, HYPER_EPS = 3, HYPER_WD = 4, HYPER_MAX_NORM = 0 };
 
 struct AdamBatch {
   float* p[ADAM_MAX];
@@ -32,9 +38,15 @@ struct AdamBatch {
   const float* step_dev;   // or null: the step count lives on the device (HIP-graph replay: the arguments are frozen at capture) and
   float lr, beta1;         //          the bias corrections are computed from it here
   const float* guard;      // or null: the guard record of grad_guard_finalize_kernel (read by adam_multi_guarded_kernel only)
+  const float* hyper;      // or null: this group's row of the hyper record {lr, beta1, beta2, eps, weight_decay, 0, 0, 0} (read by the
+};                         //          _hyper kernels only, which then ignore every by-value hyper-parameter above)
+
+struct AdamHyper {         // what adam1 reads of AdamBatch, as the _hyper kernels derive it from the record's row
+  float beta1c, beta2, beta2c, eps, wd;
 };
 
-template <bool GUARD>
+// VEC: the call sits in the 16-byte loop (used by the AdamHyper form below only).
+template <bool GUARD, bool VEC>
 __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, const AdamBatch& b, float lr_bc1, float sqrt_bc2,
                                       float coef) {
   if (GUARD) g *= coef;
@@ -45,21 +57,28 @@ __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, con
   p = p - lr_bc1 * (m / denom);
 }
 
-// GUARD = false is the unguarded step, the code it was before the guard existed (the guard pointer is not read); GUARD = true
-// reads skip and coef once, before anything else.
-template <bool GUARD>
-__device__ __forceinline__ void adam_multi(const AdamBatch& b) {
-  float coef = 1.f;
-  if (GUARD) {
-    if (b.guard[GUARD_SKIP] != 0.f) return;     // a skipped step: no load of p / m / v, nothing written
-    coef = b.guard[GUARD_COEF];
-  }
-  float lr_bc1 = b.lr_bc1, sqrt_bc2 = b.sqrt_bc2;
-  if (b.step_dev) {   // 1 - beta^step in double, as the host path does
-    const double st = (double)*b.step_dev;
-    lr_bc1 = (float)((double)b.lr / (1.0 - pow((double)b.beta1, st)));
-    sqrt_bc2 = (float)sqrt(1.0 - pow((double)b.beta2, st));
-  }
+// The same element step for the _hyper kernels, which must give the by-value kernels' bits.  Above, which products are fused into
+// which sums is the compiler's choice (-ffp-contract=fast), and it depends on where the operands live: with beta2 and beta2c
+// adjacent in the kernel arguments it computes v as fma(v, beta2, (beta2c g) g) in the 16-byte loop and as fma(g, beta2c g, v beta2)
+// in the two scalar loops, m as fma(beta1c, g - m, m) and p as fma(-lr_bc1, m / denom, p) everywhere, and g * coef as a product of
+// its own.  With the operands in the registers the record's loads leave them in, it chose otherwise (v unfused in the scalar loops),
+// so the forms are spelled out here and nothing else may be contracted.  tests/test_gpu_adam_hyper.py compares the bits on every path.
+template <bool GUARD, bool VEC>
+__device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, const AdamHyper& h, float lr_bc1, float sqrt_bc2,
+                                      float coef) {
+#pragma clang fp contract(off)
+  if (GUARD) g *= coef;
+  if (h.wd != 0.f) g = fmaf(h.wd, p, g);
+  m = fmaf(h.beta1c, g - m, m);
+  const float gc = h.beta2c * g;
+  v = VEC ? fmaf(v, h.beta2, gc * g) : fmaf(g, gc, v * h.beta2);
+  const float denom = sqrtf(v) / sqrt_bc2 + h.eps;
+  p = fmaf(-lr_bc1, m / denom, p);
+}
+
+// One workgroup's 4 096 elements of its tensor; h holds the hyper-parameters adam1 reads.
+template <bool GUARD, class H>
+__device__ __forceinline__ void adam_chunk(const AdamBatch& b, const H& h, float lr_bc1, float sqrt_bc2, float coef) {
   int lo = 0, hi = b.count;          // tensor t with first_block[t] <= blockIdx.x < first_block[t + 1]
   while (hi - lo > 1) {
     const int mid = (lo + hi) >> 1;
@@ -81,19 +100,57 @@ __device__ __forceinline__ void adam_multi(const AdamBatch& b) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         float pj = pp[j], mj = mm[j], vj = vv[j];
-        adam1<GUARD>(pj, gg[j], mj, vj, b, lr_bc1, sqrt_bc2, coef);
+        adam1<GUARD, true>(pj, gg[j], mj, vj, h, lr_bc1, sqrt_bc2, coef);
         pp[j] = pj; mm[j] = mj; vv[j] = vj;
       }
       st4(p + i, pp); st4(m + i, mm); st4(v + i, vv);
     }
-    for (long long i = nv + threadIdx.x; i < i1; i += 256) adam1<GUARD>(p[i], g[i], m[i], v[i], b, lr_bc1, sqrt_bc2, coef);
+    for (long long i = nv + threadIdx.x; i < i1; i += 256) adam1<GUARD, false>(p[i], g[i], m[i], v[i], h, lr_bc1, sqrt_bc2, coef);
   } else {
-    for (long long i = i0 + threadIdx.x; i < i1; i += 256) adam1<GUARD>(p[i], g[i], m[i], v[i], b, lr_bc1, sqrt_bc2, coef);
+    for (long long i = i0 + threadIdx.x; i < i1; i += 256) adam1<GUARD, false>(p[i], g[i], m[i], v[i], h, lr_bc1, sqrt_bc2, coef);
   }
 }
 
-__global__ __launch_bounds__(256) void adam_multi_kernel(AdamBatch b) { adam_multi<false>(b); }
-__global__ __launch_bounds__(256) void adam_multi_guarded_kernel(AdamBatch b) { adam_multi<true>(b); }
+// GUARD = false is the unguarded step, the code it was before the guard existed (the guard pointer is not read); GUARD = true
+// reads skip and coef once, before anything else.  HYPER = false takes the hyper-parameters from the kernel arguments, the code it
+// was before the record existed (the hyper pointer is not read); HYPER = true reads its group's row once, here, through a
+// wave-uniform address, and derives 1 - beta in float and the bias corrections in double from *step_dev with the expressions of
+// adam_launch and of the step_dev branch below: equal values give equal bits.
+template <bool GUARD, bool HYPER>
+__device__ __forceinline__ void adam_multi(const AdamBatch& b) {
+  float coef = 1.f;
+  if (GUARD) {
+    if (b.guard[GUARD_SKIP] != 0.f) return;     // a skipped step: no load of p / m / v, nothing written
+    coef = b.guard[GUARD_COEF];
+  }
+  if (HYPER) {
+    const float* __restrict__ row = b.hyper;
+    const float lr = row[HYPER_LR], beta1 = row[HYPER_BETA1];
+    AdamHyper h;
+    h.beta2 = row[HYPER_BETA2];
+    h.eps = row[HYPER_EPS];
+    h.wd = row[HYPER_WD];
+    h.beta1c = 1.f - beta1;
+    h.beta2c = 1.f - h.beta2;
+    const double st = (double)*b.step_dev;
+    const float lr_bc1 = (float)((double)lr / (1.0 - pow((double)beta1, st)));
+    const float sqrt_bc2 = (float)sqrt(1.0 - pow((double)h.beta2, st));
+    adam_chunk<GUARD>(b, h, lr_bc1, sqrt_bc2, coef);
+    return;
+  }
+  float lr_bc1 = b.lr_bc1, sqrt_bc2 = b.sqrt_bc2;
+  if (b.step_dev) {   // 1 - beta^step in double, as the host path does
+    const double st = (double)*b.step_dev;
+    lr_bc1 = (float)((double)b.lr / (1.0 - pow((double)b.beta1, st)));
+    sqrt_bc2 = (float)sqrt(1.0 - pow((double)b.beta2, st));
+  }
+  adam_chunk<GUARD>(b, b, lr_bc1, sqrt_bc2, coef);
+}
+
+__global__ __launch_bounds__(256) void adam_multi_kernel(AdamBatch b) { adam_multi<false, false>(b); }
+__global__ __launch_bounds__(256) void adam_multi_guarded_kernel(AdamBatch b) { adam_multi<true, false>(b); }
+__global__ __launch_bounds__(256) void adam_multi_hyper_kernel(AdamBatch b) { adam_multi<false, true>(b); }
+__global__ __launch_bounds__(256) void adam_multi_guarded_hyper_kernel(AdamBatch b) { adam_multi<true, true>(b); }
 
 // ---- the guard: global gradient norm -> {norm, coef, skip, skipped}
 
@@ -143,9 +200,8 @@ __global__ __launch_bounds__(256) void grad_sumsq_multi_kernel(GradBatch b) {
 // One workgroup: every partial of every launch, strided per thread, then the fixed tree.  Finiteness is judged on the float32 norm
 // and the clip coefficient is clip_grad_norm_'s (max_norm / (norm + 1e-6), clamped to 1; a NaN norm gives a NaN coefficient there
 // too).  The step count advances here, by 1 - skip: a skipped step does not advance the bias corrections.
-__global__ __launch_bounds__(256) void grad_guard_finalize_kernel(const double* __restrict__ partials, int total, float max_norm,
-                                                                   int skip_nonfinite, float* __restrict__ guard,
-                                                                   float* __restrict__ step_dev) {
+__device__ __forceinline__ void guard_finalize(const double* __restrict__ partials, int total, float max_norm, int skip_nonfinite,
+                                               float* __restrict__ guard, float* __restrict__ step_dev) {
   __shared__ double red[4];
   double acc = 0.0;
   for (int i = threadIdx.x; i < total; i += 256) acc += partials[i];
@@ -166,11 +222,24 @@ __global__ __launch_bounds__(256) void grad_guard_finalize_kernel(const double* 
   }
 }
 
+__global__ __launch_bounds__(256) void grad_guard_finalize_kernel(const double* __restrict__ partials, int total, float max_norm,
+                                                                   int skip_nonfinite, float* __restrict__ guard,
+                                                                   float* __restrict__ step_dev) {
+  guard_finalize(partials, total, max_norm, skip_nonfinite, guard, step_dev);
+}
+
+// max_norm from the hyper record's guard row {max_grad_norm or 0 for "no clipping", 0, ...}: the same sums, arithmetic and writes.
+__global__ __launch_bounds__(256) void grad_guard_finalize_hyper_kernel(const double* __restrict__ partials, int total,
+                                                                         const float* __restrict__ hyper_guard_row, int skip_nonfinite,
+                                                                         float* __restrict__ guard, float* __restrict__ step_dev) {
+  guard_finalize(partials, total, hyper_guard_row[HYPER_MAX_NORM], skip_nonfinite, guard, step_dev);
+}
+
 }  // namespace
 
 static int adam_launch(const WsmgAdamDesc* descs, int n, float lr, float beta1, float beta2, float eps, float weight_decay,
                        double bias_correction1, double bias_correction2, const float* step_dev, const float* guard,
-                       wsmg_stream_t s) {
+                       const float* hyper, wsmg_stream_t s) {
   if (n < 0 || (n > 0 && !descs)) return WSMG_EINVAL;
   if (!step_dev && (!(bias_correction1 > 0.0) || !(bias_correction2 > 0.0))) return WSMG_EINVAL;
   for (int i = 0; i < n;) {
@@ -201,7 +270,10 @@ static int adam_launch(const WsmgAdamDesc* descs, int n, float lr, float beta1, 
     b.lr = lr;
     b.beta1 = beta1;
     b.guard = guard;
-    if (guard) hipLaunchKernelGGL(adam_multi_guarded_kernel, dim3((unsigned)blocks), dim3(256), 0, wsmg_s(s), b);
+    b.hyper = hyper;
+    if (hyper && guard) hipLaunchKernelGGL(adam_multi_guarded_hyper_kernel, dim3((unsigned)blocks), dim3(256), 0, wsmg_s(s), b);
+    else if (hyper) hipLaunchKernelGGL(adam_multi_hyper_kernel, dim3((unsigned)blocks), dim3(256), 0, wsmg_s(s), b);
+    else if (guard) hipLaunchKernelGGL(adam_multi_guarded_kernel, dim3((unsigned)blocks), dim3(256), 0, wsmg_s(s), b);
     else hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, wsmg_s(s), b);
   }
   WSMG_RETURN_LAUNCH();
@@ -209,7 +281,7 @@ static int adam_launch(const WsmgAdamDesc* descs, int n, float lr, float beta1, 
 
 extern "C" int wsmg_adam_step_multi(const WsmgAdamDesc* descs, int n, float lr, float beta1, float beta2, float eps, float weight_decay,
                                     double bias_correction1, double bias_correction2, wsmg_stream_t s) {
-  return adam_launch(descs, n, lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2, nullptr, nullptr, s);
+  return adam_launch(descs, n, lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2, nullptr, nullptr, nullptr, s);
 }
 
 // The same step with the step COUNT read from device memory (one float32, already incremented for this step): what a captured
@@ -217,7 +289,7 @@ extern "C" int wsmg_adam_step_multi(const WsmgAdamDesc* descs, int n, float lr, 
 extern "C" int wsmg_adam_step_multi_dev(const WsmgAdamDesc* descs, int n, float lr, float beta1, float beta2, float eps,
                                         float weight_decay, const float* step_dev, wsmg_stream_t s) {
   if (!step_dev) return WSMG_EINVAL;
-  return adam_launch(descs, n, lr, beta1, beta2, eps, weight_decay, 0.0, 0.0, step_dev, nullptr, s);
+  return adam_launch(descs, n, lr, beta1, beta2, eps, weight_decay, 0.0, 0.0, step_dev, nullptr, nullptr, s);
 }
 
 // The _dev form behind a guard record (wsmg_grad_norm_multi on the same stream, before it): nothing is written when the record's
@@ -225,13 +297,33 @@ extern "C" int wsmg_adam_step_multi_dev(const WsmgAdamDesc* descs, int n, float 
 extern "C" int wsmg_adam_step_multi_guarded(const WsmgAdamDesc* descs, int n, float lr, float beta1, float beta2, float eps,
                                             float weight_decay, const float* step_dev, const float* guard, wsmg_stream_t s) {
   if (!step_dev || !guard) return WSMG_EINVAL;
-  return adam_launch(descs, n, lr, beta1, beta2, eps, weight_decay, 0.0, 0.0, step_dev, guard, s);
+  return adam_launch(descs, n, lr, beta1, beta2, eps, weight_decay, 0.0, 0.0, step_dev, guard, nullptr, s);
+}
+
+// The _dev / _guarded step (guard null / not null) with lr, beta1, beta2, eps and weight_decay read from hyper_row, one 8-float row
+// of the hyper record in device memory.  Unlike the forms above, which check a table as they fill it, every descriptor of every
+// launch is checked here before the first launch (and the workgroup total against 2^30, which is stricter than per launch).
+extern "C" int wsmg_adam_step_multi_hyper(const WsmgAdamDesc* descs, int n, const float* hyper_row, const float* step_dev,
+                                          const float* guard, wsmg_stream_t s) {
+  if (n < 0 || (n > 0 && !descs) || !hyper_row || !step_dev) return WSMG_EINVAL;
+  if (((uintptr_t)hyper_row & 3) || ((uintptr_t)step_dev & 3) || ((uintptr_t)guard & 3)) return WSMG_EINVAL;
+  long long total = 0;
+  for (int i = 0; i < n; ++i) {
+    const WsmgAdamDesc& d = descs[i];
+    if (d.n < 0 || (d.n > 0 && (!d.param || !d.grad || !d.exp_avg || !d.exp_avg_sq))) return WSMG_EINVAL;
+    if (d.n > 0 && (((uintptr_t)d.param | (uintptr_t)d.grad | (uintptr_t)d.exp_avg | (uintptr_t)d.exp_avg_sq) & 3)) return WSMG_EINVAL;
+    if (d.n > (1ll << 30) * ADAM_CHUNK) return WSMG_EINVAL;
+    total += (d.n + ADAM_CHUNK - 1) / ADAM_CHUNK;
+    if (total > (1ll << 30)) return WSMG_EINVAL;
+  }
+  return adam_launch(descs, n, 0.f, 0.f, 0.f, 0.f, 0.f, 0.0, 0.0, step_dev, guard, hyper_row, s);
 }
 
 // Global L2 norm of the descs' gradients (param / exp_avg / exp_avg_sq are not read) into the guard record.  Every argument is
 // checked, and the partials' capacity against the total workgroup count, before the first launch.
-extern "C" int wsmg_grad_norm_multi(const WsmgAdamDesc* descs, int n, double* partials, long long partials_cap, float max_norm,
-                                    int skip_nonfinite, float* guard, float* step_dev, wsmg_stream_t s) {
+// hyper_guard_row (or null): max_norm is read from it on the device and the by-value max_norm is ignored.
+static int grad_norm_launch(const WsmgAdamDesc* descs, int n, double* partials, long long partials_cap, float max_norm,
+                            const float* hyper_guard_row, int skip_nonfinite, float* guard, float* step_dev, wsmg_stream_t s) {
   if (n < 0 || (n > 0 && !descs) || !guard || !partials || partials_cap < 0 || !(max_norm >= 0.f)) return WSMG_EINVAL;
   if (((uintptr_t)partials & 7) || ((uintptr_t)guard & 3) || ((uintptr_t)step_dev & 3)) return WSMG_EINVAL;
   long long total = 0;
@@ -259,7 +351,24 @@ extern "C" int wsmg_grad_norm_multi(const WsmgAdamDesc* descs, int n, double* pa
     hipLaunchKernelGGL(grad_sumsq_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, wsmg_s(s), b);
     base += blocks;
   }
-  hipLaunchKernelGGL(grad_guard_finalize_kernel, dim3(1), dim3(256), 0, wsmg_s(s), (const double*)partials, base, max_norm,
-                     skip_nonfinite, guard, step_dev);
+  if (hyper_guard_row)
+    hipLaunchKernelGGL(grad_guard_finalize_hyper_kernel, dim3(1), dim3(256), 0, wsmg_s(s), (const double*)partials, base,
+                       hyper_guard_row, skip_nonfinite, guard, step_dev);
+  else
+    hipLaunchKernelGGL(grad_guard_finalize_kernel, dim3(1), dim3(256), 0, wsmg_s(s), (const double*)partials, base, max_norm,
+                       skip_nonfinite, guard, step_dev);
   WSMG_RETURN_LAUNCH();
+}
+
+extern "C" int wsmg_grad_norm_multi(const WsmgAdamDesc* descs, int n, double* partials, long long partials_cap, float max_norm,
+                                    int skip_nonfinite, float* guard, float* step_dev, wsmg_stream_t s) {
+  return grad_norm_launch(descs, n, partials, partials_cap, max_norm, nullptr, skip_nonfinite, guard, step_dev, s);
+}
+
+// wsmg_grad_norm_multi with max_norm read from the hyper record's guard row in device memory (a value <= 0 there: no clipping).
+extern "C" int wsmg_grad_norm_multi_hyper(const WsmgAdamDesc* descs, int n, double* partials, long long partials_cap,
+                                          const float* hyper_guard_row, int skip_nonfinite, float* guard, float* step_dev,
+                                          wsmg_stream_t s) {
+  if (!hyper_guard_row || ((uintptr_t)hyper_guard_row & 3)) return WSMG_EINVAL;
+  return grad_norm_launch(descs, n, partials, partials_cap, 0.f, hyper_guard_row, skip_nonfinite, guard, step_dev, s);
 }

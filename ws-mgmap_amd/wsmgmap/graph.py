@@ -119,7 +119,9 @@ class GraphedAct:
 class GraphedUpdate:
     def __init__(self, policy, optimizer, loss_fn, eager_calls=3):
         """loss_fn(pred, aux_loss, observations, weights) -> scalar loss tensor.  The first `eager_calls` updates run eagerly
-        (first-call initialisations of the library and of the allocator must not happen under capture)."""
+        (first-call initialisations of the library and of the allocator must not happen under capture).  With
+        `wsmgmap.optim.Adam(..., hyper_on_device=True)`, `param_groups` edits and learning-rate schedulers take effect at the next
+        call (without the flag a replay steps with the values of its capture)."""
         if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
             raise _abi.WsmgError("GraphedUpdate: data-parallel updates are not captured (the gradient exchange stays eager)")
         self.policy, self.optimizer, self.loss_fn = policy, optimizer, loss_fn
@@ -233,6 +235,8 @@ class GraphedUpdate:
                 rnn_hidden_states.copy_(h)
             cur.wait_stream(self._stream)
             return loss
+        if hasattr(self.optimizer, "sync_hyper"):
+            self.optimizer.sync_hyper()      # the hyper record follows param_groups: before a capture and before every replay
         key = self._signature(observations, rnn_hidden_states, prev_actions, masks, weights, dd)
         g = self._graphs.pop(key, None)
         if g is None:

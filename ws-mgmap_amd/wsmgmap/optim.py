@@ -12,7 +12,12 @@ reads — no host synchronisation, capturable in a HIP graph.  `global_grad_norm
 
 `Adam(skip_nonfinite=True, guard_buffers=module)` extends the skip to what the forward pass already wrote: `zero_grad()` snapshots the
 BatchNorm running statistics below `module` on the device (wsmg_copy_multi), and a skipped step copies them back
-(wsmg_copy_multi_guarded, which reads the same guard record and writes nothing after a step that was taken)."""
+(wsmg_copy_multi_guarded, which reads the same guard record and writes nothing after a step that was taken).
+
+`Adam(capturable=True or a guard option, hyper_on_device=True)` keeps `lr`, `betas`, `eps`, `weight_decay` of every parameter group
+and `max_grad_norm` in a small device record that the kernels read (wsmg_adam_step_multi_hyper, wsmg_grad_norm_multi_hyper): a
+captured step then follows `param_groups` edits and `torch.optim.lr_scheduler` steps, which kernel arguments frozen at capture
+cannot.  `sync_hyper()` refreshes the record, outside the graph; an eager `step()` and `GraphedUpdate` call it themselves."""
 import ctypes
 import math
 
@@ -28,6 +33,18 @@ class _AdamDesc(ctypes.Structure):
 
 ADAM_CHUNK = 4096         # elements per workgroup (csrc/wsmg_optim.hip): one float64 partial each in the norm's workspace
 ADAM_MAX = 48             # tensors (or copies) per launch (csrc/wsmg_common.h): longer lists are cut into several launches
+HYPER_ROW = 8             # floats per row of the hyper record (include/wsmgmap.h): {lr, beta1, beta2, eps, weight_decay, 0, 0, 0} per
+#                           parameter group, then the guard's row {max_grad_norm or 0, 0, ...}
+
+
+def _check_max_grad_norm(max_grad_norm):
+    if max_grad_norm is not None and not (math.isfinite(max_grad_norm) and max_grad_norm > 0.0):
+        raise ValueError(f"invalid max_grad_norm: {max_grad_norm} (a finite positive number, or None for no clipping)")
+
+
+def _check_hyper(lr, betas, eps, weight_decay):
+    if lr < 0.0 or eps < 0.0 or weight_decay < 0.0 or not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+        raise ValueError(f"invalid Adam hyper-parameters: lr={lr} betas={betas} eps={eps} weight_decay={weight_decay}")
 
 
 def _norm_blocks(descs):
@@ -60,7 +77,7 @@ def global_grad_norm(params):
 
 class Adam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, maximize=False,
-                 capturable=False, max_grad_norm=None, skip_nonfinite=False, guard_buffers=None):
+                 capturable=False, max_grad_norm=None, skip_nonfinite=False, guard_buffers=None, hyper_on_device=False):
         """capturable=True: the step count also lives in a device scalar (one per parameter group, incremented on the device)
         and the kernel computes the bias corrections from it — the form `wsmgmap.graph.GraphedUpdate` captures into a HIP graph
         (kernel arguments are frozen at capture).  All stepped parameters of a group must then share one step count.
@@ -79,11 +96,19 @@ class Adam(torch.optim.Optimizer):
         allocation, on the current stream; the guarded step copies them back when, and only when, the guard record says the step
         was skipped.  Both are device launches behind the same record: no host synchronisation, capturable together with the
         step (after one eager snapshot: the allocation is never made under capture).  A `step()` with no snapshot since the
-        previous one raises.  The snapshot is not optimizer state: `state_dict()` does not hold it."""
+        previous one raises.  The snapshot is not optimizer state: `state_dict()` does not hold it.
+
+        hyper_on_device=True (needs capturable=True or the guarded step: only those keep the step count on the device): the
+        kernels read `lr`, `betas`, `eps`, `weight_decay` of their parameter group, and `max_grad_norm`, from a float32 record in
+        device memory, not from their launch arguments, so a step captured in a HIP graph follows later `param_groups` edits,
+        `torch.optim.lr_scheduler` steps and assignments to `max_grad_norm`.  `sync_hyper()` compares those values with a host
+        mirror and, if one changed, refreshes the record with one asynchronous copy on the current stream: an eager `step()` and
+        `GraphedUpdate` call it; around a graph of your own (`torch.cuda.graph`) call it before each replay.  Under capture
+        nothing can be copied: a `step()` whose values differ from the mirror raises there.  Same arithmetic, bit for bit, as
+        without the flag.  The record has one row per parameter group: `add_param_group` is refused after construction."""
         self._capturable = bool(capturable)
         self._step_dev = {}
-        if max_grad_norm is not None and not (math.isfinite(max_grad_norm) and max_grad_norm > 0.0):
-            raise ValueError(f"invalid max_grad_norm: {max_grad_norm} (a finite positive number, or None for no clipping)")
+        _check_max_grad_norm(max_grad_norm)
         self._max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self._skip_nonfinite = bool(skip_nonfinite)
         self._guarded = self._max_grad_norm is not None or self._skip_nonfinite
@@ -100,13 +125,24 @@ class Adam(torch.optim.Optimizer):
         self._snap_bufs = None     # the protected buffers (and the addresses the lists were built for)
         self._snap_ptrs = None
         self._snap_fresh = False   # a snapshot was taken since the previous step()
+        self._hyper_on_device = bool(hyper_on_device)
+        if self._hyper_on_device and not (self._capturable or self._guarded):
+            raise ValueError("hyper_on_device=True needs capturable=True or the guarded step (max_grad_norm / skip_nonfinite): only "
+                             "those keep the step count on the device, which the record-reading kernels take it from")
+        self._hyper = None         # hyper_on_device only: the device record, a pinned staging tensor of its size, the host mirror of
+        self._hyper_stage = None   # what the record holds (one tuple per row) and the event behind the last copy out of the staging
+        self._hyper_mirror = None  # tensor (allocated by _reset_hyper, never by a default construction)
+        self._hyper_event = None
+        self._hyper_fixed = False  # the record's rows are laid out: no further parameter group
         if amsgrad or maximize:
             raise ValueError("wsmgmap.optim.Adam implements amsgrad=False, maximize=False (what the reference trains with)")
-        if lr < 0.0 or eps < 0.0 or weight_decay < 0.0 or not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
-            raise ValueError(f"invalid Adam hyper-parameters: lr={lr} betas={betas} eps={eps} weight_decay={weight_decay}")
+        _check_hyper(lr, betas, eps, weight_decay)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False))
         if self._guarded:
             self._reset_guard()
+        if self._hyper_on_device:
+            self._reset_hyper()
+            self._hyper_fixed = True
 
     def _reset_guard(self):
         """(Re-)create the guard's device tensors from the host-side step counts: at construction and after load_state_dict, so
@@ -123,6 +159,113 @@ class Adam(torch.optim.Optimizer):
         self._guard_step = torch.full((), float(steps.pop() if steps else 0), device=dev, dtype=torch.float32)
         blocks = sum((p.numel() + ADAM_CHUNK - 1) // ADAM_CHUNK for p in params)
         self._partials = torch.empty(max(1, blocks), device=dev, dtype=torch.float64)
+
+    def _reset_hyper(self):
+        """(Re-)create the hyper record, its staging tensor and the mirror from `param_groups` and `max_grad_norm`: at construction
+        and after load_state_dict, where the guard's tensors are made — never in step()."""
+        self._hyper = self._hyper_stage = self._hyper_mirror = self._hyper_event = None
+        params = [p for group in self.param_groups for p in group["params"]]
+        if not params or not all(p.is_cuda for p in params):
+            return                 # step() refuses such parameters
+        dev = params[0].device
+        n = (len(self.param_groups) + 1) * HYPER_ROW
+        with torch.cuda.device(dev):
+            self._hyper = torch.zeros(n, device=dev, dtype=torch.float32)
+            self._hyper_stage = torch.zeros(n, dtype=torch.float32, pin_memory=True)
+            self.sync_hyper()
+
+    def _hyper_values(self):
+        """What the record should hold now, one tuple per row, validated with the constructor's rules (ValueError)."""
+        rows = []
+        for group in self.param_groups:
+            lr, (b1, b2), eps, wd = float(group["lr"]), group["betas"], float(group["eps"]), float(group["weight_decay"])
+            b1, b2 = float(b1), float(b2)
+            _check_hyper(lr, (b1, b2), eps, wd)
+            rows.append((lr, b1, b2, eps, wd))
+        _check_max_grad_norm(self._max_grad_norm)
+        rows.append((self._max_grad_norm or 0.0,))
+        return rows
+
+    def _hyper_is_stale(self, rows):
+        if self._hyper is not None and len(rows) * HYPER_ROW != self._hyper.numel():
+            raise _abi.WsmgError("wsmgmap.optim.Adam(hyper_on_device=True): the number of parameter groups changed since the hyper "
+                                 "record was laid out (one row per group)")
+        return rows != self._hyper_mirror
+
+    def sync_hyper(self):
+        """hyper_on_device=True: bring the device record up to `param_groups` (lr, betas, eps, weight_decay; a tensor-valued lr is
+        read with float()) and `max_grad_norm` -> whether a copy was issued.  Nothing changed since the last call: nothing is done.
+        Otherwise the values are validated (ValueError, the record keeps its contents), written to the pinned staging tensor and
+        copied into the record with one non-blocking copy on the current stream.  Cannot copy under stream capture: raises there
+        if the record is stale.  Without hyper_on_device: returns False."""
+        if not self._hyper_on_device or self._hyper is None:
+            return False
+        rows = self._hyper_values()
+        if not self._hyper_is_stale(rows):
+            return False
+        if torch.cuda.is_current_stream_capturing():
+            raise _abi.WsmgError("wsmgmap.optim.Adam(hyper_on_device=True): param_groups / max_grad_norm changed since the last "
+                                 "sync_hyper() and the record cannot be refreshed under stream capture; call sync_hyper() before "
+                                 "the capture")
+        if self._hyper_event is not None:
+            self._hyper_event.synchronize()     # the previous copy has read the staging tensor (it was queued before the last step)
+        flat = [0.0] * self._hyper.numel()
+        for i, row in enumerate(rows):
+            flat[i * HYPER_ROW:i * HYPER_ROW + len(row)] = row
+        self._hyper_stage.copy_(torch.tensor(flat, dtype=torch.float32))      # rounds to float32 as a by-value c_float argument does
+        dev = self._hyper.device
+        with torch.cuda.device(dev):
+            self._hyper.copy_(self._hyper_stage, non_blocking=True)
+            self._hyper_event = torch.cuda.Event()
+            self._hyper_event.record(torch.cuda.current_stream(dev))
+        self._hyper_mirror = rows
+        return True
+
+    def _hyper_row(self, i):
+        """Device address of row i of the hyper record (i = len(param_groups): the guard's row)."""
+        return ctypes.c_void_p(self._hyper.data_ptr() + 4 * HYPER_ROW * i)
+
+    def _hyper_before_step(self):
+        """step() with hyper_on_device: refresh the record (eager), or refuse a stale one (under capture) — before any launch."""
+        if self._hyper is None:
+            raise _abi.WsmgError("wsmgmap.optim.Adam(hyper_on_device=True): the hyper record does not exist (construct the optimizer "
+                                 "over the CUDA parameters it steps)")
+        if torch.cuda.is_current_stream_capturing():
+            if self._hyper_is_stale(self._hyper_values()):
+                raise _abi.WsmgError("wsmgmap.optim.Adam(hyper_on_device=True): param_groups / max_grad_norm changed since the last "
+                                     "sync_hyper(); the record cannot be refreshed under stream capture — call sync_hyper() before "
+                                     "capturing step()")
+        else:
+            self.sync_hyper()
+
+    @property
+    def hyper_record(self):
+        """hyper_on_device=True: the device record as a [groups + 1][8] float32 view (read-only use; reading it synchronises)."""
+        return None if self._hyper is None else self._hyper.view(-1, HYPER_ROW)
+
+    @property
+    def max_grad_norm(self):
+        return self._max_grad_norm
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, value):
+        """A new clip threshold.  Only between positive values: turning clipping on or off would change which path a graph captured
+        (and whether the step is guarded at all).  Takes effect at the next eager step, or at the next sync_hyper() with
+        hyper_on_device=True."""
+        if (value is None) != (self._max_grad_norm is None):
+            raise ValueError("max_grad_norm cannot be turned on or off after construction (None <-> a number): construct the "
+                             "optimizer with the clipping it should have")
+        if value is not None:
+            value = float(value)
+            _check_max_grad_norm(value)
+        self._max_grad_norm = value
+
+    def add_param_group(self, param_group):
+        if self._hyper_fixed:
+            raise ValueError("wsmgmap.optim.Adam(hyper_on_device=True): add_param_group after construction is refused — the hyper "
+                             "record has one row per group and captured graphs hold its rows' addresses; pass every group to the "
+                             "constructor")
+        super().add_param_group(param_group)
 
     def _protected_buffers(self):
         """[(qualified name, tensor)]: running_mean, running_var and num_batches_tracked of every BatchNorm layer below the
@@ -196,10 +339,12 @@ class Adam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        if self._hyper_on_device:
+            self._hyper_before_step()
         if self._guarded:
             self._guarded_step()
             return loss
-        for group in self.param_groups:
+        for gi, group in enumerate(self.param_groups):
             by_step = {}
             for p in group["params"]:
                 g = p.grad
@@ -230,14 +375,21 @@ class Adam(torch.optim.Optimizer):
                 dev = items[0][0].device
                 stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
                 with torch.cuda.device(dev):
+                    if self._hyper_on_device and self._hyper.device != dev:
+                        raise _abi.WsmgError("wsmgmap.optim.Adam(hyper_on_device=True): the hyper record is not on the stepped "
+                                             "parameters' device")
                     if self._capturable:
                         key = id(group)
                         if key not in self._step_dev:
                             self._step_dev[key] = torch.full((), float(step - 1), device=dev, dtype=torch.float32)
                         sd = self._step_dev[key]
                         sd.add_(1.0)      # on the device: a replayed graph advances it without the host
-                        _abi.call("wsmg_adam_step_multi_dev", descs, len(items), float(group["lr"]), float(b1), float(b2),
-                                  float(group["eps"]), float(group["weight_decay"]), ctypes.c_void_p(sd.data_ptr()), stream)
+                        if self._hyper_on_device:
+                            _abi.call("wsmg_adam_step_multi_hyper", descs, len(items), self._hyper_row(gi),
+                                      ctypes.c_void_p(sd.data_ptr()), None, stream)
+                        else:
+                            _abi.call("wsmg_adam_step_multi_dev", descs, len(items), float(group["lr"]), float(b1), float(b2),
+                                      float(group["eps"]), float(group["weight_decay"]), ctypes.c_void_p(sd.data_ptr()), stream)
                     else:
                         _abi.call("wsmg_adam_step_multi", descs, len(items), float(group["lr"]), float(b1), float(b2), float(group["eps"]),
                                   float(group["weight_decay"]), 1.0 - b1 ** step, 1.0 - b2 ** step, stream)
@@ -252,7 +404,7 @@ class Adam(torch.optim.Optimizer):
                                  "zero_grad() or snapshot_buffers() before the forward pass (an older snapshot would roll the "
                                  "statistics back by more than one update)")
         groups, steps, dev = [], set(), None
-        for group in self.param_groups:
+        for gi, group in enumerate(self.param_groups):
             items = []
             for p in group["params"]:
                 g = p.grad
@@ -281,13 +433,13 @@ class Adam(torch.optim.Optimizer):
                 steps.add(st["step"])
                 items.append((p, g, st["exp_avg"], st["exp_avg_sq"]))
             if items:
-                groups.append((group, items))
+                groups.append((gi, group, items))
         if not groups:
             return
         if len(steps) > 1:
             raise _abi.WsmgError("wsmgmap.optim.Adam: the guarded step keeps one step count on the device: all stepped parameters "
                                  "must share it")
-        every = [it for _, items in groups for it in items]
+        every = [it for _, _, items in groups for it in items]
         descs = (_AdamDesc * len(every))()
         for d, (p, g, m, v) in zip(descs, every):
             d.param, d.grad, d.exp_avg, d.exp_avg_sq, d.n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
@@ -298,15 +450,25 @@ class Adam(torch.optim.Optimizer):
                                      "optimizer over the CUDA parameters it steps)")
             if self._guard_buffers is not None and self._snap.device != dev:
                 raise _abi.WsmgError("wsmgmap.optim.Adam(guard_buffers=...): the snapshot is not on the stepped parameters' device")
+            if self._hyper_on_device and self._hyper.device != dev:
+                raise _abi.WsmgError("wsmgmap.optim.Adam(hyper_on_device=True): the hyper record is not on the stepped parameters' device")
             guard, sd = ctypes.c_void_p(self._guard.data_ptr()), ctypes.c_void_p(self._guard_step.data_ptr())
             # the finalize advances the step count by 1 - skip: a skipped step does not advance the bias corrections
-            _abi.call("wsmg_grad_norm_multi", descs, len(every), ctypes.c_void_p(self._partials.data_ptr()), self._partials.numel(),
-                      self._max_grad_norm or 0.0, int(self._skip_nonfinite), guard, sd, stream)
+            if self._hyper_on_device:
+                _abi.call("wsmg_grad_norm_multi_hyper", descs, len(every), ctypes.c_void_p(self._partials.data_ptr()),
+                          self._partials.numel(), self._hyper_row(len(self.param_groups)), int(self._skip_nonfinite), guard, sd, stream)
+            else:
+                _abi.call("wsmg_grad_norm_multi", descs, len(every), ctypes.c_void_p(self._partials.data_ptr()), self._partials.numel(),
+                          self._max_grad_norm or 0.0, int(self._skip_nonfinite), guard, sd, stream)
             at = 0
-            for group, items in groups:
+            for gi, group, items in groups:
                 b1, b2 = group["betas"]
-                _abi.call("wsmg_adam_step_multi_guarded", ctypes.byref(descs, at * ctypes.sizeof(_AdamDesc)), len(items),
-                          float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), sd, guard, stream)
+                at_descs = ctypes.byref(descs, at * ctypes.sizeof(_AdamDesc))
+                if self._hyper_on_device:
+                    _abi.call("wsmg_adam_step_multi_hyper", at_descs, len(items), self._hyper_row(gi), sd, guard, stream)
+                else:
+                    _abi.call("wsmg_adam_step_multi_guarded", at_descs, len(items),
+                              float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), sd, guard, stream)
                 at += len(items)
             written = [it[0] for it in every]
             if self._guard_buffers is not None:
@@ -354,3 +516,5 @@ class Adam(torch.optim.Optimizer):
         self._step_dev = {}       # re-created from the loaded step counts at the next capturable step
         if self._guarded:
             self._reset_guard()   # the guard record (skipped = 0) and its step count, from the loaded step counts
+        if self._hyper_on_device:
+            self._reset_hyper()   # the hyper record and its mirror, from the loaded param_groups
