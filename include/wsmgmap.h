@@ -361,6 +361,34 @@ int wsmg_adam_step_multi_hyper(const WsmgAdamDesc* descs, int n, const float* hy
 int wsmg_grad_norm_multi_hyper(const WsmgAdamDesc* descs, int n, double* partials, long long partials_cap,
                                const float* hyper_guard_row, int skip_nonfinite, float* guard, float* step_dev,
                                wsmg_stream_t stream);
+/* WHICH tensor made the guard skip: a per-tensor report of the gradients, and a latch that keeps the report of a skipped step until
+ * the host reads it (the reference has no counterpart: its trainer checks nothing, dagger_trainer.py:536-541).  Only grad and n of a
+ * descriptor are read; a descriptor with n == 0 owns no chunk, may have a NULL grad, and gets an all-zero row.
+ * report is [n][4] 32-bit words, row i for descs[i]:
+ *   word 0  float32  (float)sqrt(S_i), S_i = the float64 sum of tensor i's 4 096-element partials in the order wsmg_grad_norm_multi
+ *                    adds the whole list's (for a list of one tensor: the bits of guard[0])
+ *   word 1  float32  max |g| over the FINITE elements (0 if there is none)
+ *   word 2  uint32   NaN elements          word 3  uint32   +Inf / -Inf elements
+ * wsmg_grad_report_multi: partials is what wsmg_grad_norm_multi[_hyper] wrote for the same gradients earlier on the same stream (the
+ * same list, or that list with zero-length descriptors in between) and must not be NULL — without such a call use
+ * wsmg_grad_stats_multi; scan is a workspace of 4 words per 4 096-element chunk (scan_cap counts chunks, as partials_cap does).
+ * guard and step_dev (both or neither) are the guard record and the step count that call wrote.  latch (or NULL; needs guard) is
+ * [8 + 4 n] words and is written ONLY when guard[2] (skip) != 0 — after a step that was taken no kernel stores one byte of it:
+ *   latch[0] (uint32)guard[3]: steps skipped so far, this one included (the caller zeroes the latch once: 0 = never skipped)
+ *   latch[1] (uint32)*step_dev + latch[0]: the ordinal of this attempt (steps taken + steps skipped)
+ *   latch[2] lowest i with NaNs + Infs > 0, or 0xffffffff: every element was finite and the float32 norm overflowed
+ *   latch[3] i of the largest word 0 (a NaN counts as the largest, ties go to the lowest i)
+ *   latch[4] tensors with NaNs + Infs > 0     latch[5..7] 0     latch[8 ..] a copy of this step's report
+ * wsmg_grad_stats_multi: the stand-alone form — the sum-of-squares launches into partials, then the report; no guard, no latch.
+ * Deterministic (fixed-order reductions, no atomics), no allocation, no synchronisation.  WSMG_EINVAL: NULL descs / partials / scan /
+ * report, a negative count or capacity, partials not 8-byte or any other table not 4-byte aligned, a NULL or misaligned grad of a
+ * non-empty descriptor, latch without guard, guard without step_dev or the reverse, a descriptor with n >= 2^32 (the counters are
+ * 32-bit), more than 2^30 chunks; WSMG_ENOMEM: partials_cap or scan_cap below the chunk total.  A rejected call launches nothing. */
+int wsmg_grad_report_multi(const WsmgAdamDesc* descs, int n, const double* partials, long long partials_cap, uint32_t* scan,
+                           long long scan_cap, const float* guard, const float* step_dev, uint32_t* report, uint32_t* latch,
+                           wsmg_stream_t stream);
+int wsmg_grad_stats_multi(const WsmgAdamDesc* descs, int n, double* partials, long long partials_cap, uint32_t* scan,
+                          long long scan_cap, uint32_t* report, wsmg_stream_t stream);
 
 /* Tests / tools: tile of the LDS-window kernel that serves 3x3 stride-1 pad-1 layers with Cout % 128 == 0, Cin % 32 == 0, Cin >= 64 and
  * B*H*W >= 65536 (0 = off -> implicit-GEMM kernel, 1 = tile chosen by shape, 256 or 512 pixels per workgroup; default 1 or

@@ -10,6 +10,8 @@ per step, arms interleaved over --rounds rounds of --steps steps:
     wsmg-guarded                 wsmgmap.optim.Adam(max_grad_norm=..., skip_nonfinite=True): norm launches + finalize + guarded step
     wsmg-guarded-buffers         the same with guard_buffers=policy: snapshot_buffers() (what zero_grad() adds) + the step with the
                                  conditional roll-back of the BatchNorm statistics behind it (steps taken: the roll-back returns at once)
+    wsmg-guarded-report          wsmg-guarded with grad_report=True: the per-tensor report and its latch behind the norm (steps taken:
+                                 the latch's launch returns at once)
     clip+wsmg                    torch.nn.utils.clip_grad_norm_ in front of the unguarded step (what the guard replaces)
 
 WSMG_LIB=<another build of libwsmgmap.so> times that library's unguarded step (an older build has no guarded arm: --arms wsmg)."""
@@ -57,6 +59,8 @@ for name in args.arms.split(","):
         opt = WsmgAdam(policy.parameters(), lr=1e-6, max_grad_norm=0.5 * norm, skip_nonfinite=True)
     elif name == "wsmg-guarded-hyper":
         opt = WsmgAdam(policy.parameters(), lr=1e-6, max_grad_norm=0.5 * norm, skip_nonfinite=True, hyper_on_device=True)
+    elif name == "wsmg-guarded-report":
+        opt = WsmgAdam(policy.parameters(), lr=1e-6, max_grad_norm=0.5 * norm, skip_nonfinite=True, grad_report=True)
     elif name == "wsmg-guarded-buffers":
         opt = WsmgAdam(policy.parameters(), lr=1e-6, max_grad_norm=0.5 * norm, skip_nonfinite=True, guard_buffers=policy)
     else:

@@ -235,6 +235,178 @@ __global__ __launch_bounds__(256) void grad_guard_finalize_hyper_kernel(const do
   guard_finalize(partials, total, hyper_guard_row[HYPER_MAX_NORM], skip_nonfinite, guard, step_dev);
 }
 
+// ---- the per-tensor gradient report (wsmg_grad_report_multi / wsmg_grad_stats_multi): which tensor made the guard skip
+//
+// Shape: three kernels behind the norm's launches, none of which the step's own kernels depend on.
+//   grad_scan_multi_kernel     grad_sumsq_multi_kernel's ownership (one 256-thread workgroup per 4 096-element chunk, the same search
+//                              over first_block, 16-byte loads of an aligned gradient with scalar tails): max |g| over the finite
+//                              elements, NaN count, Inf count of the chunk -> 4 words of the scan workspace, at the chunk's index in
+//                              the norm's partials.
+//   grad_report_fold_kernel    one workgroup per tensor (ADAM_MAX per launch, table in the kernel arguments): the tensor's float64
+//                              partials in guard_finalize's order (thread t adds chunks t, t + 256, ...; block_sum_d), its scan words
+//                              -> the report row {(float)sqrt(S), max |g|, NaNs, Infs}.  A tensor without chunks gets a zero row.
+//   grad_report_latch_kernel   one workgroup: returns before its first store unless guard[GUARD_SKIP] is set; otherwise the header
+//                              {skipped, attempt, first non-finite tensor, largest norm, non-finite tensors, 0, 0, 0} and a copy of
+//                              the report (the rows strided over the threads, the header from thread 0).
+// Every reduction is a maximum or an integer sum (any order gives the same bits) or the float64 tree above; no atomics; thread 0 stores
+// each chunk record, report row and header with ordinary stores; the only LDS is the reductions' scratch.
+
+struct ScanBatch {         // GradBatch with the scan workspace's slice: four words per workgroup
+  const float* g[ADAM_MAX];
+  int first_block[ADAM_MAX + 1];
+  long long n[ADAM_MAX];
+  int count;
+  uint32_t* scan;
+};
+
+struct FoldBatch {         // tensors row0 .. row0 + gridDim.x of the list; first/chunks index the partials and the scan workspace
+  int first[ADAM_MAX];
+  int chunks[ADAM_MAX];
+  int row0;
+  const double* partials;
+  const uint32_t* scan;
+  uint32_t* report;
+};
+
+// |g| as its bit pattern, which orders non-negative floats as unsigned integers: above Inf's pattern is NaN
+__device__ __forceinline__ void scan1(float g, uint32_t& mx, uint32_t& nan, uint32_t& inf) {
+  const uint32_t a = __float_as_uint(g) & 0x7fffffffu;
+  if (a > 0x7f800000u) ++nan;
+  else if (a == 0x7f800000u) ++inf;
+  else mx = a > mx ? a : mx;
+}
+
+__device__ __forceinline__ uint32_t wave_max_u(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const uint32_t w = (uint32_t)__shfl_xor((int)v, o, 64);
+    v = w > v ? w : v;
+  }
+  return v;
+}
+__device__ __forceinline__ uint32_t wave_sum_u(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
+  return v;
+}
+
+// {max, sum, sum} over the workgroup; red holds 12 words (every thread returns the result)
+__device__ __forceinline__ void block_scan_reduce(uint32_t& mx, uint32_t& nan, uint32_t& inf, uint32_t* red) {
+  mx = wave_max_u(mx); nan = wave_sum_u(nan); inf = wave_sum_u(inf);
+  if ((threadIdx.x & 63) == 0) {
+    const int w = threadIdx.x >> 6;
+    red[w] = mx; red[4 + w] = nan; red[8 + w] = inf;
+  }
+  __syncthreads();
+  mx = red[0];
+#pragma unroll
+  for (int w = 1; w < 4; ++w) mx = red[w] > mx ? red[w] : mx;
+  nan = red[4] + red[5] + red[6] + red[7];
+  inf = red[8] + red[9] + red[10] + red[11];
+}
+
+__global__ __launch_bounds__(256) void grad_scan_multi_kernel(ScanBatch b) {
+  __shared__ uint32_t red[12];
+  int lo = 0, hi = b.count;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if ((int)blockIdx.x >= b.first_block[mid]) lo = mid; else hi = mid;
+  }
+  const float* __restrict__ g = b.g[lo];
+  const long long n = b.n[lo];
+  const long long i0 = (long long)((int)blockIdx.x - b.first_block[lo]) * ADAM_CHUNK;
+  const long long i1 = i0 + ADAM_CHUNK < n ? i0 + ADAM_CHUNK : n;
+  uint32_t mx = 0, nan = 0, inf = 0;
+  if (((uintptr_t)g & 15) == 0) {
+    const long long nv = i0 + ((i1 - i0) & ~3ll);
+    for (long long i = i0 + 4 * (long long)threadIdx.x; i < nv; i += 4 * 256) {
+      const f32x4 gg = ld4(g + i);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) scan1(gg[j], mx, nan, inf);
+    }
+    for (long long i = nv + threadIdx.x; i < i1; i += 256) scan1(g[i], mx, nan, inf);
+  } else {
+    for (long long i = i0 + threadIdx.x; i < i1; i += 256) scan1(g[i], mx, nan, inf);
+  }
+  block_scan_reduce(mx, nan, inf, red);
+  if (threadIdx.x == 0) {
+    uint32_t* __restrict__ out = b.scan + 4 * (long long)blockIdx.x;
+    out[0] = mx; out[1] = nan; out[2] = inf; out[3] = 0u;
+  }
+}
+
+__global__ __launch_bounds__(256) void grad_report_fold_kernel(FoldBatch b) {
+  __shared__ double red[4];
+  __shared__ uint32_t ured[12];
+  const int first = b.first[blockIdx.x], chunks = b.chunks[blockIdx.x];
+  const double* __restrict__ partials = b.partials + first;
+  const uint32_t* __restrict__ scan = b.scan + 4 * (long long)first;
+  double acc = 0.0;
+  uint32_t mx = 0, nan = 0, inf = 0;
+  for (int i = threadIdx.x; i < chunks; i += 256) {
+    acc += partials[i];
+    const uint32_t m = scan[4 * (long long)i];
+    mx = m > mx ? m : mx;
+    nan += scan[4 * (long long)i + 1];
+    inf += scan[4 * (long long)i + 2];
+  }
+  const double sum = block_sum_d(acc, red);
+  block_scan_reduce(mx, nan, inf, ured);
+  if (threadIdx.x == 0) {
+    uint32_t* __restrict__ row = b.report + 4 * ((long long)b.row0 + blockIdx.x);
+    row[0] = __float_as_uint((float)sqrt(sum));
+    row[1] = mx; row[2] = nan; row[3] = inf;
+  }
+}
+
+__device__ __forceinline__ unsigned long long wave_max_ull(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long w = __shfl_xor(v, o, 64);
+    v = w > v ? w : v;
+  }
+  return v;
+}
+
+// The largest norm as the maximum of (key << 32 | ~i): key is the norm's bit pattern (norms are >= +0, so the patterns order as the
+// values do) or 0xffffffff for a NaN, and the complemented index makes the lowest i win a tie.  No row at all gives i = 0xffffffff.
+__global__ __launch_bounds__(256) void grad_report_latch_kernel(const uint32_t* __restrict__ report, int n,
+                                                                const float* __restrict__ guard, const float* __restrict__ step_dev,
+                                                                uint32_t* __restrict__ latch) {
+  __shared__ unsigned long long bred[4];
+  __shared__ uint32_t ured[12];
+  if (guard[GUARD_SKIP] == 0.f) return;          // a step that was taken: not one byte of the latch is stored
+  unsigned long long best = 0ull;
+  uint32_t notfirst = 0, bad = 0, unused = 0;    // notfirst = ~(lowest non-finite i): a maximum, as block_scan_reduce takes it
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const uint32_t w0 = report[4 * (long long)i];
+    const uint32_t key = (w0 & 0x7fffffffu) > 0x7f800000u ? 0xffffffffu : w0;
+    const unsigned long long cand = ((unsigned long long)key << 32) | (uint32_t)~(uint32_t)i;
+    best = cand > best ? cand : best;
+    if (report[4 * (long long)i + 2] + report[4 * (long long)i + 3] != 0u) {     // (counts of one tensor sum below 2^32: n < 2^32)
+      ++bad;
+      const uint32_t c = ~(uint32_t)i;
+      notfirst = c > notfirst ? c : notfirst;
+    }
+  }
+  best = wave_max_ull(best);
+  if ((threadIdx.x & 63) == 0) bred[threadIdx.x >> 6] = best;
+  block_scan_reduce(notfirst, bad, unused, ured);          // (its barrier also publishes bred)
+  for (long long i = threadIdx.x; i < 4ll * n; i += 256) latch[8 + i] = report[i];
+  if (threadIdx.x == 0) {
+    best = bred[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) best = bred[w] > best ? bred[w] : best;
+    const uint32_t skipped = (uint32_t)guard[GUARD_SKIPPED];
+    latch[0] = skipped;
+    latch[1] = (uint32_t)*step_dev + skipped;
+    latch[2] = ~notfirst;                        // nothing non-finite: ~0
+    latch[3] = ~(uint32_t)best;
+    latch[4] = bad;
+    latch[5] = 0u; latch[6] = 0u; latch[7] = 0u;
+  }
+}
+
 }  // namespace
 
 static int adam_launch(const WsmgAdamDesc* descs, int n, float lr, float beta1, float beta2, float eps, float weight_decay,
@@ -319,20 +491,9 @@ extern "C" int wsmg_adam_step_multi_hyper(const WsmgAdamDesc* descs, int n, cons
   return adam_launch(descs, n, 0.f, 0.f, 0.f, 0.f, 0.f, 0.0, 0.0, step_dev, guard, hyper_row, s);
 }
 
-// Global L2 norm of the descs' gradients (param / exp_avg / exp_avg_sq are not read) into the guard record.  Every argument is
-// checked, and the partials' capacity against the total workgroup count, before the first launch.
-// hyper_guard_row (or null): max_norm is read from it on the device and the by-value max_norm is ignored.
-static int grad_norm_launch(const WsmgAdamDesc* descs, int n, double* partials, long long partials_cap, float max_norm,
-                            const float* hyper_guard_row, int skip_nonfinite, float* guard, float* step_dev, wsmg_stream_t s) {
-  if (n < 0 || (n > 0 && !descs) || !guard || !partials || partials_cap < 0 || !(max_norm >= 0.f)) return WSMG_EINVAL;
-  if (((uintptr_t)partials & 7) || ((uintptr_t)guard & 3) || ((uintptr_t)step_dev & 3)) return WSMG_EINVAL;
-  long long total = 0;
-  for (int i = 0; i < n; ++i) {
-    if (descs[i].n < 0 || (descs[i].n > 0 && !descs[i].grad)) return WSMG_EINVAL;
-    total += (descs[i].n + ADAM_CHUNK - 1) / ADAM_CHUNK;
-    if (total > (1ll << 30)) return WSMG_EINVAL;
-  }
-  if (total > partials_cap) return WSMG_ENOMEM;
+// The sum-of-squares launches over checked descs: chunk c of the list (descriptors with n == 0 own none) -> partials[c].  Returns the
+// chunk total.
+static int grad_sumsq_launches(const WsmgAdamDesc* descs, int n, double* partials, wsmg_stream_t s) {
   int base = 0;
   for (int i = 0; i < n;) {
     GradBatch b;
@@ -351,6 +512,24 @@ static int grad_norm_launch(const WsmgAdamDesc* descs, int n, double* partials, 
     hipLaunchKernelGGL(grad_sumsq_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, wsmg_s(s), b);
     base += blocks;
   }
+  return base;
+}
+
+// Global L2 norm of the descs' gradients (param / exp_avg / exp_avg_sq are not read) into the guard record.  Every argument is
+// checked, and the partials' capacity against the total workgroup count, before the first launch.
+// hyper_guard_row (or null): max_norm is read from it on the device and the by-value max_norm is ignored.
+static int grad_norm_launch(const WsmgAdamDesc* descs, int n, double* partials, long long partials_cap, float max_norm,
+                            const float* hyper_guard_row, int skip_nonfinite, float* guard, float* step_dev, wsmg_stream_t s) {
+  if (n < 0 || (n > 0 && !descs) || !guard || !partials || partials_cap < 0 || !(max_norm >= 0.f)) return WSMG_EINVAL;
+  if (((uintptr_t)partials & 7) || ((uintptr_t)guard & 3) || ((uintptr_t)step_dev & 3)) return WSMG_EINVAL;
+  long long total = 0;
+  for (int i = 0; i < n; ++i) {
+    if (descs[i].n < 0 || (descs[i].n > 0 && !descs[i].grad)) return WSMG_EINVAL;
+    total += (descs[i].n + ADAM_CHUNK - 1) / ADAM_CHUNK;
+    if (total > (1ll << 30)) return WSMG_EINVAL;
+  }
+  if (total > partials_cap) return WSMG_ENOMEM;
+  const int base = grad_sumsq_launches(descs, n, partials, s);
   if (hyper_guard_row)
     hipLaunchKernelGGL(grad_guard_finalize_hyper_kernel, dim3(1), dim3(256), 0, wsmg_s(s), (const double*)partials, base,
                        hyper_guard_row, skip_nonfinite, guard, step_dev);
@@ -371,4 +550,82 @@ extern "C" int wsmg_grad_norm_multi_hyper(const WsmgAdamDesc* descs, int n, doub
                                           wsmg_stream_t s) {
   if (!hyper_guard_row || ((uintptr_t)hyper_guard_row & 3)) return WSMG_EINVAL;
   return grad_norm_launch(descs, n, partials, partials_cap, 0.f, hyper_guard_row, skip_nonfinite, guard, step_dev, s);
+}
+
+// The report's argument checks (every descriptor, and the chunk total against both capacities, before the first launch): 0, WSMG_EINVAL or WSMG_ENOMEM.
+static int grad_report_check(const WsmgAdamDesc* descs, int n, const double* partials, long long partials_cap, const uint32_t* scan,
+                             long long scan_cap, const uint32_t* report) {
+  if (n < 0 || (n > 0 && !descs) || !partials || partials_cap < 0 || !scan || scan_cap < 0 || !report) return WSMG_EINVAL;
+  if (((uintptr_t)partials & 7) || ((uintptr_t)scan & 3) || ((uintptr_t)report & 3)) return WSMG_EINVAL;
+  long long total = 0;
+  for (int i = 0; i < n; ++i) {
+    const WsmgAdamDesc& d = descs[i];
+    if (d.n < 0 || d.n >= (1ll << 32) || (d.n > 0 && (!d.grad || ((uintptr_t)d.grad & 3)))) return WSMG_EINVAL;   // 32-bit counters
+    total += (d.n + ADAM_CHUNK - 1) / ADAM_CHUNK;
+    if (total > (1ll << 30)) return WSMG_EINVAL;
+  }
+  return (total > partials_cap || total > scan_cap) ? WSMG_ENOMEM : 0;
+}
+
+// The scan launches (grad_sumsq_launches' batches, so a chunk has one index in partials and scan), the fold launches over every
+// descriptor, and the latch's launch if there is one.  Arguments are checked.
+static void grad_report_launches(const WsmgAdamDesc* descs, int n, const double* partials, uint32_t* scan, const float* guard,
+                                 const float* step_dev, uint32_t* report, uint32_t* latch, wsmg_stream_t s) {
+  int base = 0;
+  for (int i = 0; i < n;) {
+    ScanBatch b;
+    b.count = 0;
+    int blocks = 0;
+    for (; i < n && b.count < ADAM_MAX; ++i) {
+      if (descs[i].n == 0) continue;
+      const int k = b.count++;
+      b.g[k] = descs[i].grad; b.n[k] = descs[i].n;
+      b.first_block[k] = blocks;
+      blocks += (int)((descs[i].n + ADAM_CHUNK - 1) / ADAM_CHUNK);
+    }
+    if (!b.count) continue;
+    b.first_block[b.count] = blocks;
+    b.scan = scan + 4 * (long long)base;
+    hipLaunchKernelGGL(grad_scan_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, wsmg_s(s), b);
+    base += blocks;
+  }
+  int first = 0;
+  for (int i = 0; i < n;) {
+    FoldBatch b;
+    b.row0 = i;
+    int k = 0;
+    for (; i < n && k < ADAM_MAX; ++i, ++k) {
+      b.first[k] = first;
+      b.chunks[k] = (int)((descs[i].n + ADAM_CHUNK - 1) / ADAM_CHUNK);
+      first += b.chunks[k];
+    }
+    b.partials = partials; b.scan = scan; b.report = report;
+    hipLaunchKernelGGL(grad_report_fold_kernel, dim3((unsigned)k), dim3(256), 0, wsmg_s(s), b);
+  }
+  if (latch)
+    hipLaunchKernelGGL(grad_report_latch_kernel, dim3(1), dim3(256), 0, wsmg_s(s), (const uint32_t*)report, n, guard, step_dev, latch);
+}
+
+// Per-tensor report of the gradients whose sums of squares wsmg_grad_norm_multi[_hyper] left in partials (the same descs or, as
+// wsmgmap.optim.Adam passes them, the same list with zero-length descriptors in between: those own no chunk), and the latch that
+// keeps the report of a skipped step.  Only grad and n of a descriptor are read.
+extern "C" int wsmg_grad_report_multi(const WsmgAdamDesc* descs, int n, const double* partials, long long partials_cap, uint32_t* scan,
+                                      long long scan_cap, const float* guard, const float* step_dev, uint32_t* report, uint32_t* latch,
+                                      wsmg_stream_t s) {
+  if ((latch && !guard) || (!guard != !step_dev)) return WSMG_EINVAL;
+  if (((uintptr_t)guard & 3) || ((uintptr_t)step_dev & 3) || ((uintptr_t)latch & 3)) return WSMG_EINVAL;
+  const int rc = grad_report_check(descs, n, partials, partials_cap, scan, scan_cap, report);
+  if (rc) return rc;
+  grad_report_launches(descs, n, partials, scan, guard, step_dev, report, latch, s);
+  WSMG_RETURN_LAUNCH();
+}
+
+// The stand-alone form: the sum-of-squares launches into partials, then the report; no guard, no latch, no step count.
+extern "C" int wsmg_grad_stats_multi(const WsmgAdamDesc* descs, int n, double* partials, long long partials_cap, uint32_t* scan,
+                                     long long scan_cap, uint32_t* report, wsmg_stream_t s) {
+  const int rc = grad_report_check(descs, n, partials, partials_cap, scan, scan_cap, report);
+  if (rc) return rc;
+  grad_sumsq_launches(descs, n, partials, s);
+  grad_report_launches(descs, n, partials, scan, nullptr, nullptr, report, nullptr, s);
+  WSMG_RETURN_LAUNCH();
 }

@@ -167,6 +167,9 @@ _SIG["wsmg_adam_step_multi_guarded"] = [c_p, c_i, c_f, c_f, c_f, c_f, c_f, c_p, 
 # the two steps of common_trainer.py:67-69 / dagger_trainer.py:536 with lr, betas, eps, weight_decay, max_grad_norm read from a device record
 _SIG["wsmg_adam_step_multi_hyper"] = [c_p, c_i, c_p, c_p, c_p, c_p]
 _SIG["wsmg_grad_norm_multi_hyper"] = [c_p, c_i, c_p, ctypes.c_longlong, c_p, c_i, c_p, c_p, c_p]
+# which tensor made the guard skip: the per-tensor report and its latch / the stand-alone statistics
+_SIG["wsmg_grad_report_multi"] = [c_p, c_i, c_p, ctypes.c_longlong, c_p, ctypes.c_longlong, c_p, c_p, c_p, c_p, c_p]
+_SIG["wsmg_grad_stats_multi"] = [c_p, c_i, c_p, ctypes.c_longlong, c_p, ctypes.c_longlong, c_p, c_p]
 _SIG["wsmg_rows_gemm_f32"] = ([c_p, c_i, c_i] * 3 + [c_p, c_i, c_i, c_p, c_p, c_i, c_i] + [c_p, c_i, c_i] * 3 + [c_p, c_i] * 3
                               + [c_i, c_p, ctypes.c_uint, c_p, c_i, c_p, c_p])
 _SIG["wsmg_rows_gemm_workgroups"] = [c_i, c_i]

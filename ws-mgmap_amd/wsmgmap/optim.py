@@ -17,7 +17,13 @@ BatchNorm running statistics below `module` on the device (wsmg_copy_multi), and
 `Adam(capturable=True or a guard option, hyper_on_device=True)` keeps `lr`, `betas`, `eps`, `weight_decay` of every parameter group
 and `max_grad_norm` in a small device record that the kernels read (wsmg_adam_step_multi_hyper, wsmg_grad_norm_multi_hyper): a
 captured step then follows `param_groups` edits and `torch.optim.lr_scheduler` steps, which kernel arguments frozen at capture
-cannot.  `sync_hyper()` refreshes the record, outside the graph; an eager `step()` and `GraphedUpdate` call it themselves."""
+cannot.  `sync_hyper()` refreshes the record, outside the graph; an eager `step()` and `GraphedUpdate` call it themselves.
+
+`Adam(a guard option, grad_report=True)` names the tensor behind a skipped step: behind the norm, wsmg_grad_report_multi writes one
+row per parameter {norm, max |g| over the finite elements, NaN count, Inf count} and, only when the guard skips, copies the rows and a
+header into a latch that keeps them until the host reads it, however many clean steps (or graph replays) follow.  `grad_report()`
+and `last_skipped()` read them back; `grad_stats(params)` is the table alone, beside `global_grad_norm`."""
+import collections
 import ctypes
 import math
 
@@ -51,6 +57,58 @@ def _norm_blocks(descs):
     return sum((d.n + ADAM_CHUNK - 1) // ADAM_CHUNK for d in descs)
 
 
+GradStat = collections.namedtuple("GradStat", "index name norm max_abs nan inf")
+GradStat.__doc__ = """One row of the per-tensor gradient report: `index` in the flattened `param_groups` order, `norm` the tensor's L2 norm
+(float32 of a float64 sum), `max_abs` the largest |g| among the finite elements (0.0 if there is none), `nan` / `inf` element counts."""
+SkippedStep = collections.namedtuple("SkippedStep", "attempt skipped first_nonfinite largest nonfinite_tensors stats")
+SkippedStep.__doc__ = """The latched report of the most recent skipped step: `attempt` its ordinal (steps taken + steps skipped, the host's
+`state[p]["step"]` of that step), `skipped` how many steps had been skipped then, `first_nonfinite` the GradStat of the lowest-index
+tensor with a NaN or Inf (None: every element was finite and the float32 norm overflowed), `largest` the GradStat with the largest norm
+(a NaN norm counts as the largest), `nonfinite_tensors` how many tensors held a NaN or Inf, `stats` every row of that step."""
+LATCH_HEADER = 8          # words in front of the latch's rows (include/wsmgmap.h)
+
+
+def stats_as_float(table):
+    """The float32 view of words 0-1 (norm, max |g|) of a report table ([n, 4] int32, as `grad_stats` returns it): [n, 2]."""
+    return table[:, :2].view(torch.float32)
+
+
+def _stats_rows(table, names):
+    """[GradStat] of a report table on the host."""
+    f = stats_as_float(table).tolist()
+    c = table[:, 2:].tolist()
+    return [GradStat(i, names[i], f[i][0], f[i][1], c[i][0] & 0xffffffff, c[i][1] & 0xffffffff) for i in range(len(f))]
+
+
+def grad_stats(params):
+    """Per-tensor gradient statistics, one row per parameter in the order given: an [n, 4] int32 device table whose words are
+    {float32 L2 norm, float32 max |g| over the finite elements, NaN count, Inf count} (`stats_as_float` views the first two).  A
+    parameter without a gradient, or with no elements, has an all-zero row.  Deterministic (float64 sums in a fixed order: two calls
+    return the same bits), a few launches per 48 tensors, no host synchronisation.  Dense float32 CUDA gradients on one device only."""
+    params = list(params)
+    grads = [p.grad for p in params]
+    some = [g for g in grads if g is not None]
+    if not some:
+        raise _abi.WsmgError("wsmgmap.optim.grad_stats: no parameter has a gradient")
+    dev = some[0].device
+    for g in some:
+        if g.is_sparse or not (g.is_cuda and g.dtype == torch.float32 and g.device == dev):
+            raise _abi.WsmgError("wsmgmap.optim.grad_stats: gradients must be dense float32 CUDA tensors on one device")
+    grads = [g if g is None or g.is_contiguous() else g.contiguous() for g in grads]     # (copies live until the launches are queued)
+    descs = (_AdamDesc * len(grads))()
+    for d, g in zip(descs, grads):
+        if g is not None and g.numel():
+            d.grad, d.n = g.data_ptr(), g.numel()
+    with torch.cuda.device(dev):
+        cap = max(1, _norm_blocks(descs))
+        partials = torch.empty(cap, device=dev, dtype=torch.float64)
+        scan = torch.empty(4 * cap, device=dev, dtype=torch.int32)
+        report = torch.empty(len(grads), 4, device=dev, dtype=torch.int32)
+        _abi.call("wsmg_grad_stats_multi", descs, len(grads), ctypes.c_void_p(partials.data_ptr()), cap, ctypes.c_void_p(scan.data_ptr()),
+                  cap, ctypes.c_void_p(report.data_ptr()), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    return report
+
+
 def global_grad_norm(params):
     """L2 norm over the `.grad` of every parameter that has one (as `clip_grad_norm_` over them computes it, but accumulated in
     float64 in a fixed order: two calls return the same bits): a 0-dim float32 tensor on the gradients' device.  A few launches per
@@ -77,7 +135,8 @@ def global_grad_norm(params):
 
 class Adam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, maximize=False,
-                 capturable=False, max_grad_norm=None, skip_nonfinite=False, guard_buffers=None, hyper_on_device=False):
+                 capturable=False, max_grad_norm=None, skip_nonfinite=False, guard_buffers=None, hyper_on_device=False,
+                 grad_report=False):
         """capturable=True: the step count also lives in a device scalar (one per parameter group, incremented on the device)
         and the kernel computes the bias corrections from it — the form `wsmgmap.graph.GraphedUpdate` captures into a HIP graph
         (kernel arguments are frozen at capture).  All stepped parameters of a group must then share one step count.
@@ -105,7 +164,16 @@ class Adam(torch.optim.Optimizer):
         mirror and, if one changed, refreshes the record with one asynchronous copy on the current stream: an eager `step()` and
         `GraphedUpdate` call it; around a graph of your own (`torch.cuda.graph`) call it before each replay.  Under capture
         nothing can be copied: a `step()` whose values differ from the mirror raises there.  Same arithmetic, bit for bit, as
-        without the flag.  The record has one row per parameter group: `add_param_group` is refused after construction."""
+        without the flag.  The record has one row per parameter group: `add_param_group` is refused after construction.
+
+        grad_report=True (needs the guarded step): behind the norm, every guarded step also writes a per-tensor report on the device
+        — one row per parameter in the flattened `param_groups` order, whether or not it has a gradient in this step (none: a zero
+        row), so a parameter that comes and goes never shifts another tensor's row — and, only when the guard skips, copies it into
+        a latch together with the attempt's ordinal and the index of the first tensor that held a NaN or Inf.  The latch keeps that
+        until the next skipped step: `last_skipped()` reads it whenever the host gets round to it, `grad_report()` reads the most
+        recent step's rows.  A few launches more per step, no host synchronisation, capturable with the step; parameters, moments,
+        the guard record and the step count are what they are without the flag, bit for bit.  The tables are not optimizer state
+        (`state_dict()` does not hold them) and are laid out once: `add_param_group` is refused after construction."""
         self._capturable = bool(capturable)
         self._step_dev = {}
         _check_max_grad_norm(max_grad_norm)
@@ -134,6 +202,14 @@ class Adam(torch.optim.Optimizer):
         self._hyper_mirror = None  # tensor (allocated by _reset_hyper, never by a default construction)
         self._hyper_event = None
         self._hyper_fixed = False  # the record's rows are laid out: no further parameter group
+        self._grad_report = bool(grad_report)
+        if self._grad_report and not self._guarded:
+            raise ValueError("grad_report=True needs the guarded step (max_grad_norm / skip_nonfinite): the report is written behind "
+                             "the guard's norm and latched by its skip flag")
+        self._report = None        # grad_report only: the [parameters][4] report, the latch [8 + 4 parameters] and the scan workspace
+        self._latch = None         # (4 words per chunk), all int32 (allocated by _reset_guard, never by a default construction)
+        self._scan = None
+        self._report_fixed = False  # the report's rows are laid out: no further parameter group
         if amsgrad or maximize:
             raise ValueError("wsmgmap.optim.Adam implements amsgrad=False, maximize=False (what the reference trains with)")
         _check_hyper(lr, betas, eps, weight_decay)
@@ -143,11 +219,12 @@ class Adam(torch.optim.Optimizer):
         if self._hyper_on_device:
             self._reset_hyper()
             self._hyper_fixed = True
+        self._report_fixed = self._grad_report
 
     def _reset_guard(self):
         """(Re-)create the guard's device tensors from the host-side step counts: at construction and after load_state_dict, so
         that step() itself allocates and fills nothing — a fill captured into a HIP graph would reset the record at every replay."""
-        self._guard = self._guard_step = self._partials = None
+        self._guard = self._guard_step = self._partials = self._report = self._latch = self._scan = None
         params = [p for group in self.param_groups for p in group["params"]]
         if not params or not all(p.is_cuda for p in params):
             return                 # step() refuses such parameters
@@ -159,6 +236,10 @@ class Adam(torch.optim.Optimizer):
         self._guard_step = torch.full((), float(steps.pop() if steps else 0), device=dev, dtype=torch.float32)
         blocks = sum((p.numel() + ADAM_CHUNK - 1) // ADAM_CHUNK for p in params)
         self._partials = torch.empty(max(1, blocks), device=dev, dtype=torch.float64)
+        if self._grad_report:      # the latch starts at zero: word 0 == 0 reads "never skipped"
+            self._scan = torch.empty(4 * max(1, blocks), device=dev, dtype=torch.int32)
+            self._report = torch.zeros(len(params), 4, device=dev, dtype=torch.int32)
+            self._latch = torch.zeros(LATCH_HEADER + 4 * len(params), device=dev, dtype=torch.int32)
 
     def _reset_hyper(self):
         """(Re-)create the hyper record, its staging tensor and the mirror from `param_groups` and `max_grad_norm`: at construction
@@ -264,6 +345,10 @@ class Adam(torch.optim.Optimizer):
         if self._hyper_fixed:
             raise ValueError("wsmgmap.optim.Adam(hyper_on_device=True): add_param_group after construction is refused — the hyper "
                              "record has one row per group and captured graphs hold its rows' addresses; pass every group to the "
+                             "constructor")
+        if self._report_fixed:
+            raise ValueError("wsmgmap.optim.Adam(grad_report=True): add_param_group after construction is refused — the report has "
+                             "one row per parameter and captured graphs hold its tables' addresses; pass every group to the "
                              "constructor")
         super().add_param_group(param_group)
 
@@ -440,6 +525,10 @@ class Adam(torch.optim.Optimizer):
             raise _abi.WsmgError("wsmgmap.optim.Adam: the guarded step keeps one step count on the device: all stepped parameters "
                                  "must share it")
         every = [it for _, _, items in groups for it in items]
+        rows = None
+        if self._grad_report:      # the gradient behind every report row (the stepped list's, in its order), None where there is none
+            stepped = iter(every)
+            rows = [None if p.grad is None else next(stepped)[1] for group in self.param_groups for p in group["params"]]
         descs = (_AdamDesc * len(every))()
         for d, (p, g, m, v) in zip(descs, every):
             d.param, d.grad, d.exp_avg, d.exp_avg_sq, d.n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
@@ -452,6 +541,8 @@ class Adam(torch.optim.Optimizer):
                 raise _abi.WsmgError("wsmgmap.optim.Adam(guard_buffers=...): the snapshot is not on the stepped parameters' device")
             if self._hyper_on_device and self._hyper.device != dev:
                 raise _abi.WsmgError("wsmgmap.optim.Adam(hyper_on_device=True): the hyper record is not on the stepped parameters' device")
+            if rows is not None and (self._report is None or self._report.shape[0] != len(rows)):
+                raise _abi.WsmgError("wsmgmap.optim.Adam(grad_report=True): the report's tables do not fit the parameters")
             guard, sd = ctypes.c_void_p(self._guard.data_ptr()), ctypes.c_void_p(self._guard_step.data_ptr())
             # the finalize advances the step count by 1 - skip: a skipped step does not advance the bias corrections
             if self._hyper_on_device:
@@ -460,6 +551,16 @@ class Adam(torch.optim.Optimizer):
             else:
                 _abi.call("wsmg_grad_norm_multi", descs, len(every), ctypes.c_void_p(self._partials.data_ptr()), self._partials.numel(),
                           self._max_grad_norm or 0.0, int(self._skip_nonfinite), guard, sd, stream)
+            if rows is not None:
+                # descriptors of their own over ALL parameters: the stepped list with a zero-length one for every parameter without a
+                # gradient — those own no chunk, so the norm's partials line up, and no row ever shifts
+                rdescs = (_AdamDesc * len(rows))()
+                for d, g in zip(rdescs, rows):
+                    if g is not None and g.numel():
+                        d.grad, d.n = g.data_ptr(), g.numel()
+                _abi.call("wsmg_grad_report_multi", rdescs, len(rows), ctypes.c_void_p(self._partials.data_ptr()),
+                          self._partials.numel(), ctypes.c_void_p(self._scan.data_ptr()), self._scan.numel() // 4, guard, sd,
+                          ctypes.c_void_p(self._report.data_ptr()), ctypes.c_void_p(self._latch.data_ptr()), stream)
             at = 0
             for gi, group, items in groups:
                 b1, b2 = group["betas"]
@@ -489,6 +590,44 @@ class Adam(torch.optim.Optimizer):
         """How many guarded steps found a non-finite norm and wrote nothing (since construction or load_state_dict): one readback."""
         return 0 if self._guard is None else int(self._guard[3].item())
 
+    def _report_names(self, names):
+        """One name per report row: the `named_parameters()` keys of a module (matched by identity), a sequence of strings, or
+        "group{g}.param{i}"."""
+        default = [f"group{gi}.param{i}" for gi, group in enumerate(self.param_groups) for i in range(len(group["params"]))]
+        if names is None:
+            return default
+        if isinstance(names, torch.nn.Module):
+            by_id = {id(p): name for name, p in names.named_parameters()}
+            params = [p for group in self.param_groups for p in group["params"]]
+            return [by_id.get(id(p), d) for p, d in zip(params, default)]
+        names = [str(x) for x in names]
+        if len(names) != len(default):
+            raise ValueError(f"wsmgmap.optim.Adam: {len(names)} names for {len(default)} parameters")
+        return names
+
+    def grad_report(self, names=None):
+        """grad_report=True: the per-tensor report of the most recent guarded step as a list of GradStat, one per parameter in the
+        flattened `param_groups` order (a parameter without a gradient in that step: zeros) — one synchronising readback.  `names`:
+        an `nn.Module` (its `named_parameters()` keys, the state_dict keys), a sequence of strings, or None for "group{g}.param{i}".
+        An empty list when the report does not exist (constructed without the flag, or over parameters that are not on a device)."""
+        if self._report is None:
+            return []
+        return _stats_rows(self._report.cpu(), self._report_names(names))
+
+    def last_skipped(self, names=None):
+        """grad_report=True: what the device latched at the most recent SKIPPED step, however many steps were taken since — a
+        SkippedStep, or None if no step was skipped since construction / load_state_dict (or the latch does not exist).  One
+        synchronising readback; `names` as for `grad_report`."""
+        if self._latch is None:
+            return None
+        latch = self._latch.cpu()
+        skipped, attempt, first, largest, bad = (x & 0xffffffff for x in latch[:5].tolist())
+        if skipped == 0:
+            return None
+        stats = _stats_rows(latch[LATCH_HEADER:].view(-1, 4), self._report_names(names))
+        return SkippedStep(attempt, skipped, None if first == 0xffffffff else stats[first],
+                           None if largest == 0xffffffff else stats[largest], bad, stats)
+
     def note_replayed_steps(self, n=1):
         """A captured graph that contains this optimizer's step was replayed n times: advance the host-side step counts (the
         device counters advanced inside the graph).  With the guard on the host count is the ATTEMPTED steps; the device count,
@@ -515,6 +654,6 @@ class Adam(torch.optim.Optimizer):
                 st["step"] = int(round(float(st["step"])))
         self._step_dev = {}       # re-created from the loaded step counts at the next capturable step
         if self._guarded:
-            self._reset_guard()   # the guard record (skipped = 0) and its step count, from the loaded step counts
+            self._reset_guard()   # the guard record (skipped = 0) and its step count, from the loaded step counts; the report, zeroed
         if self._hyper_on_device:
             self._reset_hyper()   # the hyper record and its mirror, from the loaded param_groups
