@@ -9,13 +9,13 @@ launch), then a parameter with zero elements and a parameter without a gradient:
 
 THE BARS: counts equal; max |g| bit-equal (a maximum of float32 values); the norm within 2 float32 ulps, relative 2^-22 — the sums are
 float64 on both sides (relative 1e-16 apart at most per addition), so the only visible roundings are the square root and the cast."""
-import ctypes
 import functools
 
 import numpy as np
 import pytest
 import torch
 
+from adam_util import _bits, _ptr, _stream
 from oracle import cases
 from oracle import detfill as df
 from util import T, state_dict_values
@@ -90,18 +90,6 @@ class DevSet:
         g = _grads()[row]
         self.grads[row].copy_(T(np.array(g)))
         self.host[row] = np.array(g)
-
-
-def _bits(t):
-    return t.detach().contiguous().view(torch.int32)
-
-
-def _ptr(t, byte_off=0):
-    return ctypes.c_void_p(t.data_ptr() + byte_off)
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _check_table(name, table, host, tail=False):

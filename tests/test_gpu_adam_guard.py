@@ -9,100 +9,23 @@ into a second launch, so the norm's partials span launches); values from oracle.
 THE BAR of every stepped comparison is the existing Adam bar, rtol 2e-6 / atol 1e-7 (one float32 rounding of p is 6e-8 relative).
 The guard adds to a plain step: the float32 rounding of the norm (6e-8), of norm + 1e-6 and of the quotient (6e-8 each), and of
 g * coef (6e-8) — under 3e-7 relative on g, 6e-7 on its square, inside the bar; it was not widened."""
-import ctypes
 import functools
 
 import numpy as np
 import pytest
 import torch
 
+import adam_util
+from adam_util import ALL_SIZES, SIZES, TOTAL_BLOCKS, _bits, _norm64, _ptr, _stream
 from oracle import cases
-from oracle import detfill as df
 from util import T, state_dict_values
 
 pytestmark = pytest.mark.gpu
 
-SIZES = [1, 3, 4, 4095, 4096, 4097, 8193]
-ALL_SIZES = SIZES + SIZES + [5 + 7 * i for i in range(50 - 2 * len(SIZES))]
-CHUNK = 4096
-TOTAL_BLOCKS = sum((n + CHUNK - 1) // CHUNK for n in ALL_SIZES)
 LR, B1, B2, EPS = 2.5e-4, 0.9, 0.999, 1e-8
 RTOL, ATOL = 2e-6, 1e-7
-
-
-@functools.lru_cache(maxsize=None)
-def _values():
-    """[(offset in floats from a 16-byte boundary, (p, g, m, v))] — computed once, never written."""
-    out = []
-    for i, n in enumerate(ALL_SIZES):
-        off = 1 if len(SIZES) <= i < 2 * len(SIZES) else 0
-        vals = [df.uniform(f"guard.{i}.{what}", (n,), sc) for what, sc in (("p", 2.0), ("g", 0.2), ("m", 0.02))]
-        vals.append(np.abs(df.uniform(f"guard.{i}.v", (n,), 0.002)))
-        for a in vals:
-            a.setflags(write=False)
-        out.append((off, tuple(vals)))
-    return out
-
-
-class DevSet:
-    """The tensors on the device, each a view into a zeroed buffer with 8 floats of slack: .views[i] = [p, g, m, v]."""
-
-    def __init__(self, fresh, gscale=None, values=None):
-        self.values = _values() if values is None else values
-        self.bufs, self.views = [], []
-        for off, (p, g, m, v) in self.values:
-            if fresh:
-                m, v = np.zeros_like(m), np.zeros_like(v)
-            row = []
-            for k, a in enumerate((p, g, m, v)):
-                buf = torch.zeros(a.size + 8, device="cuda")
-                assert buf.data_ptr() % 16 == 0
-                view = buf[off:off + a.size]
-                src = T(a)
-                view.copy_(src * gscale if (k == 1 and gscale is not None) else src)
-                row.append(view)
-                self.bufs.append((off, a.size, buf))
-            assert row[0].data_ptr() % 16 == 4 * off
-            self.views.append(row)
-
-    def descs(self):
-        from wsmgmap.optim import _AdamDesc
-        d = (_AdamDesc * len(self.views))()
-        for x, (p, g, m, v) in zip(d, self.views):
-            x.param, x.grad, x.exp_avg, x.exp_avg_sq, x.n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
-        return d
-
-    def params(self):
-        out = []
-        for p, g, _, _ in self.views:
-            q = torch.nn.Parameter(p)
-            assert q.data_ptr() == p.data_ptr()
-            q.grad = g
-            out.append(q)
-        return out
-
-    def slack_untouched(self):
-        return all(bool((buf[:off] == 0).all()) and bool((buf[off + n:] == 0).all()) for off, n, buf in self.bufs)
-
-    def grads_unchanged(self):
-        return all(torch.equal(row[1].cpu().view(torch.int32), T(vals[1]).view(torch.int32))
-                   for row, (_, vals) in zip(self.views, self.values))
-
-
-def _bits(t):
-    return t.detach().contiguous().view(torch.int32)
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
-def _norm64(values):
-    return float(torch.linalg.vector_norm(torch.cat([T(g).double() for _, (_, g, _, _) in values])))
+_values = functools.partial(adam_util._values, "guard")            # this file's numbers
+DevSet = functools.partial(adam_util.DevSet, "guard")
 
 
 def _oracle(values, fresh, start_step, n_steps, wd=0.0, max_norm=None):

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+from adam_util import _bits, _ptr, _stream
 from oracle import cases
 from util import T, state_dict_values
 
@@ -21,21 +22,8 @@ pytestmark = pytest.mark.gpu
 LR = 2.5e-4
 
 
-def _bits(t):
-    t = t.detach().contiguous()
-    return t.view(torch.int64) if t.element_size() == 8 else t.view(torch.int32)
-
-
 def _same(a, b):
     return a.dtype == b.dtype and a.shape == b.shape and torch.equal(_bits(a), _bits(b))
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _bn_buffers(module):

@@ -3,16 +3,16 @@ adam_multi_guarded_hyper_kernel, grad_guard_finalize_hyper_kernel; wsmg_adam_ste
 wsmgmap.optim.Adam(hyper_on_device=True).sync_hyper(); wsmgmap.graph.GraphedUpdate), so that a step captured in a HIP graph follows
 `param_groups` edits, `torch.optim.lr_scheduler` and a new `max_grad_norm`.
 
-Three yardsticks.  (1) THE SAME BITS as the by-value kernels of the parent commit (adam_multi_kernel, adam_multi_guarded_kernel,
-grad_guard_finalize_kernel: their device code is unchanged) for equal values — `torch.equal` on int32 views, no tolerance.
+Three yardsticks.  (1) THE SAME BITS as the by-value kernels (adam_multi_kernel, adam_multi_guarded_kernel,
+grad_guard_finalize_kernel: the same element step, adam1, behind another front end) for equal values — `torch.equal` on int32 views, no
+tolerance.
 (2) float64 `torch.optim.Adam` (+ `clip_grad_norm_`) on the same schedule at the project's Adam bar, rtol 2e-6 / atol 1e-7, not
 widened: the record adds no rounding (the values reach the kernel as the float32 a by-value argument would be).  (3) What the flag is
 for: a replayed graph steps with the values of NOW; without the flag it steps with the values of its capture (asserted too).
 
-Tensors as tests/test_gpu_adam_guard.py lays them out: sizes around the 4-element vector and the 4 096-element workgroup, once 16-byte
+Tensors as tests/adam_util.py lays them out: sizes around the 4-element vector and the 4 096-element workgroup, once 16-byte
 aligned and once one float off, then ragged small sizes up to 50 tensors (the table of 48 spills into a second launch); values from
 oracle.detfill."""
-import ctypes
 import functools
 import warnings
 
@@ -20,89 +20,20 @@ import numpy as np
 import pytest
 import torch
 
+import adam_util
+from adam_util import ALL_SIZES, SIZES, TOTAL_BLOCKS, _bits, _norm64, _ptr, _stream
 from oracle import cases
-from oracle import detfill as df
 from util import T, state_dict_values
 
 pytestmark = pytest.mark.gpu
 
-SIZES = [1, 3, 4, 4095, 4096, 4097, 8193]
-ALL_SIZES = SIZES + SIZES + [5 + 7 * i for i in range(50 - 2 * len(SIZES))]
-CHUNK = 4096
-TOTAL_BLOCKS = sum((n + CHUNK - 1) // CHUNK for n in ALL_SIZES)
 EPS = 1e-8
 RTOL, ATOL = 2e-6, 1e-7
 # (lr, weight_decay, betas) of four consecutive steps: each of the three changes at least once
 SCHED = [(2.5e-4, 0.0, (0.9, 0.999)), (1.25e-4, 0.01, (0.9, 0.999)), (1.25e-4, 0.01, (0.8, 0.99)), (5e-5, 0.0, (0.85, 0.995))]
 PICK = [1, 2, 5, 6, len(SIZES) + 6, len(ALL_SIZES) - 1]            # 3, 4, 4097, 8193 elements, 8193 unaligned, 250: the graph tests
-
-
-@functools.lru_cache(maxsize=None)
-def _values():
-    """[(offset in floats from a 16-byte boundary, (p, g, m, v))] — computed once, never written."""
-    out = []
-    for i, n in enumerate(ALL_SIZES):
-        off = 1 if len(SIZES) <= i < 2 * len(SIZES) else 0
-        vals = [df.uniform(f"hyper.{i}.{what}", (n,), sc) for what, sc in (("p", 2.0), ("g", 0.2), ("m", 0.02))]
-        vals.append(np.abs(df.uniform(f"hyper.{i}.v", (n,), 0.002)))
-        for a in vals:
-            a.setflags(write=False)
-        out.append((off, tuple(vals)))
-    return out
-
-
-class DevSet:
-    """The tensors on the device, each a view into a zeroed buffer with 8 floats of slack: .views[i] = [p, g, m, v]."""
-
-    def __init__(self, values=None):
-        self.values = _values() if values is None else values
-        self.bufs, self.views = [], []
-        for off, arrays in self.values:
-            row = []
-            for a in arrays:
-                buf = torch.zeros(a.size + 8, device="cuda")
-                assert buf.data_ptr() % 16 == 0
-                view = buf[off:off + a.size]
-                view.copy_(T(a))
-                row.append(view)
-                self.bufs.append((off, a.size, buf))
-            assert row[0].data_ptr() % 16 == 4 * off
-            self.views.append(row)
-
-    def descs(self):
-        from wsmgmap.optim import _AdamDesc
-        d = (_AdamDesc * len(self.views))()
-        for x, (p, g, m, v) in zip(d, self.views):
-            x.param, x.grad, x.exp_avg, x.exp_avg_sq, x.n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
-        return d
-
-    def params(self):
-        out = []
-        for p, g, _, _ in self.views:
-            q = torch.nn.Parameter(p)
-            assert q.data_ptr() == p.data_ptr()
-            q.grad = g
-            out.append(q)
-        return out
-
-    def slack_untouched(self):
-        return all(bool((buf[:off] == 0).all()) and bool((buf[off + n:] == 0).all()) for off, n, buf in self.bufs)
-
-
-def _bits(t):
-    return t.detach().contiguous().view(torch.int32)
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _ptr(t, byte_offset=0):
-    return ctypes.c_void_p(t.data_ptr() + byte_offset)
-
-
-def _norm64(values):
-    return float(torch.linalg.vector_norm(torch.cat([T(g).double() for _, (_, g, _, _) in values])))
+_values = functools.partial(adam_util._values, "hyper")            # this file's numbers
+DevSet = functools.partial(adam_util.DevSet, "hyper")
 
 
 def _split(items, n_groups):
@@ -155,6 +86,35 @@ def _form(form, values):
     return dict(capturable=True) if form == "capturable" else dict(max_grad_norm=0.5 * _norm64(values), skip_nonfinite=True)
 
 
+def _float64_adam(values, n_groups=1):
+    """(parameters, torch.optim.Adam) in float64 over the values, with their moments at step 0."""
+    qs = [torch.nn.Parameter(T(p).double()) for _, (p, _, _, _) in values]
+    ref = torch.optim.Adam([{"params": g} for g in _split(qs, n_groups)], lr=1e-3, eps=EPS)
+    for q, (_, (_, _, m, v)) in zip(qs, values):
+        ref.state[q] = {"step": torch.tensor(0.0), "exp_avg": T(m).double().clone(), "exp_avg_sq": T(v).double().clone()}
+    return qs, ref
+
+
+def _float64_step(qs, ref, values, max_norm=None):
+    for q, (_, (_, g, _, _)) in zip(qs, values):
+        q.grad = T(g).double().clone()
+    if max_norm is not None:
+        torch.nn.utils.clip_grad_norm_(qs, max_norm)
+    ref.step()
+
+
+def _within_the_adam_bar(name, qs, ref, state):
+    """Parameters and both moments ([(p, exp_avg, exp_avg_sq)]) against the float64 optimizer's at rtol 2e-6 / atol 1e-7."""
+    worst = 0.0
+    for i, (q, (p, m, v)) in enumerate(zip(qs, state)):
+        s = ref.state[q]
+        for what, got, want in (("p", p, q.detach()), ("m", m, s["exp_avg"]), ("v", v, s["exp_avg_sq"])):
+            got = got.detach().double().cpu().reshape(want.shape)
+            worst = max(worst, float(((got - want).abs() / (ATOL / RTOL + want.abs())).max()))
+            torch.testing.assert_close(got, want, rtol=RTOL, atol=ATOL, msg=lambda t: f"tensor {i} {what}: {t}")
+    print(f"{name}: worst |err| / (atol/rtol + |ref|) against float64 = {worst:.3e} (bar {RTOL:.1e})")
+
+
 def _record_rows(opt):
     """What the record should hold, as float32 rows."""
     rows = [[g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], 0, 0, 0] for g in opt.param_groups]
@@ -177,11 +137,7 @@ def test_schedule_gives_the_by_value_bits_and_matches_float64_adam(form, n_group
     pa, oa = _adam(da, n_groups, hyper_on_device=True, **kw)
     pb, ob = _adam(db, n_groups, **kw)
     assert oa.hyper_record.shape == (n_groups + 1, 8) and oa._hyper_stage.is_pinned()
-    # the float64 oracle
-    qs = [torch.nn.Parameter(T(p).double()) for _, (p, _, _, _) in values]
-    ref = torch.optim.Adam([{"params": g} for g in _split(qs, n_groups)], lr=1e-3, eps=EPS)
-    for q, (_, (_, _, m, v)) in zip(qs, values):
-        ref.state[q] = {"step": torch.tensor(0.0), "exp_avg": T(m).double().clone(), "exp_avg_sq": T(v).double().clone()}
+    qs, ref = _float64_adam(values, n_groups)                       # the float64 oracle
     for k in range(len(SCHED)):
         for opt in (oa, ob, ref):
             _apply(opt, k)
@@ -190,23 +146,53 @@ def test_schedule_gives_the_by_value_bits_and_matches_float64_adam(form, n_group
         torch.cuda.synchronize()
         _same_bits(f"{form}, {n_groups} group(s), step {k + 1}", pa, oa, pb, ob)
         assert torch.equal(oa.hyper_record.cpu(), _record_rows(oa)), "the record is not param_groups' values as float32"
-        for q, (_, (_, g, _, _)) in zip(qs, values):
-            q.grad = T(g).double().clone()
-        if form == "guarded":
-            torch.nn.utils.clip_grad_norm_(qs, kw["max_grad_norm"])
-        ref.step()
+        _float64_step(qs, ref, values, kw.get("max_grad_norm"))
     assert oa.sync_hyper() is False                                   # nothing changed since the last step
     if form == "guarded":
         assert float(oa._guard[1]) < 0.51 and oa.skipped_steps == 0 and float(oa._guard_step) == len(SCHED)
-    worst = 0.0
-    for i, (q, (p, m, v)) in enumerate(zip(qs, _state(pa, oa))):
-        s = ref.state[q]
-        for what, got, want in (("p", p, q.detach()), ("m", m, s["exp_avg"]), ("v", v, s["exp_avg_sq"])):
-            got = got.detach().double().cpu().reshape(want.shape)
-            worst = max(worst, float(((got - want).abs() / (ATOL / RTOL + want.abs())).max()))
-            torch.testing.assert_close(got, want, rtol=RTOL, atol=ATOL, msg=lambda t: f"tensor {i} {what}: {t}")
-    print(f"{form}, {n_groups} group(s): worst |err| / (atol/rtol + |ref|) against float64 = {worst:.3e} (bar {RTOL:.1e})")
+    _within_the_adam_bar(f"{form}, {n_groups} group(s)", qs, ref, _state(pa, oa))
     assert da.slack_untouched() and db.slack_untouched()
+
+
+# ----------------------------------------------------------------------------- 1b. the one element step where the three loops meet
+MEET = [(1, 0), (3, 0), (4, 0), (7, 0), (4096, 0), (4097, 0), (4097, 1), (8195, 0)]     # (elements, floats off a 16-byte boundary)
+
+
+@functools.lru_cache(maxsize=None)
+def _meet_values():
+    """One set in which the 16-byte body, its scalar tail and the misaligned scalar loop all run and a tensor crosses a chunk edge:
+    4 097 elements once aligned (a body of 4 096, then a second workgroup's tail of one) and once one float off; 8 195 = two full
+    chunks and a tail of three; 1, 3, 7: tails only or a body of one vector."""
+    return [adam_util._fill(f"hyper.meet.{i}", off, n) for i, (n, off) in enumerate(MEET)]
+
+
+def test_one_element_step_on_every_loop_gives_every_front_end_the_same_bits():
+    """Three steps with weight_decay = 0.01 (schedule entry 1) through the capturable by-value form and its hyper_on_device twin,
+    and through the guarded pair clipped at half the norm (coef < 1): within each pair parameters, both moments, the guard record
+    and the device step count are equal bit for bit after every step, and all four sit inside the Adam bar of float64
+    clip_grad_norm_ + torch.optim.Adam."""
+    values = _meet_values()
+    for form in ("capturable", "guarded"):
+        kw = _form(form, values)
+        da, db = DevSet(values=values), DevSet(values=values)
+        pa, oa = _adam(da, hyper_on_device=True, **kw)
+        pb, ob = _adam(db, **kw)
+        qs, ref = _float64_adam(values)
+        for opt in (oa, ob, ref):
+            _apply(opt, 1)
+        assert oa.param_groups[0]["weight_decay"] == 0.01
+        for k in range(3):
+            oa.step()
+            ob.step()
+            torch.cuda.synchronize()
+            _same_bits(f"{form}, step {k + 1}", pa, oa, pb, ob)
+            _float64_step(qs, ref, values, kw.get("max_grad_norm"))
+        assert _device_step(oa) == _device_step(ob) == 3.0
+        if form == "guarded":
+            assert float(oa._guard[1]) < 0.51 and float(ob._guard[1]) < 0.51 and oa.skipped_steps == 0
+        _within_the_adam_bar(f"{form}, hyper_on_device", qs, ref, _state(pa, oa))
+        _within_the_adam_bar(f"{form}, by value", qs, ref, _state(pb, ob))
+        assert da.slack_untouched() and db.slack_untouched()
 
 
 # ----------------------------------------------------------------------------- 3 + 4. inside a HIP graph
@@ -215,7 +201,7 @@ def _captured(form, n_groups=2):
     the same step.  Six small tensors with static gradient buffers, in two groups (the 4-tensor group and the 2-tensor group)."""
     values = [_values()[i] for i in PICK]
     kw = _form(form, values)
-    ds, twin = DevSet(values), DevSet(values)
+    ds, twin = DevSet(values=values), DevSet(values=values)
     from wsmgmap import optim
 
     def make(s, **more):
@@ -346,7 +332,7 @@ def test_skip_under_replay_writes_nothing_and_the_next_replay_uses_the_new_lr():
 def test_stale_record_under_capture_raises_and_invalid_values_leave_the_record_alone():
     from wsmgmap import _abi, optim
     values = [_values()[i] for i in PICK]
-    ds = DevSet(values)
+    ds = DevSet(values=values)
     params, opt = _adam(ds, capturable=True, hyper_on_device=True)
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())

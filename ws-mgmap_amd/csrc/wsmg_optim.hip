@@ -8,15 +8,19 @@
 // table's block prefix.  Arithmetic as torch.optim.Adam (amsgrad = False, maximize = False), in its order:
 //     g' = g + wd p;  m += (1 - b1) (g' - m);  v = b2 v + (1 - b2) g' g';  p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)
 //
-// The GUARDED step (wsmg_grad_norm_multi + wsmg_adam_step_multi_guarded) puts the global gradient norm in front of it, on the
-// device: grad_sumsq_multi_kernel writes one float64 sum of squares per workgroup (same table, same 4 096-element ownership, no
-// atomics), grad_guard_finalize_kernel adds them in a fixed order and writes the guard record {norm, coef, skip, skipped} and
-// the step count, and adam_multi_guarded_kernel returns before its first load when `skip` is set and reads g * coef otherwise
-// (torch.nn.utils.clip_grad_norm_'s arithmetic, without writing the gradients).  No host synchronisation anywhere.
-//
-// The HYPER forms (wsmg_adam_step_multi_hyper, wsmg_grad_norm_multi_hyper) read lr, betas, eps, weight_decay and max_grad_norm from
-// a float32 record in device memory instead of their kernel arguments, which a captured HIP graph freezes: the host refreshes the
-// record between replays (wsmgmap.optim.Adam(hyper_on_device=True).sync_hyper()).  No kernel writes the record.
+// ONE element step (adam1), ONE table of chunks (ChunkTable, chunk_tensor + locate_chunk, for_each_batch on the host), ONE descriptor check
+// (check_descs, before an entry point's first launch), and four front ends that differ in where the step's inputs come from:
+//   wsmg_adam_step_multi          hyper-parameters and bias corrections by value
+//   wsmg_adam_step_multi_dev      the step COUNT from device memory (a captured HIP graph freezes kernel arguments)
+//   wsmg_adam_step_multi_guarded  the _dev form behind the guard record {norm, coef, skip, skipped} of wsmg_grad_norm_multi:
+//                                 grad_sumsq_multi_kernel writes one float64 sum of squares per workgroup (same table, same 4 096-
+//                                 element ownership, no atomics), grad_guard_finalize_kernel adds them in a fixed order and writes the
+//                                 record and the step count, and the step returns before its first load when `skip` is set and reads
+//                                 g * coef otherwise (torch.nn.utils.clip_grad_norm_'s arithmetic, without writing the gradients)
+//   wsmg_adam_step_multi_hyper    the _dev / _guarded form with lr, betas, eps, weight_decay (and wsmg_grad_norm_multi_hyper with
+//                                 max_grad_norm) read from a float32 record in device memory that the host refreshes between replays
+//                                 (wsmgmap.optim.Adam(hyper_on_device=True).sync_hyper()); no kernel writes the record
+// No host synchronisation anywhere.
 #include "wsmg_common.h"
 
 namespace {
@@ -26,43 +30,76 @@ constexpr int ADAM_CHUNK = 4096;  // elements per workgroup
 // The hyper record (include/wsmgmap.h): one 8-float row per parameter group, then the guard's row.
 enum { HYPER_LR = 0, HYPER_BETA1 = 1, HYPER_BETA2 = 2, HYPER_EPS = 3, HYPER_WD = 4, HYPER_MAX_NORM = 0 };
 
+// The tensors of one launch and the workgroups that own their chunks; every batch struct below embeds it and adds its pointers.
+struct ChunkTable {
+  int first_block[ADAM_MAX + 1];  // prefix of workgroups per tensor
+  long long n[ADAM_MAX];
+  int count;
+};
+
+struct Chunk { int tensor; long long i0, i1; };   // elements [i0, i1) of table entry `tensor`
+
+// This workgroup's tensor: t with first_block[t] <= blockIdx.x < first_block[t + 1].
+__device__ __forceinline__ int chunk_tensor(const ChunkTable& tb) {
+  int lo = 0, hi = tb.count;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if ((int)blockIdx.x >= tb.first_block[mid]) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// This workgroup's chunk, (tensor, i0, i1): its 4 096 elements of its tensor.  Callers that pass t = chunk_tensor(tb) have loaded
+// their pointers of entry t in between, so that those loads and the table's are issued together.
+__device__ __forceinline__ Chunk locate_chunk(const ChunkTable& tb, int t) {
+  const long long n = tb.n[t];
+  const long long i0 = (long long)((int)blockIdx.x - tb.first_block[t]) * ADAM_CHUNK;
+  return {t, i0, i0 + ADAM_CHUNK < n ? i0 + ADAM_CHUNK : n};
+}
+
+// A read-only walk over a chunk of a gradient: f(g[i]) for this thread's elements, in the order the float64 sums depend on —
+// 16-byte loads of an aligned gradient with j = 0..3 in order, then the scalar tail; a misaligned gradient element by element.
+template <class F>
+__device__ __forceinline__ void walk_grad(const float* __restrict__ g, long long i0, long long i1, F f) {
+  if (((uintptr_t)g & 15) == 0) {
+    const long long nv = i0 + ((i1 - i0) & ~3ll);
+    for (long long i = i0 + 4 * (long long)threadIdx.x; i < nv; i += 4 * 256) {
+      const f32x4 gg = ld4(g + i);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) f(gg[j]);
+    }
+    for (long long i = nv + threadIdx.x; i < i1; i += 256) f(g[i]);
+  } else {
+    for (long long i = i0 + threadIdx.x; i < i1; i += 256) f(g[i]);
+  }
+}
+
+struct AdamHyper {         // what the element step reads: 1 - beta1, beta2, 1 - beta2, eps, weight_decay
+  float beta1c, beta2, beta2c, eps, wd;
+};
+
 struct AdamBatch {
   float* p[ADAM_MAX];
   const float* g[ADAM_MAX];
   float* m[ADAM_MAX];
   float* v[ADAM_MAX];
-  int first_block[ADAM_MAX + 1];  // prefix of workgroups per tensor
-  long long n[ADAM_MAX];
-  int count;
-  float lr_bc1, beta1c, beta2, beta2c, sqrt_bc2, eps, wd;
+  ChunkTable tab;
+  AdamHyper h;             // by value (the _hyper kernels derive theirs from the record's row and ignore this one, lr and beta1)
+  float lr_bc1, sqrt_bc2;  // by value, when step_dev is null
   const float* step_dev;   // or null: the step count lives on the device (HIP-graph replay: the arguments are frozen at capture) and
-  float lr, beta1;         //          the bias corrections are computed from it here
-  const float* guard;      // or null: the guard record of grad_guard_finalize_kernel (read by adam_multi_guarded_kernel only)
+  float lr, beta1;         //          the bias corrections are computed from it in the kernel
+  const float* guard;      // or null: the guard record of grad_guard_finalize_kernel (read by the guarded kernels only)
   const float* hyper;      // or null: this group's row of the hyper record {lr, beta1, beta2, eps, weight_decay, 0, 0, 0} (read by the
-};                         //          _hyper kernels only, which then ignore every by-value hyper-parameter above)
+};                         //          _hyper kernels only)
 
-struct AdamHyper {         // what adam1 reads of AdamBatch, as the _hyper kernels derive it from the record's row
-  float beta1c, beta2, beta2c, eps, wd;
-};
-
-// VEC: the call sits in the 16-byte loop (used by the AdamHyper form below only).
-template <bool GUARD, bool VEC>
-__device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, const AdamBatch& b, float lr_bc1, float sqrt_bc2,
-                                      float coef) {
-  if (GUARD) g *= coef;
-  if (b.wd != 0.f) g = fmaf(b.wd, p, g);
-  m = m + b.beta1c * (g - m);
-  v = v * b.beta2 + b.beta2c * g * g;
-  const float denom = sqrtf(v) / sqrt_bc2 + b.eps;
-  p = p - lr_bc1 * (m / denom);
-}
-
-// The same element step for the _hyper kernels, which must give the by-value kernels' bits.  Above, which products are fused into
-// which sums is the compiler's choice (-ffp-contract=fast), and it depends on where the operands live: with beta2 and beta2c
-// adjacent in the kernel arguments it computes v as fma(v, beta2, (beta2c g) g) in the 16-byte loop and as fma(g, beta2c g, v beta2)
-// in the two scalar loops, m as fma(beta1c, g - m, m) and p as fma(-lr_bc1, m / denom, p) everywhere, and g * coef as a product of
-// its own.  With the operands in the registers the record's loads leave them in, it chose otherwise (v unfused in the scalar loops),
-// so the forms are spelled out here and nothing else may be contracted.  tests/test_gpu_adam_hyper.py compares the bits on every path.
+// THE element step.  These forms define it, rounding by rounding, for every front end; nothing else may be contracted:
+//     g' = coef g (GUARD only: a product of its own);  g' = fma(wd, p, g') unless wd == 0
+//     m  = fma(1 - b1, g' - m, m)
+//     v  = fma(v, b2, ((1 - b2) g') g') in the 16-byte loop (VEC),  fma(g', (1 - b2) g', v b2) in the two scalar loops
+//     p  = fma(-lr_bc1, m / (sqrt(v) / sqrt_bc2 + eps), p)
+// The two forms of v round differently and which loop an element meets is fixed by its address and index, so both are part of the
+// definition: a step's bits do not depend on the front end, the compiler's contraction choices or the layout of AdamBatch.
+// tests/test_gpu_adam_hyper.py compares the front ends' bits on every path.
 template <bool GUARD, bool VEC>
 __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, const AdamHyper& h, float lr_bc1, float sqrt_bc2,
                                       float coef) {
@@ -76,21 +113,16 @@ __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, con
   p = fmaf(-lr_bc1, m / denom, p);
 }
 
-// One workgroup's 4 096 elements of its tensor; h holds the hyper-parameters adam1 reads.
-template <bool GUARD, class H>
-__device__ __forceinline__ void adam_chunk(const AdamBatch& b, const H& h, float lr_bc1, float sqrt_bc2, float coef) {
-  int lo = 0, hi = b.count;          // tensor t with first_block[t] <= blockIdx.x < first_block[t + 1]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if ((int)blockIdx.x >= b.first_block[mid]) lo = mid; else hi = mid;
-  }
-  float* __restrict__ p = b.p[lo];
-  const float* __restrict__ g = b.g[lo];
-  float* __restrict__ m = b.m[lo];
-  float* __restrict__ v = b.v[lo];
-  const long long n = b.n[lo];
-  const long long i0 = (long long)((int)blockIdx.x - b.first_block[lo]) * ADAM_CHUNK;
-  const long long i1 = i0 + ADAM_CHUNK < n ? i0 + ADAM_CHUNK : n;
+// One workgroup's 4 096 elements of its tensor (a loop nest of its own: it loads and stores four arrays).
+template <bool GUARD>
+__device__ __forceinline__ void adam_chunk(const AdamBatch& b, const AdamHyper& h, float lr_bc1, float sqrt_bc2, float coef) {
+  const int t = chunk_tensor(b.tab);
+  float* __restrict__ p = b.p[t];
+  const float* __restrict__ g = b.g[t];
+  float* __restrict__ m = b.m[t];
+  float* __restrict__ v = b.v[t];
+  const Chunk c = locate_chunk(b.tab, t);
+  const long long i0 = c.i0, i1 = c.i1;
   const bool vec = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0);
   if (vec) {
     const long long nv = i0 + ((i1 - i0) & ~3ll);
@@ -111,11 +143,10 @@ __device__ __forceinline__ void adam_chunk(const AdamBatch& b, const H& h, float
   }
 }
 
-// GUARD = false is the unguarded step, the code it was before the guard existed (the guard pointer is not read); GUARD = true
-// reads skip and coef once, before anything else.  HYPER = false takes the hyper-parameters from the kernel arguments, the code it
-// was before the record existed (the hyper pointer is not read); HYPER = true reads its group's row once, here, through a
-// wave-uniform address, and derives 1 - beta in float and the bias corrections in double from *step_dev with the expressions of
-// adam_launch and of the step_dev branch below: equal values give equal bits.
+// The front ends.  GUARD reads skip and coef once, before anything else (otherwise the guard pointer is not read).  HYPER reads its
+// group's row once, here, through a wave-uniform address, and derives 1 - beta in float as adam_launch does (otherwise the hyper
+// pointer is not read and the values are the kernel arguments).  With a device step count the bias corrections are 1 - beta^step in
+// double, the host's expressions: equal values give equal bits.
 template <bool GUARD, bool HYPER>
 __device__ __forceinline__ void adam_multi(const AdamBatch& b) {
   float coef = 1.f;
@@ -142,9 +173,10 @@ __device__ __forceinline__ void adam_multi(const AdamBatch& b) {
   if (b.step_dev) {   // 1 - beta^step in double, as the host path does
     const double st = (double)*b.step_dev;
     lr_bc1 = (float)((double)b.lr / (1.0 - pow((double)b.beta1, st)));
-    sqrt_bc2 = (float)sqrt(1.0 - pow((double)b.beta2, st));
+    sqrt_bc2 = (float)sqrt(1.0 - pow((double)b.h.beta2, st));
   }
-  adam_chunk<GUARD>(b, b, lr_bc1, sqrt_bc2, coef);
+  const AdamHyper h = b.h;
+  adam_chunk<GUARD>(b, h, lr_bc1, sqrt_bc2, coef);
 }
 
 __global__ __launch_bounds__(256) void adam_multi_kernel(AdamBatch b) { adam_multi<false, false>(b); }
@@ -154,12 +186,10 @@ __global__ __launch_bounds__(256) void adam_multi_guarded_hyper_kernel(AdamBatch
 
 // ---- the guard: global gradient norm -> {norm, coef, skip, skipped}
 
-struct GradBatch {         // adam_multi_kernel's table, the gradients' half
+struct GradBatch {         // the table's gradients and this launch's slice of the partials: one float64 per workgroup
   const float* g[ADAM_MAX];
-  int first_block[ADAM_MAX + 1];
-  long long n[ADAM_MAX];
-  int count;
-  double* partials;        // this launch's slice: one float64 per workgroup
+  ChunkTable tab;
+  double* partials;
 };
 
 // fixed order: the wave's xor tree, then the four waves in index order (thread 0 returns the sum)
@@ -172,27 +202,11 @@ __device__ __forceinline__ double block_sum_d(double acc, double* red) {
 
 __global__ __launch_bounds__(256) void grad_sumsq_multi_kernel(GradBatch b) {
   __shared__ double red[4];
-  int lo = 0, hi = b.count;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if ((int)blockIdx.x >= b.first_block[mid]) lo = mid; else hi = mid;
-  }
-  const float* __restrict__ g = b.g[lo];
-  const long long n = b.n[lo];
-  const long long i0 = (long long)((int)blockIdx.x - b.first_block[lo]) * ADAM_CHUNK;
-  const long long i1 = i0 + ADAM_CHUNK < n ? i0 + ADAM_CHUNK : n;
+  const int t = chunk_tensor(b.tab);
+  const float* __restrict__ g = b.g[t];
+  const Chunk c = locate_chunk(b.tab, t);
   double acc = 0.0;        // float64: gradients of 1e30 square to 1e60, and the sum's order then costs nothing visible in float32
-  if (((uintptr_t)g & 15) == 0) {
-    const long long nv = i0 + ((i1 - i0) & ~3ll);
-    for (long long i = i0 + 4 * (long long)threadIdx.x; i < nv; i += 4 * 256) {
-      const f32x4 gg = ld4(g + i);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc += (double)gg[j] * (double)gg[j];
-    }
-    for (long long i = nv + threadIdx.x; i < i1; i += 256) acc += (double)g[i] * (double)g[i];
-  } else {
-    for (long long i = i0 + threadIdx.x; i < i1; i += 256) acc += (double)g[i] * (double)g[i];
-  }
+  walk_grad(g, c.i0, c.i1, [&](float x) { acc += (double)x * (double)x; });
   const double sum = block_sum_d(acc, red);
   if (threadIdx.x == 0) b.partials[blockIdx.x] = sum;
 }
@@ -238,8 +252,8 @@ __global__ __launch_bounds__(256) void grad_guard_finalize_hyper_kernel(const do
 // ---- the per-tensor gradient report (wsmg_grad_report_multi / wsmg_grad_stats_multi): which tensor made the guard skip
 //
 // Shape: three kernels behind the norm's launches, none of which the step's own kernels depend on.
-//   grad_scan_multi_kernel     grad_sumsq_multi_kernel's ownership (one 256-thread workgroup per 4 096-element chunk, the same search
-//                              over first_block, 16-byte loads of an aligned gradient with scalar tails): max |g| over the finite
+//   grad_scan_multi_kernel     grad_sumsq_multi_kernel's ownership and walk (one 256-thread workgroup per 4 096-element chunk,
+//                              locate_chunk, walk_grad): max |g| over the finite
 //                              elements, NaN count, Inf count of the chunk -> 4 words of the scan workspace, at the chunk's index in
 //                              the norm's partials.
 //   grad_report_fold_kernel    one workgroup per tensor (ADAM_MAX per launch, table in the kernel arguments): the tensor's float64
@@ -253,9 +267,7 @@ __global__ __launch_bounds__(256) void grad_guard_finalize_hyper_kernel(const do
 
 struct ScanBatch {         // GradBatch with the scan workspace's slice: four words per workgroup
   const float* g[ADAM_MAX];
-  int first_block[ADAM_MAX + 1];
-  long long n[ADAM_MAX];
-  int count;
+  ChunkTable tab;
   uint32_t* scan;
 };
 
@@ -307,27 +319,11 @@ __device__ __forceinline__ void block_scan_reduce(uint32_t& mx, uint32_t& nan, u
 
 __global__ __launch_bounds__(256) void grad_scan_multi_kernel(ScanBatch b) {
   __shared__ uint32_t red[12];
-  int lo = 0, hi = b.count;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if ((int)blockIdx.x >= b.first_block[mid]) lo = mid; else hi = mid;
-  }
-  const float* __restrict__ g = b.g[lo];
-  const long long n = b.n[lo];
-  const long long i0 = (long long)((int)blockIdx.x - b.first_block[lo]) * ADAM_CHUNK;
-  const long long i1 = i0 + ADAM_CHUNK < n ? i0 + ADAM_CHUNK : n;
+  const int t = chunk_tensor(b.tab);
+  const float* __restrict__ g = b.g[t];
+  const Chunk c = locate_chunk(b.tab, t);
   uint32_t mx = 0, nan = 0, inf = 0;
-  if (((uintptr_t)g & 15) == 0) {
-    const long long nv = i0 + ((i1 - i0) & ~3ll);
-    for (long long i = i0 + 4 * (long long)threadIdx.x; i < nv; i += 4 * 256) {
-      const f32x4 gg = ld4(g + i);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) scan1(gg[j], mx, nan, inf);
-    }
-    for (long long i = nv + threadIdx.x; i < i1; i += 256) scan1(g[i], mx, nan, inf);
-  } else {
-    for (long long i = i0 + threadIdx.x; i < i1; i += 256) scan1(g[i], mx, nan, inf);
-  }
+  walk_grad(g, c.i0, c.i1, [&](float x) { scan1(x, mx, nan, inf); });
   block_scan_reduce(mx, nan, inf, red);
   if (threadIdx.x == 0) {
     uint32_t* __restrict__ out = b.scan + 4 * (long long)blockIdx.x;
@@ -409,51 +405,86 @@ __global__ __launch_bounds__(256) void grad_report_latch_kernel(const uint32_t* 
 
 }  // namespace
 
-static int adam_launch(const WsmgAdamDesc* descs, int n, float lr, float beta1, float beta2, float eps, float weight_decay,
+// ---- the host side: one descriptor check, one batching loop
+
+// What an entry point needs of a descriptor with n > 0 (of every one: 0 <= n <= max_n).
+enum { DESC_GRAD = 0, DESC_ALL = 1, DESC_ALIGN4 = 2 };   // grad only / all four pointers; | DESC_ALIGN4: each a multiple of 4
+constexpr long long DESC_MAX_N = (1ll << 30) * ADAM_CHUNK;
+
+// THE descriptor check, run by every entry point before its first launch: the list's chunk total (>= 0; at most 2^30, the grid's
+// bound), or WSMG_EINVAL (the error codes are negative, so one return value carries both: callers test `< 0`).
+static long long check_descs(const WsmgAdamDesc* descs, int n, int need, long long max_n) {
+  if (n < 0 || (n > 0 && !descs)) return WSMG_EINVAL;
+  long long total = 0;
+  for (int i = 0; i < n; ++i) {
+    const WsmgAdamDesc& d = descs[i];
+    if (d.n < 0 || d.n > max_n) return WSMG_EINVAL;
+    if (d.n == 0) continue;
+    if (!d.grad || ((need & DESC_ALL) && (!d.param || !d.exp_avg || !d.exp_avg_sq))) return WSMG_EINVAL;
+    uintptr_t bits = (uintptr_t)d.grad;
+    if (need & DESC_ALL) bits |= (uintptr_t)d.param | (uintptr_t)d.exp_avg | (uintptr_t)d.exp_avg_sq;
+    if ((need & DESC_ALIGN4) && (bits & 3)) return WSMG_EINVAL;
+    total += (d.n + ADAM_CHUNK - 1) / ADAM_CHUNK;
+    if (total > (1ll << 30)) return WSMG_EINVAL;
+  }
+  return total;
+}
+
+// THE batching loop over checked descs: at most ADAM_MAX tensors per launch, descriptors with n == 0 own no chunk and no table
+// entry.  The caller's batch b (its other fields already set) is filled in place: slot(k, desc) stores entry k's pointers,
+// launch(blocks, base) launches `blocks` workgroups whose first chunk is chunk `base` of the list.  Returns the chunk total.
+template <class Slot, class Launch>
+static int for_each_batch(const WsmgAdamDesc* descs, int n, ChunkTable& tb, Slot slot, Launch launch) {
+  int base = 0;
+  for (int i = 0; i < n;) {
+    tb.count = 0;
+    int blocks = 0;
+    for (; i < n && tb.count < ADAM_MAX; ++i) {
+      if (descs[i].n == 0) continue;
+      const int k = tb.count++;
+      slot(k, descs[i]);
+      tb.n[k] = descs[i].n;
+      tb.first_block[k] = blocks;
+      blocks += (int)((descs[i].n + ADAM_CHUNK - 1) / ADAM_CHUNK);
+    }
+    if (!tb.count) continue;
+    tb.first_block[tb.count] = blocks;
+    launch(blocks, base);
+    base += blocks;
+  }
+  return base;
+}
+
+static int adam_launch(const WsmgAdamDesc* descs, int n, int need, float lr, float beta1, float beta2, float eps, float weight_decay,
                        double bias_correction1, double bias_correction2, const float* step_dev, const float* guard,
                        const float* hyper, wsmg_stream_t s) {
-  if (n < 0 || (n > 0 && !descs)) return WSMG_EINVAL;
   if (!step_dev && (!(bias_correction1 > 0.0) || !(bias_correction2 > 0.0))) return WSMG_EINVAL;
-  for (int i = 0; i < n;) {
-    AdamBatch b;
-    b.count = 0;
-    int blocks = 0;
-    for (; i < n && b.count < ADAM_MAX; ++i) {
-      const WsmgAdamDesc& d = descs[i];
-      if (d.n < 0 || (d.n > 0 && (!d.param || !d.grad || !d.exp_avg || !d.exp_avg_sq))) return WSMG_EINVAL;
-      if (d.n == 0) continue;
-      const int k = b.count++;
-      b.p[k] = d.param; b.g[k] = d.grad; b.m[k] = d.exp_avg; b.v[k] = d.exp_avg_sq; b.n[k] = d.n;
-      b.first_block[k] = blocks;
-      const long long nb = (d.n + ADAM_CHUNK - 1) / ADAM_CHUNK;
-      if (nb > (1ll << 30) - blocks) return WSMG_EINVAL;
-      blocks += (int)nb;
-    }
-    if (!b.count) continue;
-    b.first_block[b.count] = blocks;
-    b.lr_bc1 = step_dev ? 0.f : (float)((double)lr / bias_correction1);
-    b.beta1c = 1.f - beta1;
-    b.beta2 = beta2;
-    b.beta2c = 1.f - beta2;
-    b.sqrt_bc2 = step_dev ? 1.f : (float)sqrt(bias_correction2);
-    b.eps = eps;
-    b.wd = weight_decay;
-    b.step_dev = step_dev;
-    b.lr = lr;
-    b.beta1 = beta1;
-    b.guard = guard;
-    b.hyper = hyper;
-    if (hyper && guard) hipLaunchKernelGGL(adam_multi_guarded_hyper_kernel, dim3((unsigned)blocks), dim3(256), 0, wsmg_s(s), b);
-    else if (hyper) hipLaunchKernelGGL(adam_multi_hyper_kernel, dim3((unsigned)blocks), dim3(256), 0, wsmg_s(s), b);
-    else if (guard) hipLaunchKernelGGL(adam_multi_guarded_kernel, dim3((unsigned)blocks), dim3(256), 0, wsmg_s(s), b);
-    else hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, wsmg_s(s), b);
-  }
+  if (check_descs(descs, n, need, DESC_MAX_N) < 0) return WSMG_EINVAL;
+  AdamBatch b;
+  b.h = {1.f - beta1, beta2, 1.f - beta2, eps, weight_decay};
+  b.lr_bc1 = step_dev ? 0.f : (float)((double)lr / bias_correction1);
+  b.sqrt_bc2 = step_dev ? 1.f : (float)sqrt(bias_correction2);
+  b.step_dev = step_dev;
+  b.lr = lr;
+  b.beta1 = beta1;
+  b.guard = guard;
+  b.hyper = hyper;
+  for_each_batch(descs, n, b.tab,
+                 [&](int k, const WsmgAdamDesc& d) { b.p[k] = d.param; b.g[k] = d.grad; b.m[k] = d.exp_avg; b.v[k] = d.exp_avg_sq; },
+                 [&](int blocks, int) {
+                   const dim3 grid((unsigned)blocks);
+                   if (hyper && guard) hipLaunchKernelGGL(adam_multi_guarded_hyper_kernel, grid, dim3(256), 0, wsmg_s(s), b);
+                   else if (hyper) hipLaunchKernelGGL(adam_multi_hyper_kernel, grid, dim3(256), 0, wsmg_s(s), b);
+                   else if (guard) hipLaunchKernelGGL(adam_multi_guarded_kernel, grid, dim3(256), 0, wsmg_s(s), b);
+                   else hipLaunchKernelGGL(adam_multi_kernel, grid, dim3(256), 0, wsmg_s(s), b);
+                 });
   WSMG_RETURN_LAUNCH();
 }
 
 extern "C" int wsmg_adam_step_multi(const WsmgAdamDesc* descs, int n, float lr, float beta1, float beta2, float eps, float weight_decay,
                                     double bias_correction1, double bias_correction2, wsmg_stream_t s) {
-  return adam_launch(descs, n, lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2, nullptr, nullptr, nullptr, s);
+  return adam_launch(descs, n, DESC_ALL, lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2, nullptr, nullptr,
+                     nullptr, s);
 }
 
 // The same step with the step COUNT read from device memory (one float32, already incremented for this step): what a captured
@@ -461,7 +492,7 @@ extern "C" int wsmg_adam_step_multi(const WsmgAdamDesc* descs, int n, float lr, 
 extern "C" int wsmg_adam_step_multi_dev(const WsmgAdamDesc* descs, int n, float lr, float beta1, float beta2, float eps,
                                         float weight_decay, const float* step_dev, wsmg_stream_t s) {
   if (!step_dev) return WSMG_EINVAL;
-  return adam_launch(descs, n, lr, beta1, beta2, eps, weight_decay, 0.0, 0.0, step_dev, nullptr, nullptr, s);
+  return adam_launch(descs, n, DESC_ALL, lr, beta1, beta2, eps, weight_decay, 0.0, 0.0, step_dev, nullptr, nullptr, s);
 }
 
 // The _dev form behind a guard record (wsmg_grad_norm_multi on the same stream, before it): nothing is written when the record's
@@ -469,65 +500,37 @@ extern "C" int wsmg_adam_step_multi_dev(const WsmgAdamDesc* descs, int n, float 
 extern "C" int wsmg_adam_step_multi_guarded(const WsmgAdamDesc* descs, int n, float lr, float beta1, float beta2, float eps,
                                             float weight_decay, const float* step_dev, const float* guard, wsmg_stream_t s) {
   if (!step_dev || !guard) return WSMG_EINVAL;
-  return adam_launch(descs, n, lr, beta1, beta2, eps, weight_decay, 0.0, 0.0, step_dev, guard, nullptr, s);
+  return adam_launch(descs, n, DESC_ALL, lr, beta1, beta2, eps, weight_decay, 0.0, 0.0, step_dev, guard, nullptr, s);
 }
 
 // The _dev / _guarded step (guard null / not null) with lr, beta1, beta2, eps and weight_decay read from hyper_row, one 8-float row
-// of the hyper record in device memory.  Unlike the forms above, which check a table as they fill it, every descriptor of every
-// launch is checked here before the first launch (and the workgroup total against 2^30, which is stricter than per launch).
+// of the hyper record in device memory.  This form also refuses pointers that are not multiples of 4.
 extern "C" int wsmg_adam_step_multi_hyper(const WsmgAdamDesc* descs, int n, const float* hyper_row, const float* step_dev,
                                           const float* guard, wsmg_stream_t s) {
-  if (n < 0 || (n > 0 && !descs) || !hyper_row || !step_dev) return WSMG_EINVAL;
+  if (!hyper_row || !step_dev) return WSMG_EINVAL;
   if (((uintptr_t)hyper_row & 3) || ((uintptr_t)step_dev & 3) || ((uintptr_t)guard & 3)) return WSMG_EINVAL;
-  long long total = 0;
-  for (int i = 0; i < n; ++i) {
-    const WsmgAdamDesc& d = descs[i];
-    if (d.n < 0 || (d.n > 0 && (!d.param || !d.grad || !d.exp_avg || !d.exp_avg_sq))) return WSMG_EINVAL;
-    if (d.n > 0 && (((uintptr_t)d.param | (uintptr_t)d.grad | (uintptr_t)d.exp_avg | (uintptr_t)d.exp_avg_sq) & 3)) return WSMG_EINVAL;
-    if (d.n > (1ll << 30) * ADAM_CHUNK) return WSMG_EINVAL;
-    total += (d.n + ADAM_CHUNK - 1) / ADAM_CHUNK;
-    if (total > (1ll << 30)) return WSMG_EINVAL;
-  }
-  return adam_launch(descs, n, 0.f, 0.f, 0.f, 0.f, 0.f, 0.0, 0.0, step_dev, guard, hyper_row, s);
+  return adam_launch(descs, n, DESC_ALL | DESC_ALIGN4, 0.f, 0.f, 0.f, 0.f, 0.f, 0.0, 0.0, step_dev, guard, hyper_row, s);
 }
 
-// The sum-of-squares launches over checked descs: chunk c of the list (descriptors with n == 0 own none) -> partials[c].  Returns the
-// chunk total.
+// The sum-of-squares launches over checked descs: chunk c of the list -> partials[c].  Returns the chunk total.
 static int grad_sumsq_launches(const WsmgAdamDesc* descs, int n, double* partials, wsmg_stream_t s) {
-  int base = 0;
-  for (int i = 0; i < n;) {
-    GradBatch b;
-    b.count = 0;
-    int blocks = 0;
-    for (; i < n && b.count < ADAM_MAX; ++i) {
-      if (descs[i].n == 0) continue;
-      const int k = b.count++;
-      b.g[k] = descs[i].grad; b.n[k] = descs[i].n;
-      b.first_block[k] = blocks;
-      blocks += (int)((descs[i].n + ADAM_CHUNK - 1) / ADAM_CHUNK);
-    }
-    if (!b.count) continue;
-    b.first_block[b.count] = blocks;
-    b.partials = partials + base;
-    hipLaunchKernelGGL(grad_sumsq_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, wsmg_s(s), b);
-    base += blocks;
-  }
-  return base;
+  GradBatch b;
+  return for_each_batch(descs, n, b.tab, [&](int k, const WsmgAdamDesc& d) { b.g[k] = d.grad; },
+                        [&](int blocks, int base) {
+                          b.partials = partials + base;
+                          hipLaunchKernelGGL(grad_sumsq_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, wsmg_s(s), b);
+                        });
 }
 
-// Global L2 norm of the descs' gradients (param / exp_avg / exp_avg_sq are not read) into the guard record.  Every argument is
-// checked, and the partials' capacity against the total workgroup count, before the first launch.
-// hyper_guard_row (or null): max_norm is read from it on the device and the by-value max_norm is ignored.
+// Global L2 norm of the descs' gradients (param / exp_avg / exp_avg_sq are not read) into the guard record.  The partials' capacity
+// is checked against the chunk total.  hyper_guard_row (or null): max_norm is read from it on the device and the by-value max_norm
+// is ignored.
 static int grad_norm_launch(const WsmgAdamDesc* descs, int n, double* partials, long long partials_cap, float max_norm,
                             const float* hyper_guard_row, int skip_nonfinite, float* guard, float* step_dev, wsmg_stream_t s) {
-  if (n < 0 || (n > 0 && !descs) || !guard || !partials || partials_cap < 0 || !(max_norm >= 0.f)) return WSMG_EINVAL;
+  if (!guard || !partials || partials_cap < 0 || !(max_norm >= 0.f)) return WSMG_EINVAL;
   if (((uintptr_t)partials & 7) || ((uintptr_t)guard & 3) || ((uintptr_t)step_dev & 3)) return WSMG_EINVAL;
-  long long total = 0;
-  for (int i = 0; i < n; ++i) {
-    if (descs[i].n < 0 || (descs[i].n > 0 && !descs[i].grad)) return WSMG_EINVAL;
-    total += (descs[i].n + ADAM_CHUNK - 1) / ADAM_CHUNK;
-    if (total > (1ll << 30)) return WSMG_EINVAL;
-  }
+  const long long total = check_descs(descs, n, DESC_GRAD, DESC_MAX_N);
+  if (total < 0) return WSMG_EINVAL;
   if (total > partials_cap) return WSMG_ENOMEM;
   const int base = grad_sumsq_launches(descs, n, partials, s);
   if (hyper_guard_row)
@@ -552,43 +555,27 @@ extern "C" int wsmg_grad_norm_multi_hyper(const WsmgAdamDesc* descs, int n, doub
   return grad_norm_launch(descs, n, partials, partials_cap, 0.f, hyper_guard_row, skip_nonfinite, guard, step_dev, s);
 }
 
-// The report's argument checks (every descriptor, and the chunk total against both capacities, before the first launch): 0, WSMG_EINVAL or WSMG_ENOMEM.
+// The report's argument checks (the chunk total against both capacities): 0, WSMG_EINVAL or WSMG_ENOMEM.
 static int grad_report_check(const WsmgAdamDesc* descs, int n, const double* partials, long long partials_cap, const uint32_t* scan,
                              long long scan_cap, const uint32_t* report) {
-  if (n < 0 || (n > 0 && !descs) || !partials || partials_cap < 0 || !scan || scan_cap < 0 || !report) return WSMG_EINVAL;
+  if (!partials || partials_cap < 0 || !scan || scan_cap < 0 || !report) return WSMG_EINVAL;
   if (((uintptr_t)partials & 7) || ((uintptr_t)scan & 3) || ((uintptr_t)report & 3)) return WSMG_EINVAL;
-  long long total = 0;
-  for (int i = 0; i < n; ++i) {
-    const WsmgAdamDesc& d = descs[i];
-    if (d.n < 0 || d.n >= (1ll << 32) || (d.n > 0 && (!d.grad || ((uintptr_t)d.grad & 3)))) return WSMG_EINVAL;   // 32-bit counters
-    total += (d.n + ADAM_CHUNK - 1) / ADAM_CHUNK;
-    if (total > (1ll << 30)) return WSMG_EINVAL;
-  }
+  const long long total = check_descs(descs, n, DESC_GRAD | DESC_ALIGN4, (1ll << 32) - 1);   // 32-bit counters
+  if (total < 0) return WSMG_EINVAL;
   return (total > partials_cap || total > scan_cap) ? WSMG_ENOMEM : 0;
 }
 
 // The scan launches (grad_sumsq_launches' batches, so a chunk has one index in partials and scan), the fold launches over every
-// descriptor, and the latch's launch if there is one.  Arguments are checked.
+// descriptor (batched by tensor, the empty ones included: every tensor has a row), and the latch's launch if there is one.
+// Arguments are checked.
 static void grad_report_launches(const WsmgAdamDesc* descs, int n, const double* partials, uint32_t* scan, const float* guard,
                                  const float* step_dev, uint32_t* report, uint32_t* latch, wsmg_stream_t s) {
-  int base = 0;
-  for (int i = 0; i < n;) {
-    ScanBatch b;
-    b.count = 0;
-    int blocks = 0;
-    for (; i < n && b.count < ADAM_MAX; ++i) {
-      if (descs[i].n == 0) continue;
-      const int k = b.count++;
-      b.g[k] = descs[i].grad; b.n[k] = descs[i].n;
-      b.first_block[k] = blocks;
-      blocks += (int)((descs[i].n + ADAM_CHUNK - 1) / ADAM_CHUNK);
-    }
-    if (!b.count) continue;
-    b.first_block[b.count] = blocks;
-    b.scan = scan + 4 * (long long)base;
-    hipLaunchKernelGGL(grad_scan_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, wsmg_s(s), b);
-    base += blocks;
-  }
+  ScanBatch sb;
+  for_each_batch(descs, n, sb.tab, [&](int k, const WsmgAdamDesc& d) { sb.g[k] = d.grad; },
+                 [&](int blocks, int base) {
+                   sb.scan = scan + 4 * (long long)base;
+                   hipLaunchKernelGGL(grad_scan_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, wsmg_s(s), sb);
+                 });
   int first = 0;
   for (int i = 0; i < n;) {
     FoldBatch b;

@@ -80,32 +80,57 @@ def _stats_rows(table, names):
     return [GradStat(i, names[i], f[i][0], f[i][1], c[i][0] & 0xffffffff, c[i][1] & 0xffffffff) for i in range(len(f))]
 
 
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def _stream(dev):
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _adam_descs(items):
+    """The _AdamDesc array of [(p, g, exp_avg, exp_avg_sq)]."""
+    descs = (_AdamDesc * len(items))()
+    for d, (p, g, m, v) in zip(descs, items):
+        d.param, d.grad, d.exp_avg, d.exp_avg_sq, d.n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
+    return descs
+
+
+def _grad_descs(grads):
+    """Gradient-only descriptors, one per entry: None and gradients without elements get a zero-length one (no chunk, a zero row)."""
+    descs = (_AdamDesc * len(grads))()
+    for d, g in zip(descs, grads):
+        if g is not None and g.numel():
+            d.grad, d.n = g.data_ptr(), g.numel()
+    return descs
+
+
+def _checked_grad_descs(what, grads):
+    """Check a gradient list (None: no gradient) -> (device, descriptors, the contiguous gradients: copies live until the launches
+    are queued)."""
+    some = [g for g in grads if g is not None]
+    if not some:
+        raise _abi.WsmgError(f"wsmgmap.optim.{what}: no parameter has a gradient")
+    dev = some[0].device
+    for g in some:
+        if g.is_sparse or not (g.is_cuda and g.dtype == torch.float32 and g.device == dev):
+            raise _abi.WsmgError(f"wsmgmap.optim.{what}: gradients must be dense float32 CUDA tensors on one device")
+    grads = [g if g is None or g.is_contiguous() else g.contiguous() for g in grads]
+    return dev, _grad_descs(grads), grads
+
+
 def grad_stats(params):
     """Per-tensor gradient statistics, one row per parameter in the order given: an [n, 4] int32 device table whose words are
     {float32 L2 norm, float32 max |g| over the finite elements, NaN count, Inf count} (`stats_as_float` views the first two).  A
     parameter without a gradient, or with no elements, has an all-zero row.  Deterministic (float64 sums in a fixed order: two calls
     return the same bits), a few launches per 48 tensors, no host synchronisation.  Dense float32 CUDA gradients on one device only."""
-    params = list(params)
-    grads = [p.grad for p in params]
-    some = [g for g in grads if g is not None]
-    if not some:
-        raise _abi.WsmgError("wsmgmap.optim.grad_stats: no parameter has a gradient")
-    dev = some[0].device
-    for g in some:
-        if g.is_sparse or not (g.is_cuda and g.dtype == torch.float32 and g.device == dev):
-            raise _abi.WsmgError("wsmgmap.optim.grad_stats: gradients must be dense float32 CUDA tensors on one device")
-    grads = [g if g is None or g.is_contiguous() else g.contiguous() for g in grads]     # (copies live until the launches are queued)
-    descs = (_AdamDesc * len(grads))()
-    for d, g in zip(descs, grads):
-        if g is not None and g.numel():
-            d.grad, d.n = g.data_ptr(), g.numel()
+    dev, descs, grads = _checked_grad_descs("grad_stats", [p.grad for p in params])
     with torch.cuda.device(dev):
         cap = max(1, _norm_blocks(descs))
         partials = torch.empty(cap, device=dev, dtype=torch.float64)
         scan = torch.empty(4 * cap, device=dev, dtype=torch.int32)
         report = torch.empty(len(grads), 4, device=dev, dtype=torch.int32)
-        _abi.call("wsmg_grad_stats_multi", descs, len(grads), ctypes.c_void_p(partials.data_ptr()), cap, ctypes.c_void_p(scan.data_ptr()),
-                  cap, ctypes.c_void_p(report.data_ptr()), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        _abi.call("wsmg_grad_stats_multi", descs, len(grads), _ptr(partials), cap, _ptr(scan), cap, _ptr(report), _stream(dev))
     return report
 
 
@@ -113,23 +138,12 @@ def global_grad_norm(params):
     """L2 norm over the `.grad` of every parameter that has one (as `clip_grad_norm_` over them computes it, but accumulated in
     float64 in a fixed order: two calls return the same bits): a 0-dim float32 tensor on the gradients' device.  A few launches per
     48 tensors and no host synchronisation; nothing is scaled.  Dense float32 CUDA gradients on one device only."""
-    grads = [p.grad for p in params if p.grad is not None]
-    if not grads:
-        raise _abi.WsmgError("wsmgmap.optim.global_grad_norm: no parameter has a gradient")
-    dev = grads[0].device
-    for g in grads:
-        if g.is_sparse or not (g.is_cuda and g.dtype == torch.float32 and g.device == dev):
-            raise _abi.WsmgError("wsmgmap.optim.global_grad_norm: gradients must be dense float32 CUDA tensors on one device")
-    grads = [g if g.is_contiguous() else g.contiguous() for g in grads]      # (copies live until the launches are queued)
-    descs = (_AdamDesc * len(grads))()
-    for d, g in zip(descs, grads):
-        d.grad, d.n = g.data_ptr(), g.numel()
+    dev, descs, grads = _checked_grad_descs("global_grad_norm", [p.grad for p in params if p.grad is not None])
     with torch.cuda.device(dev):
         guard = torch.zeros(4, device=dev, dtype=torch.float32)
         cap = max(1, _norm_blocks(descs))
         partials = torch.empty(cap, device=dev, dtype=torch.float64)
-        _abi.call("wsmg_grad_norm_multi", descs, len(grads), ctypes.c_void_p(partials.data_ptr()), cap, 0.0, 0,
-                  ctypes.c_void_p(guard.data_ptr()), None, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        _abi.call("wsmg_grad_norm_multi", descs, len(grads), _ptr(partials), cap, 0.0, 0, _ptr(guard), None, _stream(dev))
     return guard[0]
 
 
@@ -221,11 +235,14 @@ class Adam(torch.optim.Optimizer):
             self._hyper_fixed = True
         self._report_fixed = self._grad_report
 
+    def _flat_params(self):
+        return [p for group in self.param_groups for p in group["params"]]
+
     def _reset_guard(self):
         """(Re-)create the guard's device tensors from the host-side step counts: at construction and after load_state_dict, so
         that step() itself allocates and fills nothing — a fill captured into a HIP graph would reset the record at every replay."""
         self._guard = self._guard_step = self._partials = self._report = self._latch = self._scan = None
-        params = [p for group in self.param_groups for p in group["params"]]
+        params = self._flat_params()
         if not params or not all(p.is_cuda for p in params):
             return                 # step() refuses such parameters
         steps = {st["step"] for st in self.state.values() if "step" in st}
@@ -245,7 +262,7 @@ class Adam(torch.optim.Optimizer):
         """(Re-)create the hyper record, its staging tensor and the mirror from `param_groups` and `max_grad_norm`: at construction
         and after load_state_dict, where the guard's tensors are made — never in step()."""
         self._hyper = self._hyper_stage = self._hyper_mirror = self._hyper_event = None
-        params = [p for group in self.param_groups for p in group["params"]]
+        params = self._flat_params()
         if not params or not all(p.is_cuda for p in params):
             return                 # step() refuses such parameters
         dev = params[0].device
@@ -371,7 +388,7 @@ class Adam(torch.optim.Optimizer):
         what = "wsmgmap.optim.Adam(guard_buffers=...)"
         if not named:
             raise _abi.WsmgError(f"{what}: the module has no BatchNorm layer that tracks running statistics")
-        params = [p for group in self.param_groups for p in group["params"]]
+        params = self._flat_params()
         dev = params[0].device
         for name, b in named:
             if not (b.is_cuda and b.device == dev and b.is_contiguous()):
@@ -407,8 +424,7 @@ class Adam(torch.optim.Optimizer):
             self._build_snapshot(self._protected_buffers())
         dev = self._snap.device
         with torch.cuda.device(dev):
-            _abi.call("wsmg_copy_multi", ctypes.cast(self._snap_save, ctypes.c_void_p), len(self._snap_save),
-                      ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            _abi.call("wsmg_copy_multi", ctypes.cast(self._snap_save, ctypes.c_void_p), len(self._snap_save), _stream(dev))
         self._snap_fresh = True
 
     def zero_grad(self, set_to_none=True):
@@ -417,6 +433,56 @@ class Adam(torch.optim.Optimizer):
         super().zero_grad(set_to_none=set_to_none)
         if self._guard_buffers is not None:
             self.snapshot_buffers()
+
+    def _stepped_items(self, group, guarded=False, dev=None):
+        """The parameters of `group` that have a gradient, checked, their state created and their step count advanced ->
+        ([(p, g, exp_avg, exp_avg_sq)], [step count of each], dev).  guarded: they must all sit on `dev` (None: the first one's
+        device), and moments that do not exist yet are refused under stream capture."""
+        items, steps = [], []
+        for p in group["params"]:
+            g = p.grad
+            if g is None:
+                continue
+            if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
+                raise _abi.WsmgError("wsmgmap.optim.Adam: parameters must be contiguous float32 CUDA tensors")
+            if g.is_sparse or g.dtype != torch.float32 or g.device != p.device:
+                raise _abi.WsmgError("wsmgmap.optim.Adam: gradients must be dense float32 tensors on the parameter's device")
+            if guarded:
+                if dev is None:
+                    dev = p.device
+                if p.device != dev:
+                    raise _abi.WsmgError("wsmgmap.optim.Adam: the guarded step takes one norm over all parameters: they must share a device")
+            if not g.is_contiguous():
+                g = g.contiguous()
+                g.record_stream(torch.cuda.current_stream(p.device))   # the copy must outlive the launch queued below
+            st = self.state[p]
+            if not st:
+                if guarded and torch.cuda.is_current_stream_capturing():      # the zero fills would be replayed: moments reset every time
+                    raise _abi.WsmgError("wsmgmap.optim.Adam: the moments do not exist yet; take a step (or load_state_dict) "
+                                         "before capturing step() into a graph")
+                st["step"] = 0    # a Python int while training (102 CPU-tensor increments per step cost 1 ms of host time);
+                #                   state_dict() / load_state_dict() convert from / to torch.optim.Adam's float32 tensor
+                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            st["step"] += 1       # guarded: ATTEMPTED steps; the device count (attempted - skipped) is what the kernel uses
+            items.append((p, g, st["exp_avg"], st["exp_avg_sq"]))
+            steps.append(st["step"])
+        return items, steps, dev
+
+    def _launch_step(self, descs, n, gi, group, stream, step=None, sd=None, guard=None):
+        """The step's entry point for this optimizer: the record's row (hyper_on_device), else by value behind the guard record,
+        with the device step count `sd` (capturable), or with the host's bias corrections of `step`."""
+        if self._hyper_on_device:
+            _abi.call("wsmg_adam_step_multi_hyper", descs, n, self._hyper_row(gi), sd, guard, stream)
+            return
+        b1, b2 = group["betas"]
+        by_value = (float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]))
+        if guard is not None:
+            _abi.call("wsmg_adam_step_multi_guarded", descs, n, *by_value, sd, guard, stream)
+        elif sd is not None:
+            _abi.call("wsmg_adam_step_multi_dev", descs, n, *by_value, sd, stream)
+        else:
+            _abi.call("wsmg_adam_step_multi", descs, n, *by_value, 1.0 - b1 ** step, 1.0 - b2 ** step, stream)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -431,53 +497,24 @@ class Adam(torch.optim.Optimizer):
             return loss
         for gi, group in enumerate(self.param_groups):
             by_step = {}
-            for p in group["params"]:
-                g = p.grad
-                if g is None:
-                    continue
-                if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
-                    raise _abi.WsmgError("wsmgmap.optim.Adam: parameters must be contiguous float32 CUDA tensors")
-                if g.is_sparse or g.dtype != torch.float32 or g.device != p.device:
-                    raise _abi.WsmgError("wsmgmap.optim.Adam: gradients must be dense float32 tensors on the parameter's device")
-                if not g.is_contiguous():
-                    g = g.contiguous()
-                    g.record_stream(torch.cuda.current_stream(p.device))   # the copy must outlive the launch queued below
-                st = self.state[p]
-                if not st:
-                    st["step"] = 0    # a Python int while training (102 CPU-tensor increments per step cost 1 ms of host time);
-                    #                   state_dict() / load_state_dict() convert from / to torch.optim.Adam's float32 tensor
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                st["step"] += 1
-                by_step.setdefault(st["step"], []).append((p, g, st["exp_avg"], st["exp_avg_sq"]))
-            b1, b2 = group["betas"]
+            for item, step in zip(*self._stepped_items(group)[:2]):
+                by_step.setdefault(step, []).append(item)
             if self._capturable and len(by_step) > 1:
                 raise _abi.WsmgError("wsmgmap.optim.Adam(capturable=True): the stepped parameters of a group must share one step count")
             for step, items in by_step.items():
-                descs = (_AdamDesc * len(items))()
-                for d, (p, g, m, v) in zip(descs, items):
-                    d.param, d.grad, d.exp_avg, d.exp_avg_sq, d.n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
                 dev = items[0][0].device
-                stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
                 with torch.cuda.device(dev):
                     if self._hyper_on_device and self._hyper.device != dev:
                         raise _abi.WsmgError("wsmgmap.optim.Adam(hyper_on_device=True): the hyper record is not on the stepped "
                                              "parameters' device")
+                    sd = None
                     if self._capturable:
                         key = id(group)
                         if key not in self._step_dev:
                             self._step_dev[key] = torch.full((), float(step - 1), device=dev, dtype=torch.float32)
-                        sd = self._step_dev[key]
-                        sd.add_(1.0)      # on the device: a replayed graph advances it without the host
-                        if self._hyper_on_device:
-                            _abi.call("wsmg_adam_step_multi_hyper", descs, len(items), self._hyper_row(gi),
-                                      ctypes.c_void_p(sd.data_ptr()), None, stream)
-                        else:
-                            _abi.call("wsmg_adam_step_multi_dev", descs, len(items), float(group["lr"]), float(b1), float(b2),
-                                      float(group["eps"]), float(group["weight_decay"]), ctypes.c_void_p(sd.data_ptr()), stream)
-                    else:
-                        _abi.call("wsmg_adam_step_multi", descs, len(items), float(group["lr"]), float(b1), float(b2), float(group["eps"]),
-                                  float(group["weight_decay"]), 1.0 - b1 ** step, 1.0 - b2 ** step, stream)
+                        self._step_dev[key].add_(1.0)      # on the device: a replayed graph advances it without the host
+                        sd = _ptr(self._step_dev[key])
+                    self._launch_step(_adam_descs(items), len(items), gi, group, _stream(dev), step=step, sd=sd)
                 # the kernel wrote the parameters through raw pointers: advance their autograd version counters, which is what
                 # caches of derived operands (FoldCache, InstructionEncoder.packed_rnn_weights) compare
                 torch.autograd.graph.increment_version([it[0] for it in items])
@@ -490,33 +527,8 @@ class Adam(torch.optim.Optimizer):
                                  "statistics back by more than one update)")
         groups, steps, dev = [], set(), None
         for gi, group in enumerate(self.param_groups):
-            items = []
-            for p in group["params"]:
-                g = p.grad
-                if g is None:
-                    continue
-                if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
-                    raise _abi.WsmgError("wsmgmap.optim.Adam: parameters must be contiguous float32 CUDA tensors")
-                if g.is_sparse or g.dtype != torch.float32 or g.device != p.device:
-                    raise _abi.WsmgError("wsmgmap.optim.Adam: gradients must be dense float32 tensors on the parameter's device")
-                if dev is None:
-                    dev = p.device
-                if p.device != dev:
-                    raise _abi.WsmgError("wsmgmap.optim.Adam: the guarded step takes one norm over all parameters: they must share a device")
-                if not g.is_contiguous():
-                    g = g.contiguous()
-                    g.record_stream(torch.cuda.current_stream(p.device))
-                st = self.state[p]
-                if not st:
-                    if torch.cuda.is_current_stream_capturing():      # the zero fills would be replayed: moments reset every time
-                        raise _abi.WsmgError("wsmgmap.optim.Adam: the moments do not exist yet; take a step (or load_state_dict) "
-                                             "before capturing step() into a graph")
-                    st["step"] = 0
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                st["step"] += 1     # ATTEMPTED steps; the device count (attempted - skipped) is what the kernel uses
-                steps.add(st["step"])
-                items.append((p, g, st["exp_avg"], st["exp_avg_sq"]))
+            items, counts, dev = self._stepped_items(group, guarded=True, dev=dev)
+            steps.update(counts)
             if items:
                 groups.append((gi, group, items))
         if not groups:
@@ -528,11 +540,9 @@ class Adam(torch.optim.Optimizer):
         rows = None
         if self._grad_report:      # the gradient behind every report row (the stepped list's, in its order), None where there is none
             stepped = iter(every)
-            rows = [None if p.grad is None else next(stepped)[1] for group in self.param_groups for p in group["params"]]
-        descs = (_AdamDesc * len(every))()
-        for d, (p, g, m, v) in zip(descs, every):
-            d.param, d.grad, d.exp_avg, d.exp_avg_sq, d.n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            rows = [None if p.grad is None else next(stepped)[1] for p in self._flat_params()]
+        descs = _adam_descs(every)
+        stream = _stream(dev)
         with torch.cuda.device(dev):
             if self._guard is None or self._guard.device != dev or self._partials.numel() < _norm_blocks(descs):
                 raise _abi.WsmgError("wsmgmap.optim.Adam: the guard's device state does not fit the stepped parameters (construct the "
@@ -543,33 +553,19 @@ class Adam(torch.optim.Optimizer):
                 raise _abi.WsmgError("wsmgmap.optim.Adam(hyper_on_device=True): the hyper record is not on the stepped parameters' device")
             if rows is not None and (self._report is None or self._report.shape[0] != len(rows)):
                 raise _abi.WsmgError("wsmgmap.optim.Adam(grad_report=True): the report's tables do not fit the parameters")
-            guard, sd = ctypes.c_void_p(self._guard.data_ptr()), ctypes.c_void_p(self._guard_step.data_ptr())
+            guard, sd, partials = _ptr(self._guard), _ptr(self._guard_step), _ptr(self._partials)
             # the finalize advances the step count by 1 - skip: a skipped step does not advance the bias corrections
-            if self._hyper_on_device:
-                _abi.call("wsmg_grad_norm_multi_hyper", descs, len(every), ctypes.c_void_p(self._partials.data_ptr()),
-                          self._partials.numel(), self._hyper_row(len(self.param_groups)), int(self._skip_nonfinite), guard, sd, stream)
-            else:
-                _abi.call("wsmg_grad_norm_multi", descs, len(every), ctypes.c_void_p(self._partials.data_ptr()), self._partials.numel(),
-                          self._max_grad_norm or 0.0, int(self._skip_nonfinite), guard, sd, stream)
+            norm, max_norm = (("wsmg_grad_norm_multi_hyper", self._hyper_row(len(self.param_groups))) if self._hyper_on_device
+                              else ("wsmg_grad_norm_multi", self._max_grad_norm or 0.0))
+            _abi.call(norm, descs, len(every), partials, self._partials.numel(), max_norm, int(self._skip_nonfinite), guard, sd, stream)
             if rows is not None:
                 # descriptors of their own over ALL parameters: the stepped list with a zero-length one for every parameter without a
                 # gradient — those own no chunk, so the norm's partials line up, and no row ever shifts
-                rdescs = (_AdamDesc * len(rows))()
-                for d, g in zip(rdescs, rows):
-                    if g is not None and g.numel():
-                        d.grad, d.n = g.data_ptr(), g.numel()
-                _abi.call("wsmg_grad_report_multi", rdescs, len(rows), ctypes.c_void_p(self._partials.data_ptr()),
-                          self._partials.numel(), ctypes.c_void_p(self._scan.data_ptr()), self._scan.numel() // 4, guard, sd,
-                          ctypes.c_void_p(self._report.data_ptr()), ctypes.c_void_p(self._latch.data_ptr()), stream)
+                _abi.call("wsmg_grad_report_multi", _grad_descs(rows), len(rows), partials, self._partials.numel(), _ptr(self._scan),
+                          self._scan.numel() // 4, guard, sd, _ptr(self._report), _ptr(self._latch), stream)
             at = 0
             for gi, group, items in groups:
-                b1, b2 = group["betas"]
-                at_descs = ctypes.byref(descs, at * ctypes.sizeof(_AdamDesc))
-                if self._hyper_on_device:
-                    _abi.call("wsmg_adam_step_multi_hyper", at_descs, len(items), self._hyper_row(gi), sd, guard, stream)
-                else:
-                    _abi.call("wsmg_adam_step_multi_guarded", at_descs, len(items),
-                              float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), sd, guard, stream)
+                self._launch_step(ctypes.byref(descs, at * ctypes.sizeof(_AdamDesc)), len(items), gi, group, stream, sd=sd, guard=guard)
                 at += len(items)
             written = [it[0] for it in every]
             if self._guard_buffers is not None:
@@ -598,7 +594,7 @@ class Adam(torch.optim.Optimizer):
             return default
         if isinstance(names, torch.nn.Module):
             by_id = {id(p): name for name, p in names.named_parameters()}
-            params = [p for group in self.param_groups for p in group["params"]]
+            params = self._flat_params()
             return [by_id.get(id(p), d) for p, d in zip(params, default)]
         names = [str(x) for x in names]
         if len(names) != len(default):
