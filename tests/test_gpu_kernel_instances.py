@@ -210,6 +210,36 @@ def test_conv_fwd_ex_channel_slice_on_the_implicit_gemm_route(ops):
     assert bool((base[..., :c_off] == 7.0).all()) and bool((base[..., c_off + Cout:] == 7.0).all())
 
 
+def test_stem_window_conv_statistics_match_the_implicit_gemm_route():
+    """The k8 s2 p3 64 -> 64 stem through wsmg_conv2d_fwd_bf16_stats: conv_win_fwd_kernel flushes its BatchNorm sums once per workgroup run
+    (the half-wave exchange on float64), the one statistics path no test held against a second route.  52 x 52 -> 26 x 26 with 5 x 25 tiles: a
+    partial tile column (1 of 25) and a partial tile row (1 of 5), B = 3, 8 slabs.  The second route is the implicit-GEMM kernel, which
+    wsmg_conv2d_fwd_bf16_ex takes in this process when the output is a channel slice (y_ld != Cout).  Outputs bit for bit; both routes'
+    sums against float64 sums of the returned bf16 output to 1e-6 relative (the bar of tests/test_gpu_round6.py for this quantity)."""
+    from wsmgmap import _abi, ops
+    B, H, C, OH, nslab = 3, 52, 64, 26, 8
+    x = nhwc(T(df.uniform("inst.stem.x", (B, C, H, H), 2.0)).to(torch.bfloat16)).cuda()
+    w = T(df.uniform("inst.stem.w", (C, 8, 8, C), float(np.sqrt(12.0 / (C * 64))))).to(torch.bfloat16).cuda()      # OHWI
+    bias = T(df.uniform("inst.stem.b", (C,), 0.5)).cuda()
+    args = (B, H, H, C, C, 8, 8, 2, 3, OH, OH)
+    P, st = ops._p, ops._stream
+    y_win = torch.empty(B, OH, OH, C, device="cuda", dtype=torch.bfloat16)
+    wide = torch.full((B, OH, OH, C + 64), 7.0, device="cuda", dtype=torch.bfloat16)
+    s_win = torch.zeros(nslab, 2, C, device="cuda", dtype=torch.float64)
+    s_ig = torch.zeros_like(s_win)
+    _abi.call("wsmg_conv2d_fwd_bf16_stats", P(x), P(w), P(bias), P(y_win), 2, P(s_win), nslab, *args, st())
+    _abi.call("wsmg_conv2d_fwd_bf16_ex", P(x), P(w), P(bias), wide.data_ptr() + 32 * 2, 2, P(s_ig), nslab, C + 64, *args, st())
+    torch.cuda.synchronize()
+    assert torch.equal(y_win, wide[..., 32:32 + C])
+    assert bool((wide[..., :32] == 7).all()) and bool((wide[..., 32 + C:] == 7).all())
+    assert float(y_win.float().abs().max()) > 0.5                    # (a real output, not the ReLU's zeros)
+    want = torch.stack([y_win.double().sum((0, 1, 2)), (y_win.double() ** 2).sum((0, 1, 2))])
+    for name, got in (("window", s_win.sum(0)), ("implicit-GEMM", s_ig.sum(0))):
+        rel = float((got - want).abs().max() / want.abs().max())
+        print(f"stem statistics, {name} route: max rel err {rel:.3e}")
+        assert rel < 1e-6, (name, rel)
+
+
 def _bwd_data_ex_case(name, B, Cin, Cout, k, s, p, H, W, ca):
     """wsmg_conv2d_bwd_data_bf16_ex with relu_y (the gradient is masked with the consumed tensor's ReLU) and dx2 / split_c (it is stored
     as two contiguous channel parts) against the masked float64 input gradient of the same bf16 operands; bar of the bf16 engine."""
@@ -238,7 +268,7 @@ def test_conv_bwd_data_ex_mask_and_split_on_the_implicit_gemm_route():
 
 
 # (name, forced tile (1 = by shape), B, H = W, Cin = produced channels N, Cout = reduction channels Kc).  The window kernel takes a tile
-# of mt pixels when window_bound(mt, H, W) <= 128 NPW entries (csrc/wsmg_conv_win3.hip), and at least 256 * 256 pixels:
+# of mt pixels when window_bound(mt, H, W) <= 128 NPW entries (wsmg_win3_window_bound, csrc/wsmg_conv_tile.h), and at least 256 * 256 pixels:
 #   48 x 48: window_bound(512) = 737 <= 768, window_bound(256) = 471 <= 512: both tiles fit; B = 29: 66 816 pixels.
 #   mixed512_n64: 48 x 48, B = 58: 133 632 pixels, by shape 261 tiles of 512 = one whole round over 256 CUs + 5 -> the remainder runs
 #     as 256-pixel tiles (window_bound(256) = 471 <= 512): conv_win3_mixed_kernel<512, 6, 4, 64, 1>.

@@ -19,12 +19,10 @@
 // exactly e4m3 numbers the result equals the reference's float32 `_attn` up to summation order — golden g5f.
 #include <stdio.h>
 
-#include "wsmg_common.h"
+#include "wsmg_conv_tile.h"
 
 namespace {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4v __attribute__((ext_vector_type(4)));
 constexpr int AC = 256;          // channels
 constexpr int LMAX = 224;        // tokens per set at most (a multiple of 32; the reference pads instructions to 200)
 
@@ -47,11 +45,6 @@ struct F8mArgs {
 __device__ __forceinline__ float e4m3_to_f32(uint8_t c) {
   return __builtin_amdgcn_cvt_f32_fp8((int)c, 0);
 }
-__device__ __forceinline__ unsigned short f2bf(float f) {
-  bf16_t b = (bf16_t)f;
-  return __builtin_bit_cast(unsigned short, b);
-}
-__device__ __forceinline__ float bf2f(unsigned short u) { return __uint_as_float((unsigned)u << 16); }
 
 __global__ __launch_bounds__(256) void attn_fp8_mfma_fwd_kernel(F8mArgs a) {
   __shared__ __attribute__((aligned(16))) float S[32][LMAX + 4];
@@ -154,9 +147,9 @@ __global__ __launch_bounds__(256) void attn_fp8_mfma_fwd_kernel(F8mArgs a) {
       const int idx = tid + 256 * half;            // 512 pieces of 16 bytes
       const int tk = idx >> 4, piece = idx & 15;
       const int l = 32 * c + tk;
-      u32x4v val = {0u, 0u, 0u, 0u};
-      if (l < a.L) val = *reinterpret_cast<const u32x4v*>(a.v + ((size_t)u * a.L + l) * AC + 16 * piece);
-      *reinterpret_cast<u32x4v*>(&V8[buf][tk][16 * piece]) = val;
+      u32x4 val = {0u, 0u, 0u, 0u};
+      if (l < a.L) val = *reinterpret_cast<const u32x4*>(a.v + ((size_t)u * a.L + l) * AC + 16 * piece);
+      *reinterpret_cast<u32x4*>(&V8[buf][tk][16 * piece]) = val;
     }
   };
   stage(0, 0);
@@ -170,16 +163,16 @@ __global__ __launch_bounds__(256) void attn_fp8_mfma_fwd_kernel(F8mArgs a) {
 #pragma unroll
       for (int s = 0; s < 8; ++s) {
         const float p = S[r][16 * ks + 8 * h + s];
-        const unsigned short hi = f2bf(p);
+        const unsigned short hi = f2bf_bits(p);
         phi[s] = (short)hi;
-        plo[s] = (short)f2bf(p - bf2f(hi));
+        plo[s] = (short)f2bf_bits(p - bf2f(hi));
       }
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         const int ch = 64 * wave + 32 * t + r;
         bf16x8 vb;
 #pragma unroll
-        for (int s = 0; s < 8; ++s) vb[s] = (short)f2bf(e4m3_to_f32(V8[c & 1][16 * kk + 8 * h + s][ch]));   // exact: e4m3 has 4 significant bits
+        for (int s = 0; s < 8; ++s) vb[s] = (short)f2bf_bits(e4m3_to_f32(V8[c & 1][16 * kk + 8 * h + s][ch]));   // exact: e4m3 has 4 significant bits
         o[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(phi, vb, o[t], 0, 0, 0);
         o[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(plo, vb, o[t], 0, 0, 0);
       }
@@ -530,13 +523,13 @@ __global__ __launch_bounds__(256) void attn_fp8_mfma_fused_kernel(F8fArgs a) {
         const int idx = tid + 256 * half;
         const int tk = idx >> 4, piece = idx & 15;
         const int l = 32 * c + tk;
-        u32x4v val = {0u, 0u, 0u, 0u};
+        u32x4 val = {0u, 0u, 0u, 0u};
         if (l < a.L) {
           const long lo = quant8r(vraw[c][half][0], vraw[c][half][1], iv), hi = quant8r(vraw[c][half][2], vraw[c][half][3], iv);
           val[0] = (unsigned)(lo & 0xffffffffl); val[1] = (unsigned)((unsigned long)lo >> 32);
           val[2] = (unsigned)(hi & 0xffffffffl); val[3] = (unsigned)((unsigned long)hi >> 32);
         }
-        *reinterpret_cast<u32x4v*>(&V8[c][tk][16 * piece]) = val;
+        *reinterpret_cast<u32x4*>(&V8[c][tk][16 * piece]) = val;
       }
     }
   }
@@ -612,16 +605,16 @@ __global__ __launch_bounds__(256) void attn_fp8_mfma_fused_kernel(F8fArgs a) {
 #pragma unroll
       for (int s_ = 0; s_ < 8; ++s_) {
         const float p = S[r][16 * ks + 8 * h + s_];
-        const unsigned short hi = f2bf(p);
+        const unsigned short hi = f2bf_bits(p);
         phi[s_] = (short)hi;
-        plo[s_] = (short)f2bf(p - bf2f(hi));
+        plo[s_] = (short)f2bf_bits(p - bf2f(hi));
       }
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         const int ch = 64 * wave + 32 * t + r;
         bf16x8 vb;
 #pragma unroll
-        for (int s_ = 0; s_ < 8; ++s_) vb[s_] = (short)f2bf(e4m3_to_f32(V8[c][16 * kk + 8 * h + s_][ch]));
+        for (int s_ = 0; s_ < 8; ++s_) vb[s_] = (short)f2bf_bits(e4m3_to_f32(V8[c][16 * kk + 8 * h + s_][ch]));
         o[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(phi, vb, o[t], 0, 0, 0);
         o[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(plo, vb, o[t], 0, 0, 0);
       }
@@ -678,19 +671,8 @@ extern "C" int wsmg_attn_fp8_mfma_fwd(const uint8_t* q_codes, const float* q_sca
 }
 
 // co-residency budget of the fused launch's grid barrier, from the device's own CU count
-static int fused_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-      cus = prop.multiProcessorCount;
-  }
-  return cus;
-}
-static int fused_main_limit() { const int h = fused_cus() / 2; return h < 128 ? h : 128; }
-static int fused_total_limit() { const int t = fused_cus() - 32; return t < 224 ? (t > 1 ? t : 1) : 224; }
+static int fused_main_limit() { const int h = wsmg_cu_count() / 2; return h < 128 ? h : 128; }
+static int fused_total_limit() { const int t = wsmg_cu_count() - 32; return t < 224 ? (t > 1 ? t : 1) : 224; }
 
 extern "C" int wsmg_attn_fp8_mfma_fused(const float* q, const float* k_sets, const float* v_sets, const int64_t* inverse, const int* lengths,
                                         float q_scale, float k_scale, float v_scale, float scale, int B, int U, int L, int C,

@@ -18,12 +18,10 @@
 //                partial blocks.  A set no row uses gets zeros; tokens at or past lengths[u] have p = 0 exactly, hence dl = 0 and zero
 //                gradient rows; rows past the end of a partial chunk are staged as zeros.
 // No [B][L][256] or [U][B][L] tensor exists.
-#include "wsmg_common.h"
+#include "wsmg_conv_tile.h"
 
 namespace {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4v __attribute__((ext_vector_type(4)));
 constexpr int AC = 256;          // channels
 constexpr int LMAX = 224;        // tokens per set at most (the forward's limit)
 
@@ -48,34 +46,29 @@ struct F8bArgs {
   float* dl;               // [B][L] scratch: d logits
 };
 
-__device__ __forceinline__ unsigned short f2bf(float f) {
-  bf16_t b = (bf16_t)f;
-  return __builtin_bit_cast(unsigned short, b);
-}
-__device__ __forceinline__ float bf2f(unsigned short u) { return __uint_as_float((unsigned)u << 16); }
 __device__ __forceinline__ short e4m3_to_bf(uint8_t c) {      // exact: e4m3 has 4 significant bits
-  return (short)f2bf(__builtin_amdgcn_cvt_f32_fp8((int)c, 0));
+  return (short)f2bf_bits(__builtin_amdgcn_cvt_f32_fp8((int)c, 0));
 }
 __device__ __forceinline__ void split8(const float (&x)[8], bf16x8& hi, bf16x8& lo) {
 #pragma unroll
   for (int s = 0; s < 8; ++s) {
-    const unsigned short h = f2bf(x[s]);
+    const unsigned short h = f2bf_bits(x[s]);
     hi[s] = (short)h;
-    lo[s] = (short)f2bf(x[s] - bf2f(h));
+    lo[s] = (short)f2bf_bits(x[s] - bf2f(h));
   }
 }
 // 8 consecutive e4m3 bytes -> 8 bf16 numbers
 __device__ __forceinline__ bf16x8 codes8_to_bf(long w) {
   const int w0 = (int)(w & 0xffffffffl), w1 = (int)((unsigned long)w >> 32);
   bf16x8 o;
-  o[0] = (short)f2bf(__builtin_amdgcn_cvt_f32_fp8(w0, 0));
-  o[1] = (short)f2bf(__builtin_amdgcn_cvt_f32_fp8(w0, 1));
-  o[2] = (short)f2bf(__builtin_amdgcn_cvt_f32_fp8(w0, 2));
-  o[3] = (short)f2bf(__builtin_amdgcn_cvt_f32_fp8(w0, 3));
-  o[4] = (short)f2bf(__builtin_amdgcn_cvt_f32_fp8(w1, 0));
-  o[5] = (short)f2bf(__builtin_amdgcn_cvt_f32_fp8(w1, 1));
-  o[6] = (short)f2bf(__builtin_amdgcn_cvt_f32_fp8(w1, 2));
-  o[7] = (short)f2bf(__builtin_amdgcn_cvt_f32_fp8(w1, 3));
+  o[0] = (short)f2bf_bits(__builtin_amdgcn_cvt_f32_fp8(w0, 0));
+  o[1] = (short)f2bf_bits(__builtin_amdgcn_cvt_f32_fp8(w0, 1));
+  o[2] = (short)f2bf_bits(__builtin_amdgcn_cvt_f32_fp8(w0, 2));
+  o[3] = (short)f2bf_bits(__builtin_amdgcn_cvt_f32_fp8(w0, 3));
+  o[4] = (short)f2bf_bits(__builtin_amdgcn_cvt_f32_fp8(w1, 0));
+  o[5] = (short)f2bf_bits(__builtin_amdgcn_cvt_f32_fp8(w1, 1));
+  o[6] = (short)f2bf_bits(__builtin_amdgcn_cvt_f32_fp8(w1, 2));
+  o[7] = (short)f2bf_bits(__builtin_amdgcn_cvt_f32_fp8(w1, 3));
   return o;
 }
 
@@ -179,9 +172,9 @@ __global__ __launch_bounds__(256) void attn_fp8_mfma_bwd_rows_kernel(F8bArgs a) 
       const int idx = tid + 256 * half;            // 512 pieces of 16 bytes
       const int tk = idx >> 4, piece = idx & 15;
       const int l = 32 * c + tk;
-      u32x4v val = {0u, 0u, 0u, 0u};
-      if (l < a.L) val = *reinterpret_cast<const u32x4v*>(a.k + ((size_t)u * a.L + l) * AC + 16 * piece);
-      *reinterpret_cast<u32x4v*>(&K8[buf][tk][16 * piece]) = val;
+      u32x4 val = {0u, 0u, 0u, 0u};
+      if (l < a.L) val = *reinterpret_cast<const u32x4*>(a.k + ((size_t)u * a.L + l) * AC + 16 * piece);
+      *reinterpret_cast<u32x4*>(&K8[buf][tk][16 * piece]) = val;
     }
   };
   stage(0, 0);
@@ -254,9 +247,9 @@ __global__ __launch_bounds__(256) void attn_fp8_mfma_bwd_sets_kernel(F8bArgs a) 
     for (int half = 0; half < 2; ++half) {       // query codes: 512 pieces of 16 bytes
       const int idx = tid + 256 * half;
       const int i = idx >> 4, piece = idx & 15;
-      u32x4v val = {0u, 0u, 0u, 0u};
-      if (i < n) val = *reinterpret_cast<const u32x4v*>(a.q + (size_t)pend[(head + i) & (PEND - 1)] * AC + 16 * piece);
-      *reinterpret_cast<u32x4v*>(&Q8[i][16 * piece]) = val;
+      u32x4 val = {0u, 0u, 0u, 0u};
+      if (i < n) val = *reinterpret_cast<const u32x4*>(a.q + (size_t)pend[(head + i) & (PEND - 1)] * AC + 16 * piece);
+      *reinterpret_cast<u32x4*>(&Q8[i][16 * piece]) = val;
     }
 #pragma unroll
     for (int it = 0; it < 8; ++it) {             // dout: 2048 pieces of 4 floats

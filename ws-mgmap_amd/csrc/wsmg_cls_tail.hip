@@ -23,12 +23,10 @@
 // Tensors leave as 16-byte stores after a per-wave LDS transpose (80-byte pitch: conflict-free ds_read_b128).
 // Sums over pixels are accumulated per lane, reduced over lanes, waves (in wave order) and samples (wsmg_cls_tail_finish_kernel,
 // in sample order, float64): bit-identical from run to run.
-#include "wsmg_common.h"
+#include "wsmg_conv_tile.h"
 
 namespace {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int CH = 32;          // channels of the activation = padded classes
@@ -36,11 +34,6 @@ constexpr int PITCH = 80;       // LDS tile pitch (bytes): 64 + 16
 constexpr int TILE = 32 * PITCH;
 constexpr int WAVES = 8;
 
-__device__ __forceinline__ unsigned short f2bf(float f) {
-  bf16_t b = (bf16_t)f;
-  return __builtin_bit_cast(unsigned short, b);
-}
-__device__ __forceinline__ float bf2f(unsigned short u) { return __uint_as_float((unsigned)u << 16); }
 __device__ __forceinline__ void unpack8(const u32x4 v, float (&o)[8]) {
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
@@ -51,7 +44,7 @@ __device__ __forceinline__ void unpack8(const u32x4 v, float (&o)[8]) {
 __device__ __forceinline__ bf16x8 pack8(const float (&v)[8]) {
   bf16x8 o;
 #pragma unroll
-  for (int j = 0; j < 8; ++j) o[j] = (short)f2bf(v[j]);
+  for (int j = 0; j < 8; ++j) o[j] = (short)f2bf_bits(v[j]);
   return o;
 }
 // class / channel index of accumulator register g in lane half h (C layout of the 32 x 32 MFMA: rows)
@@ -153,8 +146,8 @@ __device__ __forceinline__ void store_tile(unsigned char* lds, const float (&v)[
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     u32x2 w;
-    w[0] = (unsigned)f2bf(v[4 * j]) | ((unsigned)f2bf(v[4 * j + 1]) << 16);
-    w[1] = (unsigned)f2bf(v[4 * j + 2]) | ((unsigned)f2bf(v[4 * j + 3]) << 16);
+    w[0] = (unsigned)f2bf_bits(v[4 * j]) | ((unsigned)f2bf_bits(v[4 * j + 1]) << 16);
+    w[1] = (unsigned)f2bf_bits(v[4 * j + 2]) | ((unsigned)f2bf_bits(v[4 * j + 3]) << 16);
     *reinterpret_cast<u32x2*>(lds + r * PITCH + 16 * j + 8 * h) = w;
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -222,7 +215,7 @@ __global__ __launch_bounds__(512) void cls_tail_fwd_kernel(TailArgs a) {
     // the logits as the unfused path stores them (bf16), and their 2 x 2 average
     float vr[16];
 #pragma unroll
-    for (int g = 0; g < 16; ++g) vr[g] = bf2f(f2bf(v[g]));
+    for (int g = 0; g < 16; ++g) vr[g] = bf2f(f2bf_bits(v[g]));
     store_tile(lds, vr, r, h, lane, a.sem, q, b, a.H, a.W);
     {
       float ps[16];
@@ -237,8 +230,8 @@ __global__ __launch_bounds__(512) void cls_tail_fwd_kernel(TailArgs a) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           u32x2 w;
-          w[0] = (unsigned)f2bf(ps[4 * j]) | ((unsigned)f2bf(ps[4 * j + 1]) << 16);
-          w[1] = (unsigned)f2bf(ps[4 * j + 2]) | ((unsigned)f2bf(ps[4 * j + 3]) << 16);
+          w[0] = (unsigned)f2bf_bits(ps[4 * j]) | ((unsigned)f2bf_bits(ps[4 * j + 1]) << 16);
+          w[1] = (unsigned)f2bf_bits(ps[4 * j + 2]) | ((unsigned)f2bf_bits(ps[4 * j + 3]) << 16);
           *reinterpret_cast<u32x2*>(reinterpret_cast<unsigned char*>(a.pooled) + pp * (CH * 2) + 16 * j + 8 * h) = w;
         }
       }
@@ -363,7 +356,7 @@ __global__ __launch_bounds__(512) void cls_tail_bwd_kernel(TailArgs a) {
     // bf16, as the MFMA consumes it; the bias gradient sums the same rounded values
     unsigned short dlb[16];
 #pragma unroll
-    for (int g = 0; g < 16; ++g) { dlb[g] = f2bf(dl[g]); s_db[g] += bf2f(dlb[g]); }
+    for (int g = 0; g < 16; ++g) { dlb[g] = f2bf_bits(dl[g]); s_db[g] += bf2f(dlb[g]); }
     bf16x8 bl[2];
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
@@ -389,7 +382,7 @@ __global__ __launch_bounds__(512) void cls_tail_bwd_kernel(TailArgs a) {
           const float xh = (yv[i] - mu[i]) * is[i];
           const bool on = yv[i] * sc[i] + sh[i] > 0.f;      // the forward's own expression: the same mask
           const float d = on ? da[4 * j + i] : 0.f;
-          const float dr = bf2f(f2bf(d));          // what BatchNorm's apply pass will read back
+          const float dr = bf2f(f2bf_bits(d));          // what BatchNorm's apply pass will read back
           dbn[4 * j + i] = dr;
           s_dy[4 * j + i] += dr;
           s_dyx[4 * j + i] += dr * xh;

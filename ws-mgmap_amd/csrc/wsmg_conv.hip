@@ -14,7 +14,7 @@
 // ranges (grid.z) and combined with float atomics.
 #include <stdlib.h>
 
-#include "wsmg_common.h"
+#include "wsmg_conv_tile.h"
 
 namespace {
 
@@ -32,14 +32,6 @@ struct ConvArgs {
   int mtiles;         // pixel tiles per parity class (grid.x = mtiles * ntiles)
   int ntiles;
 };
-
-// XCD-aware, bijective remap of a 1-D block id: the dispatcher deals blocks round-robin over the
-// 8 XCDs, so give each XCD one contiguous run of logical tiles (tiles that share input windows /
-// the same A rows then share one L2).  Speed only — any placement is correct.
-__device__ __forceinline__ int xcd_swizzle(int bid, int nb) {
-  const int q = nb >> 3, r = nb & 7, x = bid & 7;
-  return x * q + (x < r ? x : r) + (bid >> 3);
-}
 
 // BWD=false: target pixel t reads source t*s - p + k.
 // BWD=true : source (t + p - k)/s where divisible.  For s == 2 the target pixels are split into
@@ -334,21 +326,12 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradArgs a) {
 // pipeline variant: DB = false everywhere (set from measurements); the DB = true instantiations no dispatcher could select are
 // not compiled
 
-int check_conv(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH, int OW) {
-  if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || KH <= 0 || KW <= 0) return WSMG_EINVAL;
-  if (Cin % 32 || Cout % 32) return WSMG_EINVAL;
-  if (stride != 1 && stride != 2) return WSMG_EINVAL;
-  if (OH != (H + 2 * pad - KH) / stride + 1 || OW != (W + 2 * pad - KW) / stride + 1) return WSMG_EINVAL;
-  if ((int64_t)B * H * W >= (1ll << 31) || (int64_t)B * OH * OW >= (1ll << 31)) return WSMG_EINVAL;
-  return 0;
-}
-
 }  // namespace
 
 extern "C" int wsmg_conv2d_fwd(const float* x, const float* w_ohwi, const float* bias, float* y, int B, int H,
                                int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH, int OW,
                                wsmg_stream_t stream) {
-  if (int e = check_conv(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
+  if (int e = wsmg_check_conv(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
   ConvArgs a{x, w_ohwi, bias, y, B, H, W, Cin, OH, OW, Cout, KH, KW, stride, pad, 0, 0};
   a.mtiles = (int)wsmg_cdiv((int64_t)B * OH * OW, BM);
   a.ntiles = (int)wsmg_cdiv(Cout, BN);
@@ -360,7 +343,7 @@ extern "C" int wsmg_conv2d_fwd(const float* x, const float* w_ohwi, const float*
 extern "C" int wsmg_conv2d_bwd_data(const float* dy, const float* w_ihwo, float* dx, int B, int H, int W, int Cin,
                                     int Cout, int KH, int KW, int stride, int pad, int OH, int OW,
                                     wsmg_stream_t stream) {
-  if (int e = check_conv(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
+  if (int e = wsmg_check_conv(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
   ConvArgs a{dy, w_ihwo, nullptr, dx, B, OH, OW, Cout, H, W, Cin, KH, KW, stride, pad, 0, 0};
   a.ntiles = (int)wsmg_cdiv(Cin, BN);
   int classes = 1;
@@ -407,7 +390,7 @@ int launch_wgrad_f32(const float* x, const float* dy, float* dw, long long slab,
 extern "C" int wsmg_conv2d_bwd_weight(const float* x, const float* dy, float* dw_ohwi, int B, int H, int W, int Cin,
                                       int Cout, int KH, int KW, int stride, int pad, int OH, int OW,
                                       wsmg_stream_t stream) {
-  if (int e = check_conv(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
+  if (int e = wsmg_check_conv(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
   return launch_wgrad_f32(x, dy, dw_ohwi, 0, B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW, wsmg_s(stream));
 }
 
@@ -415,7 +398,7 @@ extern "C" int wsmg_conv2d_bwd_weight(const float* x, const float* dy, float* dw
 extern "C" int wsmg_conv2d_bwd_weight_plan(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH, int OW,
                                            int* nsplit, long long* ws_floats) {
   if (!nsplit || !ws_floats) return WSMG_EINVAL;
-  if (int e = check_conv(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
+  if (int e = wsmg_check_conv(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
   int gx, gy, gz;
   int64_t chunk;
   wgrad_plan_f32(B, OH, OW, Cin, Cout, KH, KW, gx, gy, chunk, gz);
@@ -426,7 +409,7 @@ extern "C" int wsmg_conv2d_bwd_weight_plan(int B, int H, int W, int Cin, int Cou
 
 extern "C" int wsmg_conv2d_bwd_weight_slabs(const float* x, const float* dy, float* ws, int nsplit, long long ws_floats, int B, int H, int W,
                                             int Cin, int Cout, int KH, int KW, int stride, int pad, int OH, int OW, wsmg_stream_t stream) {
-  if (int e = check_conv(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
+  if (int e = wsmg_check_conv(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
   int gx, gy, gz;
   int64_t chunk;
   wgrad_plan_f32(B, OH, OW, Cin, Cout, KH, KW, gx, gy, chunk, gz);

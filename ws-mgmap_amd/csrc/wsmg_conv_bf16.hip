@@ -13,35 +13,12 @@
 //       lane) — no transposed copy is ever materialised.
 #include <stdlib.h>
 
-#include "wsmg_common.h"
+#include "wsmg_conv_tile.h"
 #include "wsmg_relu_mask.h"
 
 namespace {
 
-typedef __bf16 bf16_t;
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef short bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int BM = 128;
-
-__device__ __forceinline__ int xcd_swizzle(int bid, int nb) {
-  const int q = nb >> 3, r = nb & 7, x = bid & 7;
-  return x * q + (x < r ? x : r) + (bid >> 3);
-}
-
-__device__ __forceinline__ unsigned short f2bf_bits(float f) {
-  bf16_t b = (bf16_t)f;
-  return __builtin_bit_cast(unsigned short, b);
-}
-
-// raw buffer resource over a tensor: 32-bit byte offsets, out-of-range lanes read 0 (no branches)
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ u32x4 buf_load16(__amdgpu_buffer_rsrc_t r, int byte_off) {
-  return __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0);
-}
 
 struct ConvArgsB {
   const bf16_t* src;  // [B][SH][SW][Kc]
@@ -296,17 +273,12 @@ __global__ __launch_bounds__(256) void conv_igemm_bf16_kernel(ConvArgsB a) {
             const unsigned short o = f2bf_bits(v);
             *reinterpret_cast<unsigned short*>(smem + row * OP + col * 2) = o;
             if (a.stats) {   // (rows past the last pixel of the class are the only invalid ones: dpix[row] < 0 <=> m0 + row >= Mc)
-              const float vr = m0 + row < Mc ? __uint_as_float((unsigned)o << 16) : 0.f;
+              const float vr = m0 + row < Mc ? bf2f(o) : 0.f;
               sv += vr;
               qv = fmaf(vr, vr, qv);
             }
           }
-        if (a.stats) {
-          // Train-mode BatchNorm statistics of THIS output (map_encoder.py:10-12: every conv of the map stack feeds one):
-          // per-channel sum and sum of squares of the bf16-ROUNDED values, taken from the registers while the tile is
-          // staged (a second pass over the staged tile was 32-64 two-byte LDS reads per thread), added to one of `nslab`
-          // float64 slabs (slab = m-tile mod nslab: 72 adders per address instead of 4608) — the separate statistics pass
-          // over y (one full read of every conv output) disappears.
+        if (a.stats) {   // (the sums and their slabs: wsmg_conv_tile.h)
           sv += __shfl_xor(sv, 32, 64);
           qv += __shfl_xor(qv, 32, 64);
           if (h == 0 && n0 + col < a.N) {
@@ -414,10 +386,6 @@ struct WgradArgsB {
                  // wsmg_weight_grad_reduce_oihw adds the slabs in slab order, so dW is bit-reproducible (run.py:107-108 of the
                  // reference asks for deterministic kernels).  0: float atomics into a zeroed OHWI dW
 };
-
-__device__ __forceinline__ bf16x4 tr_read(const unsigned char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((bf16x4 __attribute__((address_space(3)))*)(p));
-}
 
 template <int TC, int TU, int PF, int UPT>
 __global__ __launch_bounds__(256) void conv_wgrad_bf16_kernel(WgradArgsB a) {
@@ -590,12 +558,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_kernel(WgradArgsB a) {
   }
 }
 
-int check_conv(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH, int OW) {
-  if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || KH <= 0 || KW <= 0) return WSMG_EINVAL;
-  if (Cin % 32 || Cout % 32) return WSMG_EINVAL;
-  if (stride != 1 && stride != 2) return WSMG_EINVAL;
-  if (OH != (H + 2 * pad - KH) / stride + 1 || OW != (W + 2 * pad - KW) / stride + 1) return WSMG_EINVAL;
-  if ((int64_t)B * H * W >= (1ll << 31) || (int64_t)B * OH * OW >= (1ll << 31)) return WSMG_EINVAL;
+int check_conv_bf16(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH, int OW) {
+  if (int e = wsmg_check_conv(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
   // 32-bit byte offsets into the buffer resources
   if ((int64_t)B * H * W * Cin * 2 >= (1ll << 31) || (int64_t)B * OH * OW * Cout * 2 >= (1ll << 31)) return WSMG_EINVAL;
   return 0;
@@ -753,7 +717,7 @@ extern "C" int wsmg_conv2d_splitk_plan(int B, int OH, int OW, int Cin, int Cout,
 extern "C" int wsmg_conv2d_fwd_bf16_splitk(const void* x, const void* w_ohwi, const float* bias, void* y, int flags, int ksplit,
                                            float* part, int B, int H, int W, int Cin, int Cout, int KH, int KW,
                                            int stride, int pad, int OH, int OW, wsmg_stream_t stream) {
-  if (int e = check_conv(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
+  if (int e = check_conv_bf16(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
   const int64_t M = (int64_t)B * OH * OW;
   if (ksplit < 2 || ksplit != splitk_plan(M, Cin, Cout, KH, KW) || !part || (flags & ~7)) return WSMG_EINVAL;
   ConvArgsB a{(const bf16_t*)x, (const bf16_t*)w_ohwi, nullptr, y, B, H, W, Cin, OH, OW, Cout, KH, KW, stride, pad, 0, 0, flags,
@@ -775,7 +739,7 @@ namespace {
 // y_ld (0 = Cout): pixel pitch of y in elements — y may be a channel slice of a wider tensor
 int conv_fwd_bf16_impl(const void* x, const void* w_ohwi, const float* bias, void* y, int out_f32, double* stats, int nslab, int y_ld, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
                        int OH, int OW, wsmg_stream_t stream) {
-  if (int e = check_conv(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
+  if (int e = check_conv_bf16(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
   if (stats && (nslab <= 0 || (out_f32 & 5) != 0 || (Cout & 7) != 0)) return WSMG_EINVAL;   // statistics: bf16 output, no accumulate
   const bool ex = y_ld && y_ld != Cout;
   if (ex) {
@@ -838,7 +802,7 @@ namespace {
 int conv_bwd_data_bf16_impl(const void* dy, const void* w_ihwo, void* dx, int out_f32, double* stats, int nslab, const void* relu_y,
                             void* dx2, int split_c, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH,
                             int OW, wsmg_stream_t stream) {
-  if (int e = check_conv(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
+  if (int e = check_conv_bf16(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
   if (stats && (nslab <= 0 || (out_f32 & 5) != 0 || (Cin & 7) != 0)) return WSMG_EINVAL;
   if (relu_y && ((out_f32 & 5) != 0 || (Cin & 7) != 0 || ((uintptr_t)relu_y & 15))) return WSMG_EINVAL;
   if (dx2 && ((out_f32 & 5) != 0 || (Cin & 7) != 0 || split_c <= 0 || split_c >= Cin || (split_c & 7) || ((uintptr_t)dx2 & 15))) return WSMG_EINVAL;
@@ -893,7 +857,7 @@ extern "C" int wsmg_conv2d_bwd_data_bf16_ex(const void* dy, const void* w_ihwo, 
 extern "C" int wsmg_conv_transpose2d_infer_bf16(const void* x, const void* w_ihwo, const float* bias, void* y, int flags, int B,
                                                 int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH,
                                                 int OW, wsmg_stream_t stream) {
-  if (int e = check_conv(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
+  if (int e = check_conv_bf16(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
   if (flags & ~3) return WSMG_EINVAL;
   ConvArgsB a{(const bf16_t*)x, (const bf16_t*)w_ihwo, bias, y, B, OH, OW, Cout, H, W, Cin, KH, KW, stride, pad, 0, 0, flags,
               (unsigned)((size_t)B * OH * OW * Cout * 2), (unsigned)((size_t)Cout * KH * KW * Cin * 2), nullptr, 0};
@@ -1003,7 +967,7 @@ int launch_wgrad_bf16(const void* x, const void* dy, float* dw, long long slab_f
 extern "C" int wsmg_conv2d_bwd_weight_bf16(const void* x, const void* dy, float* dw_ohwi, int B, int H, int W, int Cin,
                                            int Cout, int KH, int KW, int stride, int pad, int OH, int OW,
                                            wsmg_stream_t stream) {
-  if (int e = check_conv(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
+  if (int e = check_conv_bf16(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
   return launch_wgrad_bf16(x, dy, dw_ohwi, 0, B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW, wsmg_s(stream));
 }
 
@@ -1012,7 +976,7 @@ extern "C" int wsmg_conv2d_bwd_weight_bf16(const void* x, const void* dy, float*
 extern "C" int wsmg_conv2d_bwd_weight_bf16_plan(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH,
                                                 int OW, int* nsplit, long long* ws_floats) {
   if (!nsplit || !ws_floats) return WSMG_EINVAL;
-  if (int e = check_conv(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
+  if (int e = check_conv_bf16(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
   const WgradPlan p = wgrad_plan_bf16(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW);
   *nsplit = p.nsplit;
   *ws_floats = (long long)p.nsplit * Cout * KH * KW * Cin;
@@ -1026,7 +990,7 @@ extern "C" int wsmg_conv2d_bwd_weight_bf16_plan(int B, int H, int W, int Cin, in
 extern "C" int wsmg_conv2d_bwd_weight_bf16_slabs(const void* x, const void* dy, float* ws, int nsplit, long long ws_floats, int B, int H,
                                                  int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH, int OW,
                                                  wsmg_stream_t stream) {
-  if (int e = check_conv(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
+  if (int e = check_conv_bf16(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
   const WgradPlan p = wgrad_plan_bf16(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW);
   const long long slab = (long long)Cout * KH * KW * Cin;
   if (!ws || nsplit != p.nsplit || ws_floats < slab * p.nsplit) return WSMG_EINVAL;

@@ -21,13 +21,9 @@
 // (3) 8 waves where the layer has four co tiles (enc3).
 #include <stdlib.h>
 
-#include "wsmg_common.h"
+#include "wsmg_conv_tile.h"
 
 namespace {
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef short bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 struct S2wArgs {
   const bf16_t* x;    // [B][H][W][Cin]
@@ -37,16 +33,6 @@ struct S2wArgs {
   int B, H, W, OH, OW, Cin, tiles_y, groups;
   unsigned x_bytes, dy_bytes;
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ u32x4 buf_load16(__amdgpu_buffer_rsrc_t r, int byte_off) {
-  return __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0);
-}
-__device__ __forceinline__ bf16x4 tr_read(const unsigned char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((bf16x4 __attribute__((address_space(3)))*)(p));
-}
 
 // K, P: kernel size and padding (stride 2); TH x TW: output pixels of a tile (TW = OW: whole rows); NCO: 32-channel tiles of Cout;
 // NW: waves (NW = 2 NCO: wave -> (co tile, ci half)); NCC: 64-channel chunks of Cin (roles = K x NCC)

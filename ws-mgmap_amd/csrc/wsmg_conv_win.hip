@@ -18,13 +18,9 @@
 // t+1 being read ahead, t+2 being filled), and the weight slice of tap t+2 is requested from memory at the same time.
 #include <stdlib.h>
 
-#include "wsmg_common.h"
+#include "wsmg_conv_tile.h"
 
 namespace {
-
-typedef __bf16 bf16_t;
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 struct WinArgs {
   const bf16_t* x;    // [B][H][W][64]
@@ -33,24 +29,9 @@ struct WinArgs {
   bf16_t* y;          // [B][OH][OW][64]
   int B, H, W, OH, OW, tiles_y, tiles_x, relu;
   unsigned x_bytes, w_bytes;
-  double* stats;   // or null: [nslab][2][64] float64 batch-norm sums of the output (see conv_igemm_bf16_kernel)
+  double* stats;   // or null: [nslab][2][64] float64 batch-norm sums of the output (wsmg_conv_tile.h)
   int nslab;
 };
-
-__device__ __forceinline__ int xcd_swizzle(int bid, int nb) {
-  const int q = nb >> 3, r = nb & 7, x = bid & 7;
-  return x * q + (x < r ? x : r) + (bid >> 3);
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ u32x4 buf_load16(__amdgpu_buffer_rsrc_t r, int byte_off) {
-  return __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0);
-}
-__device__ __forceinline__ unsigned short f2bf_bits(float f) {
-  bf16_t b = (bf16_t)f;
-  return __builtin_bit_cast(unsigned short, b);
-}
 
 template <int K, int S, int P, int TH, int TW>
 __global__ __launch_bounds__(256) void conv_win_fwd_kernel(WinArgs a) {
@@ -214,9 +195,7 @@ __global__ __launch_bounds__(256) void conv_win_fwd_kernel(WinArgs a) {
       if (a.relu) v = v > 0.f ? v : 0.f;
       const unsigned short o = f2bf_bits(v);
       *reinterpret_cast<unsigned short*>(win + (wave * 32 + row) * PITCH + co * 2) = o;
-      // train-mode BatchNorm sums of the ROUNDED value, straight from the registers (a second pass over the staged tile
-      // — 32 two-byte LDS reads per thread — cost 0.07 ms of the layer)
-      const float vr = (okmask >> g) & 1u ? __uint_as_float((unsigned)o << 16) : 0.f;
+      const float vr = (okmask >> g) & 1u ? bf2f(o) : 0.f;
       sv += vr;
       qv = fmaf(vr, vr, qv);
     }

@@ -26,7 +26,7 @@
 //     slice's fragments of a step are read during the step before, so no MFMA waits on LDS right after a barrier;
 //   * backward-data of a stride-1 3 x 3 convolution is the same sum with the shifts negated and the weights as IHWO.
 //
-// Epilogue through LDS in two 64-column halves: bias / ReLU / BatchNorm sums as in conv_igemm_bf16_kernel.
+// Epilogue through LDS in two 64-column halves: bias / ReLU / BatchNorm sums as wsmg_conv_tile.h describes them.
 //
 // Where a tile's cycles go (s_memtime, cated layer 256 -> 256 at B = 512, MT = 512): address arithmetic + first window 13 %,
 // k-loop 79 % (1 294 cycles per k-step against 1 024 of MFMA), epilogue 8 %; whole kernel 54 % MFMA-busy at 1.9 GHz
@@ -42,13 +42,10 @@
 
 #include <type_traits>
 
-#include "wsmg_common.h"
+#include "wsmg_conv_tile.h"
 #include "wsmg_relu_mask.h"
 
 namespace {
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 struct Win3Args {
   const bf16_t* src;  // [B][H][W][Kc]
@@ -76,17 +73,6 @@ struct Win3Args {
 constexpr int DK = 32, ROWB = 64, NST = 4;
 constexpr int OPITCH = 64 * 2 + 16;          // epilogue staging: 64 columns of bf16 + 16
 
-__device__ __forceinline__ int xcd_swizzle3(int bid, int nb) {
-  const int q = nb >> 3, r = nb & 7, x = bid & 7;
-  return x * q + (x < r ? x : r) + (bid >> 3);
-}
-__device__ __forceinline__ unsigned short f2bf3(float f) {
-  bf16_t b = (bf16_t)f;
-  return __builtin_bit_cast(unsigned short, b);
-}
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, unsigned char* lds_wave_base, int byte_off) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds_wave_base, 16, byte_off, 0, 0, 0);
-}
 // DMA instructions a wave issues in the k-step at tap `tap`: a window piece of the next chunk (taps 0 .. npw - 1) and the weights of 3 steps on
 constexpr int n_issue(int tap, int npw) { return ((tap % 9 + 9) % 9) < npw ? 2 : 1; }
 
@@ -110,7 +96,7 @@ __device__ __forceinline__ void win3_tile_body(const Win3Args& a, const int bid,
   static_assert(MT * OPITCH <= OFF_DUMMY, "epilogue staging fits under the k-loop's LDS");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int logical = xcd_swizzle3(bid, nblocks);
+  const int logical = xcd_swizzle(bid, nblocks);
   const int m0 = m_base + (logical / a.ntiles) * MT, n0 = (logical % a.ntiles) * NT;
   const int H = a.H, W = a.W, PW = W + 2, PP = (H + 2) * PW;
   const int Mtot = a.B * H * W;
@@ -148,8 +134,7 @@ __device__ __forceinline__ void win3_tile_body(const Win3Args& a, const int bid,
   // weights: piece `wave` of a k-step = rows 16 wave .. + 15 of the [128][32] tile
   const int brow = 16 * wave + lrow;
   const int boff = (n0 + brow) * 9 * a.Kc * 2 + 16 * (slot ^ ((brow >> 2) & 3));
-  const __amdgpu_buffer_rsrc_t rs_src = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.src), 0, (int)a.src_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_wt = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.wt), 0, (int)a.wt_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_src = make_rsrc(a.src, a.src_bytes), rs_wt = make_rsrc(a.wt, a.wt_bytes);
   const int nchunks = a.Kc / DK;
 
   auto dma_window_piece = [&](int j, int chunk) {   // piece j of chunk's window -> buffer chunk & 1 (past the last chunk: zeros)
@@ -278,10 +263,10 @@ __device__ __forceinline__ void win3_tile_body(const Win3Args& a, const int bid,
         const int row = wm + 32 * t + (g & 3) + 8 * (g >> 2) + 4 * h;
         float v = acc[t][u][g] + bv;
         if (a.relu) v = v > 0.f ? v : 0.f;
-        const unsigned short o = f2bf3(v);
+        const unsigned short o = f2bf_bits(v);
         *reinterpret_cast<unsigned short*>(smem + row * OPITCH + scol * 2) = o;
-        if (a.stats) {   // train-mode BatchNorm sums of the ROUNDED values, from the registers (see conv_igemm_bf16_kernel)
-          const float vr = m0 + row < Mtot ? __uint_as_float((unsigned)o << 16) : 0.f;
+        if (a.stats) {
+          const float vr = m0 + row < Mtot ? bf2f(o) : 0.f;
           sv += vr;
           qv = fmaf(vr, vr, qv);
         }
@@ -386,22 +371,10 @@ int launch_win3(Win3Args& a, hipStream_t s) {
   return aux_form(a) ? launch_win3_aux<MT, NPW, NT, 1>(a, s) : launch_win3_aux<MT, NPW, NT, 0>(a, s);
 }
 
-int g_cus3 = 0;
-int win3_cus() {
-  if (!g_cus3) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    g_cus3 = 256;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-      g_cus3 = prop.multiProcessorCount;
-  }
-  return g_cus3;
-}
-
 // Split of a layer's M pixels x (N / NT) channel tiles into whole rounds of MT-pixel tiles and a remainder of MT/2-pixel tiles; false
 // when the plain launch is as good (whole rounds already, fewer than one round, or a remainder that would still need two rounds)
 bool mixed_plan(Win3Args& a, int64_t M, int MT, int NT) {
-  const int cus = win3_cus();
+  const int cus = wsmg_cu_count();
   const int ntiles = a.N / NT;
   const int64_t big = wsmg_cdiv(M, MT) * ntiles;
   const int64_t full = big / cus * cus;
@@ -435,14 +408,6 @@ int launch_win3_mixed(Win3Args& a, hipStream_t s) {
   return aux_form(a) ? launch_win3_mixed_aux<MT, NPW, NPW_S, NT, 1>(a, s) : launch_win3_mixed_aux<MT, NPW, NPW_S, NT, 0>(a, s);
 }
 
-// window entries a tile of mt consecutive pixels can need: the pixels, 2 pads per image row crossed, the pad rows between
-// images, and one padded row + 1 entry of halo on either side
-int window_bound(int mt, int H, int W) {
-  const int rows = (mt + W - 2) / W + 1;             // image rows a run of mt pixels can touch
-  const int imgs = (mt + H * W - 2) / (H * W) + 1;   // images
-  return mt + 2 * (rows - 1) + 2 * (W + 2) * (imgs - 1) + 2 * (W + 3) + 1;
-}
-
 }  // namespace
 
 // 3 x 3 / stride 1 / pad 1, bf16 in / bf16 out, N % 64 == 0 (128-channel tiles when N % 128 == 0), Kc % 32 == 0; WSMG_EINVAL otherwise (the caller then uses the
@@ -460,26 +425,26 @@ int wsmg_conv_win3_bf16(int bwd, const void* src, const void* wt, const float* b
   // mixed == 0 (a tile size forced through wsmg_conv_debug_win3_tile) or WSMG_CONV_WIN3_MIXED=0: one tile size per launch (rounds 2-4; A/B)
   const bool mix = mixed && WSMG_TUNE("WSMG_CONV_WIN3_MIXED", 1) != 0;
   if (N % 128 == 0) {
-    if (mt == 512 && window_bound(512, H, W) <= 128 * 6) {
-      if (mix && window_bound(256, H, W) <= 128 * 4 && mixed_plan(a, M, 512, 128)) return launch_win3_mixed<512, 6, 4, 128>(a, s);
+    if (mt == 512 && wsmg_win3_window_bound(512, H, W) <= 128 * 6) {
+      if (mix && wsmg_win3_window_bound(256, H, W) <= 128 * 4 && mixed_plan(a, M, 512, 128)) return launch_win3_mixed<512, 6, 4, 128>(a, s);
       return launch_win3<512, 6, 128>(a, s);
     }
-    if (mt == 256 && window_bound(256, H, W) <= 128 * 4) {
-      if (mix && window_bound(128, H, W) <= 128 * 2 && mixed_plan(a, M, 256, 128)) return launch_win3_mixed<256, 4, 2, 128>(a, s);
+    if (mt == 256 && wsmg_win3_window_bound(256, H, W) <= 128 * 4) {
+      if (mix && wsmg_win3_window_bound(128, H, W) <= 128 * 2 && mixed_plan(a, M, 256, 128)) return launch_win3_mixed<256, 4, 2, 128>(a, s);
       return launch_win3<256, 4, 128>(a, s);
     }
     return WSMG_EINVAL;
   }
   if (N % 64 == 0) {   // 64-channel tiles (N = 64, 192, ...)
-    if (mt == 512 && window_bound(512, H, W) <= 128 * 6) {
-      if (mix && window_bound(256, H, W) <= 128 * 4 && mixed_plan(a, M, 512, 64)) return launch_win3_mixed<512, 6, 4, 64>(a, s);
+    if (mt == 512 && wsmg_win3_window_bound(512, H, W) <= 128 * 6) {
+      if (mix && wsmg_win3_window_bound(256, H, W) <= 128 * 4 && mixed_plan(a, M, 512, 64)) return launch_win3_mixed<512, 6, 4, 64>(a, s);
       return launch_win3<512, 6, 64>(a, s);
     }
-    if (mt == 256 && window_bound(256, H, W) <= 128 * 4) return launch_win3<256, 4, 64>(a, s);
+    if (mt == 256 && wsmg_win3_window_bound(256, H, W) <= 128 * 4) return launch_win3<256, 4, 64>(a, s);
     return WSMG_EINVAL;
   }
   // 32-channel tiles (N = 32, 96, ...)
-  if (mt == 512 && window_bound(512, H, W) <= 128 * 6) return launch_win3<512, 6, 32>(a, s);
-  if (mt == 256 && window_bound(256, H, W) <= 128 * 4) return launch_win3<256, 4, 32>(a, s);
+  if (mt == 512 && wsmg_win3_window_bound(512, H, W) <= 128 * 6) return launch_win3<512, 6, 32>(a, s);
+  if (mt == 256 && wsmg_win3_window_bound(256, H, W) <= 128 * 4) return launch_win3<256, 4, 32>(a, s);
   return WSMG_EINVAL;
 }

@@ -15,12 +15,9 @@
 //     chunk cannot give a workgroup with itself.
 // Same MFMA sequence per output element as the window kernel (tap-major, slice-minor, one accumulator): bit-identical outputs.
 // BatchNorm sums: per lane over a workgroup's whole run, one set of float64 atomics per workgroup at the end.
-#include "wsmg_common.h"
+#include "wsmg_conv_tile.h"
 
 namespace {
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 struct K32Args {
   const bf16_t* src;  // [B][H][W][32]
@@ -36,14 +33,6 @@ struct K32Args {
 constexpr int MT = 256, WCAP = 512, ROWB = 64, WINB = WCAP * ROWB, TAPB = 32 * ROWB, WTB = 9 * TAPB, OP = 80;
 constexpr int K32_LDS = WINB + WTB;
 
-__device__ __forceinline__ void dma16k(__amdgpu_buffer_rsrc_t r, unsigned char* lds_wave_base, int byte_off) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds_wave_base, 16, byte_off, 0, 0, 0);
-}
-__device__ __forceinline__ unsigned short f2bfk(float f) {
-  bf16_t b = (bf16_t)f;
-  return __builtin_bit_cast(unsigned short, b);
-}
-
 __global__ __launch_bounds__(256) void conv_win3_k32_kernel(K32Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* const win = smem;
@@ -54,15 +43,14 @@ __global__ __launch_bounds__(256) void conv_win3_k32_kernel(K32Args a) {
   const int H = a.H, W = a.W, PW = W + 2, PP = (H + 2) * PW;
   const int Mtot = a.B * H * W;
   const int n0 = ((int)blockIdx.x % a.ntiles) * 32;
-  const __amdgpu_buffer_rsrc_t rs_src = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.src), 0, (int)a.src_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_wt = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.wt), 0, (int)a.wt_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_src = make_rsrc(a.src, a.src_bytes), rs_wt = make_rsrc(a.wt, a.wt_bytes);
 
   // ---- this channel tile's weights, once: piece p = (tap, 16-row half) -> wts[tap][row][64 B], 16-byte slot s of a row at s ^ ((row >> 2) & 3)
 #pragma unroll
   for (int j = 0; j < 5; ++j) {
     const int p = wave + 4 * j;
     const int tap = p >> 1, row = 16 * (p & 1) + lrow;
-    if (p < 18) dma16k(rs_wt, wts + tap * TAPB + (p & 1) * 1024, ((n0 + row) * 9 + tap) * 64 + 16 * (slot ^ ((row >> 2) & 3)));
+    if (p < 18) dma16(rs_wt, wts + tap * TAPB + (p & 1) * 1024, ((n0 + row) * 9 + tap) * 64 + 16 * (slot ^ ((row >> 2) & 3)));
   }
   const int bposk[2] = {r * ROWB + (((0 + h) ^ ((r >> 2) & 3)) << 4), r * ROWB + (((2 + h) ^ ((r >> 2) & 3)) << 4)};
   const float bv = a.bias ? a.bias[n0 + r] : 0.f;
@@ -94,7 +82,7 @@ __global__ __launch_bounds__(256) void conv_win3_k32_kernel(K32Args a) {
         const int e = e0 + 64 * j;
         const int yy = pr - 1, xx = pc - 1;
         const bool ok = e < nwin && b < a.B && yy >= 0 && yy < H && xx >= 0 && xx < W;
-        dma16k(rs_src, win + (4 * j + wave) * 1024, ok ? (((b * H + yy) * W + xx) * 32) * 2 + 16 * (slot ^ ((e >> 2) & 3)) : (int)0x80000000);
+        dma16(rs_src, win + (4 * j + wave) * 1024, ok ? (((b * H + yy) * W + xx) * 32) * 2 + 16 * (slot ^ ((e >> 2) & 3)) : (int)0x80000000);
         pc += 64;
         while (pc >= PW) { pc -= PW; ++pr; }
         while (pr >= H + 2) { pr -= H + 2; ++b; }
@@ -148,10 +136,10 @@ __global__ __launch_bounds__(256) void conv_win3_k32_kernel(K32Args a) {
         const int row = wave * 64 + 32 * t + (g & 3) + 8 * (g >> 2) + 4 * h;
         float v = acc[t][g] + bv;
         if (a.relu) v = v > 0.f ? v : 0.f;
-        const unsigned short o = f2bfk(v);
+        const unsigned short o = f2bf_bits(v);
         *reinterpret_cast<unsigned short*>(win + row * OP + r * 2) = o;
-        if (a.stats) {   // train-mode BatchNorm sums of the ROUNDED values
-          const float vr = m0 + row < Mtot ? __uint_as_float((unsigned)o << 16) : 0.f;
+        if (a.stats) {
+          const float vr = m0 + row < Mtot ? bf2f(o) : 0.f;
           sv += vr;
           qv = fmaf(vr, vr, qv);
         }
@@ -186,38 +174,25 @@ __global__ __launch_bounds__(256) void conv_win3_k32_kernel(K32Args a) {
   }
 }
 
-// window entries a tile of mt consecutive pixels can need (wsmg_conv_win3.hip's window_bound)
-int k32_window_bound(int mt, int H, int W) {
-  const int rows = (mt + W - 2) / W + 1;
-  const int imgs = (mt + H * W - 2) / (H * W) + 1;
-  return mt + 2 * (rows - 1) + 2 * (W + 2) * (imgs - 1) + 2 * (W + 3) + 1;
-}
-
 }  // namespace
 
 // Kc == 32, N % 32 == 0, plain output (no mask, no split); WSMG_EINVAL otherwise (the caller then uses the general window kernel)
 int wsmg_conv_win3_k32_bf16(int bwd, const void* src, const void* wt, const float* bias, void* dst, int relu, double* stats, int nslab,
                             int B, int H, int W, int N, int dst_ld, hipStream_t s) {
-  if (N <= 0 || N % 32 || B <= 0 || k32_window_bound(MT, H, W) > WCAP) return WSMG_EINVAL;
+  if (N <= 0 || N % 32 || B <= 0 || wsmg_win3_window_bound(MT, H, W) > WCAP) return WSMG_EINVAL;
   if (stats && nslab <= 0) return WSMG_EINVAL;
   K32Args a{(const bf16_t*)src, (const bf16_t*)wt, bias, (bf16_t*)dst, B, H, W, N, N / 32, 0, relu, bwd, dst_ld,
             (unsigned)((size_t)B * H * W * 32 * 2), (unsigned)((size_t)N * 9 * 32 * 2), stats, nslab};
   const int64_t M = (int64_t)B * H * W;
   a.mtiles = (int)wsmg_cdiv(M, MT);
-  static int cus = 0;
   static bool attr = false;
   if (!attr) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_win3_k32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, K32_LDS);
     if (e != hipSuccess) return (int)e;
-    int dev = 0;
-    hipDeviceProp_t prop;
-    cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-      cus = prop.multiProcessorCount;
     attr = true;
   }
   const int64_t tiles = (int64_t)a.mtiles * a.ntiles;
-  int64_t grid = (int64_t)WSMG_TUNE("WSMG_CONV_K32_WGS", 6) * cus;
+  int64_t grid = (int64_t)WSMG_TUNE("WSMG_CONV_K32_WGS", 6) * wsmg_cu_count();
   if (grid > tiles) grid = tiles;
   grid = grid / a.ntiles * a.ntiles;            // a workgroup's channel tile is blockIdx % ntiles for every tile it walks
   if (grid <= 0) return WSMG_EINVAL;

@@ -35,12 +35,9 @@
 // then waves 0-3 multiply.
 #include <stdlib.h>
 
-#include "wsmg_common.h"
+#include "wsmg_conv_tile.h"
 
 namespace {
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef short bf16x4 __attribute__((ext_vector_type(4)));
 
 struct W3wArgs {
   const bf16_t* x;    // [B][H][W][Cin]
@@ -58,16 +55,6 @@ struct W3wArgs {
 constexpr int RED_BYTES = 4 * 9 * 16 * 64 * 4;   // the closing reduction of a pixel-split tile: four waves' nine accumulator tiles (144 KB)
 constexpr int OOB = (int)0x80000000;
 
-__device__ __forceinline__ int xcd_swizzle_w(int bid, int nb) {
-  const int q = nb >> 3, r = nb & 7, x = bid & 7;
-  return x * q + (x < r ? x : r) + (bid >> 3);
-}
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, unsigned char* lds_wave_base, int byte_off) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds_wave_base, 16, byte_off, 0, 0, 0);
-}
-__device__ __forceinline__ bf16x4 tr_read(const unsigned char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((bf16x4 __attribute__((address_space(3)))*)(p));
-}
 // 64-byte quarter swizzle of a row of `pitch` bytes (see the header)
 template <int PITCH>
 __device__ __forceinline__ int quarter_xor(int row) {
@@ -97,7 +84,7 @@ __global__ __launch_bounds__(512) void conv_win3_wgrad_kernel(W3wArgs a) {
   const int H = a.H, W = a.W, PW = W + 2, HPW = H * PW;
   const int nseg = (HPW + KS - 1) / KS;
   // workgroup -> (tile, image range): the tiles of one range are consecutive logical ids (same XCD: they read the same images)
-  const int logical = xcd_swizzle_w(blockIdx.x, gridDim.x);
+  const int logical = xcd_swizzle(blockIdx.x, gridDim.x);
   const int ntile = a.gco * a.gci;
   const int z = logical / ntile, tl = logical - z * ntile;
   const int co0 = (tl / a.gci) * 32 * WCO, ci0 = (tl % a.gci) * 32 * WCI;
@@ -290,18 +277,6 @@ __global__ __launch_bounds__(512) void conv_win3_wgrad_kernel(W3wArgs a) {
     }
 }
 
-int w3w_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    cus = 256;     // (MI355X; also the answer where no device can be asked — the plan call of a GPU-less build check)
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-      cus = prop.multiProcessorCount;
-  }
-  return cus;
-}
-
 // The tile shapes (WCO, WCI, WK, SL, XCAP):
 //   V421: 128 co x 64 ci, 48-entry k-steps — the wide layers (cated 256 -> 256, enc6 128 -> 256, encoded_lin 256 -> 128), W <= 24
 //   V222:  64 co x 64 ci, two waves per tile pair, 64-entry k-steps — the decoder's 64-output-channel layers (256 / 192 / 64 -> 64), W <= 24
@@ -335,7 +310,7 @@ void plan_w3w(W3wArgs& a, W3wVariant v) {
   a.gco = a.Cout / (32 * kShape[v].wco);
   a.gci = a.Cin / (32 * kShape[v].wci);
   const int ntile = a.gco * a.gci;
-  int gz = w3w_cus() / ntile;
+  int gz = wsmg_cu_count() / ntile;
   if (gz < 1) gz = 1;
   if (gz > a.B) gz = a.B;
   a.imgs = (a.B + gz - 1) / gz;

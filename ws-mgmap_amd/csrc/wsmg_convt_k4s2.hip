@@ -14,12 +14,9 @@
 //   * 64 KB of LDS: two workgroups per CU.
 // Same MFMA sequence per output element as the implicit-GEMM kernel (tap row, tap column, 16-deep slice; one accumulator):
 // bit-identical outputs.  BatchNorm sums per lane over a workgroup's run, one set of float64 atomics per workgroup.
-#include "wsmg_common.h"
+#include "wsmg_conv_tile.h"
 
 namespace {
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 struct CtArgs {
   const bf16_t* src;  // [B][H][W][64]      the ConvTranspose's input (the adjoint convolution's dy)
@@ -36,14 +33,6 @@ constexpr int CT_OP = 144;                 // staged output: [input pixel][colum
 constexpr int CT_LDS = CT_WINB + CT_WTB + CT_MT * 4;
 static_assert(CT_MT * CT_OP <= CT_WINB, "the output tile is staged in the window");
 
-__device__ __forceinline__ void dma16c(__amdgpu_buffer_rsrc_t r, unsigned char* lds_wave_base, int byte_off) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds_wave_base, 16, byte_off, 0, 0, 0);
-}
-__device__ __forceinline__ unsigned short f2bfc(float f) {
-  bf16_t b = (bf16_t)f;
-  return __builtin_bit_cast(unsigned short, b);
-}
-
 __global__ __launch_bounds__(256) void convt_k4s2_kernel(CtArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* const win = smem;
@@ -55,8 +44,7 @@ __global__ __launch_bounds__(256) void convt_k4s2_kernel(CtArgs a) {
   const int Mtot = a.B * H * W;
   const int cy = (int)blockIdx.x & 1;          // parity of the kernel row: taps ky = cy, cy + 2; output rows of parity (cy + 1) & 1
   const int ty0 = (cy + 1) & 1;
-  const __amdgpu_buffer_rsrc_t rs_src = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.src), 0, (int)a.src_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_wt = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.wt), 0, (int)a.wt_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_src = make_rsrc(a.src, a.src_bytes), rs_wt = make_rsrc(a.wt, a.wt_bytes);
   const int drow = lane >> 3, dslot = lane & 7;   // DMA roles: a 1 KB piece = 8 rows of 128 B, lane = (row, 16-byte slot)
 
   // ---- weights of this row parity, once: block (cx, ay, ax) = 32 rows n of [64 k] at wts[(cx * 4 + ay * 2 + ax)]; 16-byte chunk c of row n
@@ -67,7 +55,7 @@ __global__ __launch_bounds__(256) void convt_k4s2_kernel(CtArgs a) {
     const int blk = p >> 2, n = 8 * (p & 3) + drow;
     const int cx = blk >> 2, ay = (blk >> 1) & 1, ax = blk & 1;
     const int ky = cy + 2 * ay, kx = cx + 2 * ax;
-    dma16c(rs_wt, wts + p * 1024, ((n * 4 + ky) * 4 + kx) * 128 + 16 * (dslot ^ ((n >> 1) & 7)));
+    dma16(rs_wt, wts + p * 1024, ((n * 4 + ky) * 4 + kx) * 128 + 16 * (dslot ^ ((n >> 1) & 7)));
   }
   int bpos[4];   // byte offset of this lane's weight fragment of slice ks inside a block
 #pragma unroll
@@ -97,7 +85,7 @@ __global__ __launch_bounds__(256) void convt_k4s2_kernel(CtArgs a) {
         const int e = e0 + 32 * j;
         const int yy = pr - 1, xx = pc - 1;
         const bool ok = e < nwin && b < a.B && yy >= 0 && yy < H && xx >= 0 && xx < W;
-        dma16c(rs_src, win + (4 * j + wave) * 1024, ok ? (((b * H + yy) * W + xx) * 64) * 2 + 16 * (dslot ^ ((e >> 1) & 7)) : (int)0x80000000);
+        dma16(rs_src, win + (4 * j + wave) * 1024, ok ? (((b * H + yy) * W + xx) * 64) * 2 + 16 * (dslot ^ ((e >> 1) & 7)) : (int)0x80000000);
         pc += 32;
         while (pc >= PW) { pc -= PW; ++pr; }
         while (pr >= H + 2) { pr -= H + 2; ++b; }
@@ -147,10 +135,10 @@ __global__ __launch_bounds__(256) void convt_k4s2_kernel(CtArgs a) {
 #pragma unroll
       for (int g = 0; g < 16; ++g) {
         const int row = wave * 32 + (g & 3) + 8 * (g >> 2) + 4 * h;
-        const unsigned short o = f2bfc(acc[cx][g]);
+        const unsigned short o = f2bf_bits(acc[cx][g]);
         *reinterpret_cast<unsigned short*>(win + row * CT_OP + (1 - cx) * 64 + r * 2) = o;
-        if (a.stats) {   // train-mode BatchNorm sums of the ROUNDED values
-          const float vr = m0 + row < Mtot ? __uint_as_float((unsigned)o << 16) : 0.f;
+        if (a.stats) {
+          const float vr = m0 + row < Mtot ? bf2f(o) : 0.f;
           sv += vr;
           qv = fmaf(vr, vr, qv);
         }
@@ -185,35 +173,23 @@ __global__ __launch_bounds__(256) void convt_k4s2_kernel(CtArgs a) {
   }
 }
 
-int ct_window_bound(int mt, int H, int W) {
-  const int rows = (mt + W - 2) / W + 1;
-  const int imgs = (mt + H * W - 2) / (H * W) + 1;
-  return mt + 2 * (rows - 1) + 2 * (W + 2) * (imgs - 1) + 2 * (W + 3) + 1;
-}
-
 }  // namespace
 
 // dst [B][2H][2W][32] = ConvTranspose2d(k4, s2, p1) of src [B][H][W][64] with the adjoint convolution's IHWO weights [32][4][4][64];
 // WSMG_EINVAL for geometries whose window does not fit (the caller then uses the implicit-GEMM kernel)
 int wsmg_convt_k4s2_bf16(const void* src, const void* w_ihwo, void* dst, double* stats, int nslab, int B, int H, int W, hipStream_t s) {
-  if (B <= 0 || H <= 0 || W <= 0 || ct_window_bound(CT_MT, H, W) > CT_ENT || (stats && nslab <= 0)) return WSMG_EINVAL;
+  if (B <= 0 || H <= 0 || W <= 0 || wsmg_win3_window_bound(CT_MT, H, W) > CT_ENT || (stats && nslab <= 0)) return WSMG_EINVAL;
   if ((int64_t)B * 4 * H * W * 32 * 2 >= (1ll << 31) || (int64_t)B * (H + 2) * (W + 2) >= (1 << 30)) return WSMG_EINVAL;
   CtArgs a{(const bf16_t*)src, (const bf16_t*)w_ihwo, (bf16_t*)dst, B, H, W, (int)wsmg_cdiv((int64_t)B * H * W, CT_MT),
            (unsigned)((size_t)B * H * W * 64 * 2), (unsigned)(32u * 16 * 64 * 2), stats, nslab};
-  static int cus = 0;
   static bool attr = false;
   if (!attr) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(convt_k4s2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, CT_LDS);
     if (e != hipSuccess) return (int)e;
-    int dev = 0;
-    hipDeviceProp_t prop;
-    cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-      cus = prop.multiProcessorCount;
     attr = true;
   }
   const int64_t units = (int64_t)a.mtiles * 2;
-  int64_t grid = (int64_t)WSMG_TUNE("WSMG_CONVT_WGS", 6) * cus;
+  int64_t grid = (int64_t)WSMG_TUNE("WSMG_CONVT_WGS", 6) * wsmg_cu_count();
   if (grid > units) grid = units;
   grid &= ~(int64_t)1;                          // a workgroup's row parity is blockIdx & 1 for every unit it walks
   if (grid <= 0) return WSMG_EINVAL;
