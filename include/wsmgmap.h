@@ -807,6 +807,33 @@ int wsmg_cls_tail_bwd_bf16(const void* y2, const float* gamma, const float* beta
                            const float* w6, const float* b6, int classes, const float* gt, int Hg, int Wg, const float* g_rows,
                            const void* dpooled, int B, int H, int W, void* dbn, float* workspace, long long workspace_floats,
                            float* dgamma, float* dbeta, float* dw6, float* db6, wsmg_stream_t stream);
+/* ---- scoring the semantic-map head: confusion counts and IoU (csrc/wsmg_sem_eval.hip) -----------------------------------------
+ * Not a reference operator: the reference reports the prediction monitor's cross-entropy only (policy.py:61-66).
+ * wsmg_sem_confusion_f32 / _bf16: logits [B][H][W][32] (channels >= classes padding, never read into the decision), gt float32
+ * [B][Hg][Wg], row_mask uint8 [B] or NULL (every row); confusion int64 [classes][classes] and ignored int64 [2] are ACCUMULATED
+ * into (the caller zeroes them once); pred uint8 [B][H][W] or NULL.  Per pixel of a row with row_mask[b] != 0:
+ *   prediction = argmax over channels 0 .. classes-1, ties to the lowest index (-0.0 ties +0.0), +Inf an ordinary maximum; any NaN
+ *                among those channels: no prediction, pred = 255;
+ *   label      = gt[b][min(floorf(y * ((float)Hg / (float)H)), Hg - 1)][likewise x] truncated — F.interpolate(gt.unsqueeze(1),
+ *                size=(H, W)).long() as wsmg_cls_tail_fwd_bf16 forms it; valid iff g > -1.0f && g < (float)classes, decided on the
+ *                float (NaN, +-Inf invalid; -0.5 a valid 0);
+ *   an invalid label: ignored[0] += 1 and nothing else (pred is still written); otherwise no prediction: ignored[1] += 1;
+ *   otherwise confusion[label][prediction] += 1.
+ * A row with row_mask[b] == 0 contributes nothing and its pred is 255.  No arithmetic on the logits: exact; integer sums (LDS
+ * histogram per workgroup, one flush of 64-bit integer atomics): the same result in any order.  No allocation, no synchronisation,
+ * re-entrant across streams.
+ * The prediction-only use: gt, confusion and ignored ALL NULL and pred given (Hg, Wg not read) writes pred alone.
+ * WSMG_EINVAL before anything is enqueued: NULL logits; gt, confusion, ignored not all given outside the prediction-only use (or
+ * that use without pred); classes outside [1, 32]; B, H, W <= 0; Hg, Wg <= 0 with gt; B*H*W >= 2^31.
+ * wsmg_sem_scores: one launch, scores float64 [3 + 3 classes] = { pixels counted, pixel accuracy, mIoU, then per class: IoU =
+ * TP / (TP + FP + FN), ground-truth pixels, predicted pixels }; counts as doubles (exact below 2^53); a class with TP + FP + FN = 0
+ * has IoU NaN and is left out of the mIoU's mean; mIoU NaN with no class present, accuracy NaN with nothing counted.
+ * WSMG_EINVAL: NULL confusion or scores, classes outside [1, 32]. */
+int wsmg_sem_confusion_f32(const float* logits, int classes, const float* gt, int Hg, int Wg, int B, int H, int W,
+                           const uint8_t* row_mask, int64_t* confusion, int64_t* ignored, uint8_t* pred, wsmg_stream_t stream);
+int wsmg_sem_confusion_bf16(const void* logits, int classes, const float* gt, int Hg, int Wg, int B, int H, int W,
+                            const uint8_t* row_mask, int64_t* confusion, int64_t* ignored, uint8_t* pred, wsmg_stream_t stream);
+int wsmg_sem_scores(const int64_t* confusion, int classes, double* scores, wsmg_stream_t stream);
 /* BatchNorm2d (train mode) in halves (torch.nn.BatchNorm2d behind map_encoder.py:10-12 / mg_map_policy.py:80-84): statistics from
  * the slabs a convolution's epilogue filled (wsmg_conv2d_fwd_bf16_stats) -> save_mean, save_invstd, running statistics (slabs
  * returned zeroed); and the backward's apply pass alone, for a dy already masked by the ReLU and caller-supplied sums. */

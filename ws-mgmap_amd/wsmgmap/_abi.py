@@ -112,6 +112,10 @@ _SIG["wsmg_dagger_loss_bwd"] = [c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_p
 _SIG["wsmg_cls_tail_workspace_floats"] = [c_i]
 _SIG["wsmg_cls_tail_fwd_bf16"] = [c_p] * 7 + [c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]
 _SIG["wsmg_cls_tail_bwd_bf16"] = [c_p] * 7 + [c_i, c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_l, c_p, c_p, c_p, c_p, c_p]
+# scoring the semantic-map head (csrc/wsmg_sem_eval.hip): confusion counts per pixel, then accuracy / IoU / mIoU from the matrix
+_SIG["wsmg_sem_confusion_f32"] = [c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]
+_SIG["wsmg_sem_confusion_bf16"] = list(_SIG["wsmg_sem_confusion_f32"])
+_SIG["wsmg_sem_scores"] = [c_p, c_i, c_p, c_p]
 _SIG["wsmg_bn_stats_finalize"] = [c_p, c_i, c_i, c_l, c_f, c_f, c_p, c_p, c_p, c_p, c_p]
 _SIG["wsmg_bn_bwd_apply_bf16"] = [c_p] * 7 + [c_l, c_i, c_p, c_p]
 _SIG["wsmg_attn_fp8_mfma_fwd"] = [c_p] * 9 + [c_f, c_i, c_i, c_i, c_i, c_p, c_p, c_p]

@@ -47,6 +47,16 @@ class BasePolicy(nn.Module):
         finished by then and can be one update late).  Costs the host its run-ahead: opt-in."""
         ops.check_rnn_status(sync=sync)
 
+    def semantic_prediction(self):
+        """Not a reference method.  The predicted semantic map of the last forward pass: uint8 [B, 2S, 2S], the argmax over the
+        SEM_CLASSES class logits of `net.sem_logits_nhwc` (ties to the lowest class; 255 where a class logit is NaN), in one launch
+        of the scoring kernel's prediction-only use (ops.sem_confusion) — `pred_sem_map` is not materialised and the route of the
+        forward pass is not touched.  Scores against the ground truth: wsmgmap.metrics.SemanticMapMeter."""
+        logits = getattr(self.net, "sem_logits_nhwc", None)
+        if logits is None:
+            raise ops._abi.WsmgError("semantic_prediction: no forward pass has parked semantic logits yet (net.sem_logits_nhwc is None)")
+        return ops.sem_confusion(logits, None, SEM_CLASSES, want_pred=True)[2]
+
     # -- rollout -------------------------------------------------------------------
     def update_map(self, observations, masks):
         _, proj = self.net.rgb_encoder(observations)

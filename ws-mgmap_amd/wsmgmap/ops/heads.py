@@ -149,6 +149,69 @@ def cls_tail(y2, stats, bn, conv1x1, gt=None):
                           w.contiguous(), b, None if gt is None else gt.contiguous())
 
 
+# ----------------------------------------------------------------------------- scoring the semantic-map head
+NO_PRED = 255     # `pred` of a pixel without a prediction: a NaN among its class logits, or a masked-out row
+
+
+@torch.no_grad()
+def sem_confusion(logits_nhwc, gt, classes, confusion=None, ignored=None, row_mask=None, want_pred=False):
+    """-> (confusion int64 [classes, classes], ignored int64 [2], pred uint8 [B, H, W] or None): one launch (csrc/wsmg_sem_eval.hip)
+    over the NHWC logits [B, H, W, 32] (float32 or bf16, channels >= classes padding) and gt float32 [B, Hg, Wg].
+    confusion[label][prediction] counts the pixels whose prediction — the argmax over the first `classes` channels, ties to the
+    lowest index — meets the label `F.interpolate(gt.unsqueeze(1), size=(H, W)).long()` (policy.py:61-66 of the reference).
+    ignored[0]: pixels whose label is outside [0, classes) — judged on the float, so NaN and +-Inf are outside and -0.5 is a valid 0 —;
+    ignored[1]: pixels with a valid label and a NaN among their class logits (pred = NO_PRED).  Neither enters the matrix.
+    `confusion` / `ignored` passed in are ACCUMULATED into (and returned); they are allocated and zeroed only when not passed.
+    row_mask [B] bool or uint8: rows with 0 contribute nothing and get pred = NO_PRED.  Exact: no arithmetic touches the logits.
+    gt=None is the prediction-only use: (None, None, pred), nothing is counted."""
+    _req(logits_nhwc, gt, confusion, ignored, row_mask)
+    classes = int(classes)
+    if logits_nhwc.dim() != 4 or logits_nhwc.shape[-1] != 32 or not 1 <= classes <= 32:
+        raise _abi.WsmgError("sem_confusion: logits [B, H, W, 32] (padded classes), 1 <= classes <= 32")
+    B, H, W, _ = logits_nhwc.shape
+    dev = logits_nhwc.device
+    if row_mask is not None:
+        if row_mask.dtype not in (torch.bool, torch.uint8) or row_mask.numel() != B:
+            raise _abi.WsmgError(f"sem_confusion: row_mask must be bool or uint8 with one entry per row ({B})")
+    if gt is None:
+        if confusion is not None or ignored is not None:
+            raise _abi.WsmgError("sem_confusion: without gt nothing is counted (the prediction-only use takes no confusion / ignored)")
+        Hg = Wg = 0
+        want_pred = True
+    else:
+        _f32(gt)
+        if gt.dim() != 3 or gt.shape[0] != B:
+            raise _abi.WsmgError(f"sem_confusion: ground truth [B, Hg, Wg] float32 with B = {B}, got {tuple(gt.shape)}")
+        Hg, Wg = gt.shape[1], gt.shape[2]
+        if confusion is None:
+            confusion = torch.zeros(classes, classes, device=dev, dtype=torch.int64)
+        if ignored is None:
+            ignored = torch.zeros(2, device=dev, dtype=torch.int64)
+        if confusion.dtype != torch.int64 or confusion.shape != (classes, classes) or ignored.dtype != torch.int64 or ignored.numel() != 2:
+            raise _abi.WsmgError("sem_confusion: confusion int64 [classes, classes] and ignored int64 [2]")
+    pred = torch.empty(B, H, W, device=dev, dtype=torch.uint8) if want_pred else None
+    _abi.call("wsmg_sem_confusion" + (_sfx(logits_nhwc) or "_f32"), _p(logits_nhwc), classes, _p(gt), Hg, Wg, B, H, W, _p(row_mask),
+              _p(confusion), _p(ignored), _p(pred), _stream())
+    return confusion, ignored, pred
+
+
+@torch.no_grad()
+def sem_scores(confusion, out=None):
+    """-> float64 [3 + 3 classes] on the device, one launch: pixels counted, pixel accuracy, mIoU, then per class IoU, ground-truth
+    pixels, predicted pixels, from an int64 confusion matrix [classes, classes] (rows: labels).  A class with no pixel on either
+    side has IoU NaN and is left out of the mIoU; NaN accuracy / mIoU for an empty matrix.  `out`: a float64 vector to write into."""
+    _req(confusion, out)
+    classes = confusion.shape[0] if confusion.dim() == 2 else 0
+    if confusion.dtype != torch.int64 or confusion.dim() != 2 or confusion.shape[1] != classes or not 1 <= classes <= 32:
+        raise _abi.WsmgError("sem_scores: confusion int64 [classes, classes], 1 <= classes <= 32")
+    if out is None:
+        out = torch.empty(3 + 3 * classes, device=confusion.device, dtype=torch.float64)
+    elif out.dtype != torch.float64 or out.numel() != 3 + 3 * classes:
+        raise _abi.WsmgError("sem_scores: out must be float64 [3 + 3 classes]")
+    _abi.call("wsmg_sem_scores", _p(confusion), classes, _p(out), _stream())
+    return out
+
+
 # ----------------------------------------------------------------------------- update-path heads, auxiliary reduction, trainer loss
 class _UpdateHeads(torch.autograd.Function):
     """(pred [B,A], prog [B,1], progress-loss rows [B]) of the update path in one launch per direction (csrc/wsmg_heads.hip):
