@@ -772,9 +772,11 @@ template <class T>
 int upsample_bwd_t(const T* dy, T* dx, int B, int H, int W, int C, wsmg_stream_t stream, int64_t ld_dy = 0) {
   if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3)) return WSMG_EINVAL;
   if (ld_dy == 0) ld_dy = C;
-  if (ld_dy < C || (ld_dy & 7) || ((uintptr_t)dy & 15)) return WSMG_EINVAL;
+  // the 4-channel kernel reads 4 elements at a time, so a pixel stride of 4 k will do (a contiguous dy of 4, 12 or 20 channels, which
+  // the forward pass accepts, was refused here while this asked for 8 k); only the 8-channel kernel needs 8 k
+  if (ld_dy < C || (ld_dy & 3) || ((uintptr_t)dy & 15)) return WSMG_EINVAL;
   if constexpr (std::is_same<T, bf16_t>::value) {
-    if ((C & 7) == 0 && ((uintptr_t)dx & 15) == 0) {
+    if ((C & 7) == 0 && (ld_dy & 7) == 0 && ((uintptr_t)dx & 15) == 0) {
       hipLaunchKernelGGL(upsample_bwd8_kernel, dim3(sgrid((int64_t)B * H * W * C / 8)), dim3(256), 0, wsmg_s(stream), dy, dx, B, H, W, C, ld_dy);
       WSMG_RETURN_LAUNCH();
     }
