@@ -834,6 +834,55 @@ int wsmg_sem_confusion_f32(const float* logits, int classes, const float* gt, in
 int wsmg_sem_confusion_bf16(const void* logits, int classes, const float* gt, int Hg, int Wg, int B, int H, int W,
                             const uint8_t* row_mask, int64_t* confusion, int64_t* ignored, uint8_t* pred, wsmg_stream_t stream);
 int wsmg_sem_scores(const int64_t* confusion, int classes, double* scores, wsmg_stream_t stream);
+/* ---- scoring the waypoint attention, the action mean and the progress head (csrc/wsmg_nav_eval.hip) ---------------------------
+ * Not a reference operator: the reference reports the contrastive monitor's KL, the DAgger loss and the progress monitor's MSE only
+ * (policy.py:72-88, dagger_trainer.py:526-534).
+ * wsmg_nav_rows: one launch, one workgroup per row, writes rows float64 [B][WSMG_NAV_ROW].  Three input groups, each NULL as a
+ * whole (absent); row_mask uint8 [B] or NULL (every row).  Every group of a row has a state field: WSMG_NAV_ABSENT (0: the group
+ * is NULL or row_mask[b] == 0 — "not counted"), WSMG_NAV_COUNTED (1) or WSMG_NAV_INVALID (2); in the first and the last case every
+ * other field of the group is NaN.
+ *   attention  att float32 [B][S*S], dis float32 [B][H][W] (H < S, W < S legal).
+ *              target cell = argmin over the S x S cells of the area-resized dis: the window of cell i along an axis of length L is
+ *                [floor(i*L/S), ceil((i+1)*L/S)) (F.interpolate(mode="area") of policy.py:76), summed in float32 in row-major
+ *                order and divided by its count in float32; a NaN mean (+Inf and -Inf in one window) ranks as +Inf; ties to the
+ *                lowest index.  The reference's target softmax((hi - dis) / (hi - lo) / tau) is monotone decreasing in the resized
+ *                dis: its argmax is this argmin, an exact integer, no batch-global extremes;
+ *              peak cell = argmax of att, ties to the lowest index (-0.0 ties +0.0);
+ *              fields: TARGET, PEAK (row-major cell indices), CHEB = max(|dy|, |dx|) and EUCLID = sqrt(dy^2 + dx^2) between them in
+ *                cells, MASS = the attention within Chebyshev distance 1 of the target, clipped at the map edge, summed in float64
+ *                in row-major order, ENTROPY = -sum a log a in float64 with 0 log 0 = 0 (per-thread partials over cells 256 apart, a
+ *                wave butterfly, the four waves in order: fixed, so repeatable);
+ *              INVALID: any att value NaN or negative, or any dis value of the row NaN.
+ *   action     pred float32 [B][A], 1 <= A <= 4; waypoint rows ld_waypoint >= A floats apart (as wsmg_dagger_loss_fwd takes them).
+ *              e_j = tanh((double)pred_j) - (double)waypoint_j; fields: SQ = sum e^2, L2 = sqrt(SQ), ABS + j = |e_j| (0 for j >= A);
+ *              INVALID: a non-finite pred_j or waypoint_j — every non-finite e, and an infinite pred, which tanh would saturate
+ *              to a finite e.
+ *   progress   prog, progress float32 [B]; d = (double)prog - (double)progress; fields: ABS = |d|, SQ = d^2, STOP =
+ *              2 * (progress >= stop_threshold) + (prog >= stop_threshold), compared as float32;
+ *              INVALID: a non-finite prog or progress.
+ * wsmg_nav_accumulate: one launch, one workgroup; folds rows into counts int64 [WSMG_NAV_COUNTS] and sums float64 [WSMG_NAV_SUMS],
+ * both ACCUMULATED into (the caller zeroes them once).  counts: per group the COUNTED and the INVALID rows; the attention rows with
+ * CHEB <= 0, <= 1, <= 2; the COUNTED progress rows by STOP code (WSMG_NAV_N_STOP + code: a 2 x 2 matrix, rows progress >= threshold,
+ * columns prog >= threshold).  sums, over the COUNTED rows of the field's group: CHEB, EUCLID, MASS, ENTROPY, SQ, L2, ABS + 0..3,
+ * ABS, SQ of the progress group, in this order.  Every sum continues from the stored value and adds row 0, 1, ... B-1 in order, no
+ * atomics: two runs on the same rows give the same bits.
+ * Both: no allocation, no synchronisation, re-entrant across streams, plain vector stores only.
+ * WSMG_EINVAL before anything is enqueued: wsmg_nav_rows — NULL rows; B <= 0; S <= 0 or S*S > 4096; att without dis or the reverse
+ * (likewise pred / waypoint and prog / progress); H or W <= 0 or H*W >= 2^31 with dis; A outside [1, 4] or ld_waypoint < A with
+ * pred.  All three groups NULL is legal (every state ABSENT).  wsmg_nav_accumulate — NULL rows, counts or sums; B <= 0. */
+#define WSMG_NAV_ROW 18
+enum { WSMG_NAV_ABSENT = 0, WSMG_NAV_COUNTED = 1, WSMG_NAV_INVALID = 2 };
+enum { WSMG_NAV_ATT_STATE = 0, WSMG_NAV_ATT_TARGET = 1, WSMG_NAV_ATT_PEAK = 2, WSMG_NAV_ATT_CHEB = 3, WSMG_NAV_ATT_EUCLID = 4,
+       WSMG_NAV_ATT_MASS = 5, WSMG_NAV_ATT_ENTROPY = 6, WSMG_NAV_ACT_STATE = 7, WSMG_NAV_ACT_SQ = 8, WSMG_NAV_ACT_L2 = 9,
+       WSMG_NAV_ACT_ABS = 10, WSMG_NAV_PROG_STATE = 14, WSMG_NAV_PROG_ABS = 15, WSMG_NAV_PROG_SQ = 16, WSMG_NAV_PROG_STOP = 17 };
+#define WSMG_NAV_COUNTS 13
+#define WSMG_NAV_SUMS 12
+enum { WSMG_NAV_N_ATT = 0, WSMG_NAV_N_ATT_INVALID = 1, WSMG_NAV_N_HIT0 = 2, WSMG_NAV_N_ACT = 5, WSMG_NAV_N_ACT_INVALID = 6,
+       WSMG_NAV_N_PROG = 7, WSMG_NAV_N_PROG_INVALID = 8, WSMG_NAV_N_STOP = 9 };
+int wsmg_nav_rows(const float* att, const float* dis, int S, int H, int W, const float* pred, const float* waypoint,
+                  int ld_waypoint, int A, const float* prog, const float* progress, float stop_threshold, const uint8_t* row_mask,
+                  int B, double* rows, wsmg_stream_t stream);
+int wsmg_nav_accumulate(const double* rows, int B, int64_t* counts, double* sums, wsmg_stream_t stream);
 /* BatchNorm2d (train mode) in halves (torch.nn.BatchNorm2d behind map_encoder.py:10-12 / mg_map_policy.py:80-84): statistics from
  * the slabs a convolution's epilogue filled (wsmg_conv2d_fwd_bf16_stats) -> save_mean, save_invstd, running statistics (slabs
  * returned zeroed); and the backward's apply pass alone, for a dy already masked by the ReLU and caller-supplied sums. */

@@ -116,6 +116,10 @@ _SIG["wsmg_cls_tail_bwd_bf16"] = [c_p] * 7 + [c_i, c_p, c_i, c_i, c_p, c_p, c_i,
 _SIG["wsmg_sem_confusion_f32"] = [c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]
 _SIG["wsmg_sem_confusion_bf16"] = list(_SIG["wsmg_sem_confusion_f32"])
 _SIG["wsmg_sem_scores"] = [c_p, c_i, c_p, c_p]
+# scoring the waypoint attention, the action mean and the progress head (csrc/wsmg_nav_eval.hip): a float64 record per row, then the
+# row-ordered fold into counts and sums
+_SIG["wsmg_nav_rows"] = [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_f, c_p, c_i, c_p, c_p]
+_SIG["wsmg_nav_accumulate"] = [c_p, c_i, c_p, c_p, c_p]
 _SIG["wsmg_bn_stats_finalize"] = [c_p, c_i, c_i, c_l, c_f, c_f, c_p, c_p, c_p, c_p, c_p]
 _SIG["wsmg_bn_bwd_apply_bf16"] = [c_p] * 7 + [c_l, c_i, c_p, c_p]
 _SIG["wsmg_attn_fp8_mfma_fwd"] = [c_p] * 9 + [c_f, c_i, c_i, c_i, c_i, c_p, c_p, c_p]

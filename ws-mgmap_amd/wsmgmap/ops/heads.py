@@ -212,6 +212,88 @@ def sem_scores(confusion, out=None):
     return out
 
 
+# ----------------------------------------------------------------------------- scoring the attention, action and progress heads
+# the row record and the accumulator block of csrc/wsmg_nav_eval.hip, as include/wsmgmap.h names them
+NAV_ROW, NAV_COUNTS, NAV_SUMS = 18, 13, 12
+NAV_ABSENT, NAV_COUNTED, NAV_INVALID = 0, 1, 2
+NAV_FIELDS = dict(att_state=0, att_target=1, att_peak=2, att_cheb=3, att_euclid=4, att_mass=5, att_entropy=6, act_state=7, act_sq=8,
+                  act_l2=9, act_abs=10, prog_state=14, prog_abs=15, prog_sq=16, prog_stop=17)
+NAV_SUM_FIELDS = (3, 4, 5, 6, 8, 9, 10, 11, 12, 13, 15, 16)          # the row field behind sums[k]
+NAV_N = dict(att=0, att_invalid=1, hit0=2, act=5, act_invalid=6, prog=7, prog_invalid=8, stop=9)
+
+
+@torch.no_grad()
+def nav_rows(att=None, dis=None, S=0, pred=None, waypoint=None, prog=None, progress=None, row_mask=None, stop_threshold=0.8,
+             out=None, B=None):
+    """-> rows float64 [B, NAV_ROW], one launch (csrc/wsmg_nav_eval.hip), one record per row of three groups, each given as a
+    pair or left None (absent):
+      attention  att float32 [B, S*S] against dis float32 [B, H, W]: the target cell (argmin of the area-resized dis, the argmax of
+                 the contrastive monitor's target), the attention's peak cell, their Chebyshev / Euclidean distance in cells, the
+                 attention mass within one cell of the target, the entropy;
+      action     pred float32 [B, A <= 4] against waypoint float32 [B, >= A]: sum e^2, its root and |e_j| of e = tanh(pred) - waypoint;
+      progress   prog / progress float32 with B elements: |d|, d^2 and the stop code 2 (progress >= thr) + (prog >= thr).
+    Field positions: NAV_FIELDS; each group's state field is NAV_COUNTED, NAV_INVALID (NaN / negative attention, NaN in dis,
+    non-finite pred / waypoint / prog / progress) or NAV_ABSENT (group not given, or row_mask[b] == 0), the group's other fields NaN
+    unless counted.  row_mask [B] bool or uint8.  B is read from the first tensor given (`B=` with none); `out`: a record to write."""
+    _req(att, dis, pred, waypoint, prog, progress, row_mask, out)
+    _f32(att, dis, pred, waypoint, prog, progress)
+    given = [t for t in (att, dis, pred, waypoint, prog, progress) if t is not None]
+    if (att is None) != (dis is None) or (pred is None) != (waypoint is None) or (prog is None) != (progress is None):
+        raise _abi.WsmgError("nav_rows: att / dis, pred / waypoint and prog / progress come in pairs")
+    if given:
+        B = given[0].shape[0] if given[0].dim() else 0
+    elif B is None:
+        B = out.shape[0] if out is not None and out.dim() == 2 else 0
+    B, S = int(B), int(S)
+    if B <= 0:
+        raise _abi.WsmgError("nav_rows: no rows (with no group given, pass B or out)")
+    H = W = A = ld = 0
+    if att is not None:
+        if not 1 <= S <= 64 or att.dim() != 2 or tuple(att.shape) != (B, S * S) or dis.dim() != 3 or dis.shape[0] != B or dis.numel() == 0:
+            raise _abi.WsmgError(f"nav_rows: attention [B, S*S] (1 <= S <= 64) and dis [B, H, W] with B = {B}, S = {S}, got "
+                                 f"{tuple(att.shape)} and {tuple(dis.shape)}")
+        H, W = dis.shape[1], dis.shape[2]
+    else:
+        S = S if 1 <= S <= 64 else 1
+    if pred is not None:
+        A = pred.shape[-1] if pred.dim() == 2 else 0
+        if pred.dim() != 2 or pred.shape[0] != B or not 1 <= A <= 4 or waypoint.dim() != 2 or waypoint.shape[0] != B or waypoint.shape[1] < A:
+            raise _abi.WsmgError(f"nav_rows: pred [B, A <= 4] and waypoint [B, >= A] with B = {B}, got {tuple(pred.shape)} and "
+                                 f"{tuple(waypoint.shape)}")
+        ld = waypoint.shape[1]
+    if prog is not None and (prog.numel() != B or progress.numel() != B):
+        raise _abi.WsmgError(f"nav_rows: prog and progress with {B} elements, got {tuple(prog.shape)} and {tuple(progress.shape)}")
+    if row_mask is not None and (row_mask.dtype not in (torch.bool, torch.uint8) or row_mask.numel() != B):
+        raise _abi.WsmgError(f"nav_rows: row_mask must be bool or uint8 with one entry per row ({B})")
+    if out is None:
+        dev = given[0].device if given else (row_mask.device if row_mask is not None else torch.device("cuda"))
+        out = torch.empty(B, NAV_ROW, device=dev, dtype=torch.float64)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (B, NAV_ROW):
+        raise _abi.WsmgError(f"nav_rows: out must be float64 [{B}, {NAV_ROW}], got {out.dtype} {tuple(out.shape)}")
+    _abi.call("wsmg_nav_rows", _p(att), _p(dis), S, H, W, _p(pred), _p(waypoint), ld, A, _p(prog), _p(progress), float(stop_threshold),
+              _p(row_mask), B, _p(out), _stream())
+    return out
+
+
+@torch.no_grad()
+def nav_accumulate(rows, counts=None, sums=None):
+    """-> (counts int64 [NAV_COUNTS], sums float64 [NAV_SUMS]): one launch, one workgroup, folds a `nav_rows` record into the
+    counts (NAV_N: counted and invalid rows per group, attention hits at Chebyshev distance <= 0 / 1 / 2, the 2 x 2 stop confusion)
+    and the sums of the float fields (NAV_SUM_FIELDS) over each group's counted rows.  Both are ACCUMULATED into when passed (and
+    allocated zeroed when not); every sum continues from its stored value and adds the rows in order, so it is repeatable to the bit."""
+    _req(rows, counts, sums)
+    if rows.dtype != torch.float64 or rows.dim() != 2 or rows.shape[1] != NAV_ROW or rows.shape[0] == 0:
+        raise _abi.WsmgError(f"nav_accumulate: rows float64 [B, {NAV_ROW}], got {rows.dtype} {tuple(rows.shape)}")
+    if counts is None:
+        counts = torch.zeros(NAV_COUNTS, device=rows.device, dtype=torch.int64)
+    if sums is None:
+        sums = torch.zeros(NAV_SUMS, device=rows.device, dtype=torch.float64)
+    if counts.dtype != torch.int64 or counts.numel() != NAV_COUNTS or sums.dtype != torch.float64 or sums.numel() != NAV_SUMS:
+        raise _abi.WsmgError(f"nav_accumulate: counts int64 [{NAV_COUNTS}] and sums float64 [{NAV_SUMS}]")
+    _abi.call("wsmg_nav_accumulate", _p(rows), rows.shape[0], _p(counts), _p(sums), _stream())
+    return counts, sums
+
+
 # ----------------------------------------------------------------------------- update-path heads, auxiliary reduction, trainer loss
 class _UpdateHeads(torch.autograd.Function):
     """(pred [B,A], prog [B,1], progress-loss rows [B]) of the update path in one launch per direction (csrc/wsmg_heads.hip):
