@@ -206,7 +206,9 @@ def test_attention_fwd_bwd(ops, masked):
 
 
 def test_attention_map_sized(ops):
-    """I = 576 map cells, no mask, B = 9 (the map-attention call site)."""
+    """I = 576 map cells, no mask, B = 9: the map-attention call site's shape on the GENERIC kernels — `kv.cuda()` twice makes two
+    device tensors, and wsmg_attn_fwd takes the keys-are-values kernel only where k and v are one pointer.  That kernel at the
+    map's sizes (up to 2304 and 2560 tokens) is held by tests/test_gpu_attn_edges.py."""
     q = T(df.uniform("attn2.q", (9, 256), 6.0))
     kv = T(df.uniform("attn2.kv", (9, 576, 256), 3.0))
     o_ref, a_ref = policy_ref.attn(q.double(), kv.double().permute(0, 2, 1), kv.double().permute(0, 2, 1))
