@@ -1,13 +1,9 @@
 """CPU: the host side of the per-tensor gradient report — wsmgmap.optim.Adam(grad_report=True), `grad_report()`, `last_skipped()`,
 wsmgmap.optim.grad_stats — the two entry points in the header and the binding, the constructor's refusals, and a default construction
 that holds nothing new.  The kernels, the latch and the graph replay are tested in tests/test_gpu_adam_grad_report.py."""
-import os
-import re
-
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("wsmg_grad_report_multi", "wsmg_grad_stats_multi")
 
 
@@ -16,12 +12,11 @@ def _param(n=5):
 
 
 def test_entry_points_are_declared_bound_and_exported():
+    """(Their declarations against the binding: tests/test_abi_cpu.py.)"""
     from wsmgmap import _abi
-    header = open(os.path.join(ROOT, "include", "wsmgmap.h")).read()
-    declared = set(re.findall(r"\b(wsmg_[a-z0-9_]+)\s*\(", header))
     L = _abi.lib()
     for name in NAMES:
-        assert name in declared and name in _abi.exported_names() and hasattr(L, name)
+        assert name in _abi.exported_names() and hasattr(L, name)
     assert len(getattr(L, NAMES[0]).argtypes) == 11 and len(getattr(L, NAMES[1]).argtypes) == 8
     assert L.wsmg_abi_version() == 1
 

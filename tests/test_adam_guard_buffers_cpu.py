@@ -4,13 +4,10 @@ unsupported argument with WSMG_EINVAL before anything is enqueued (no GPU is pre
 own); the constructor's checks; and a construction without the option holds nothing of it.  The kernel and the optimizer's device
 side are tested in tests/test_gpu_adam_guard_buffers.py."""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL = -1
 NAME = "wsmg_copy_multi_guarded"
 A, B, G = 1 << 20, 2 << 20, 3 << 20        # dummy addresses: never dereferenced, every call below is refused
@@ -25,13 +22,8 @@ def _descs(*rows):
 
 
 def test_entry_point_is_exported_declared_and_bound():
+    """(The declaration's own words — a WsmgCopyDesc list, a count, a float guard record, the stream: tests/test_abi_cpu.py.)"""
     from wsmgmap import _abi
-    header = open(os.path.join(ROOT, "include", "wsmgmap.h")).read()
-    m = re.search(r"\bint\s+" + NAME + r"\s*\(([^)]*)\)\s*;", header)
-    assert m, f"{NAME} is not declared in include/wsmgmap.h"
-    params = [p.strip() for p in m.group(1).split(",")]
-    assert [("*" in p or p.startswith("wsmg_stream_t")) for p in params] == [True, False, True, True]
-    assert params[0].startswith("const WsmgCopyDesc*") and params[1].startswith("int ") and params[2].startswith("const float*")
     assert _abi._SIG[NAME] == [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     L = _abi.lib()
     assert NAME in _abi.exported_names() and hasattr(L, NAME)

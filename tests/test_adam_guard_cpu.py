@@ -1,13 +1,9 @@
 """CPU: the host side of the guarded Adam step (wsmgmap.optim.Adam(max_grad_norm=..., skip_nonfinite=...)): constructor
 validation, no device state for a default construction, torch.optim.Adam's state_dict layout with the options on, and the two
 entry points in the header and the binding.  The kernels are tested in tests/test_gpu_adam_guard.py."""
-import os
-import re
-
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("wsmg_grad_norm_multi", "wsmg_adam_step_multi_guarded")
 
 
@@ -68,10 +64,9 @@ def test_state_dict_layout_is_torch_adams_with_the_options_on():
 
 
 def test_entry_points_are_declared_bound_and_exported():
+    """(Their declarations against the binding: tests/test_abi_cpu.py.)"""
     from wsmgmap import _abi
-    header = open(os.path.join(ROOT, "include", "wsmgmap.h")).read()
-    declared = set(re.findall(r"\b(wsmg_[a-z0-9_]+)\s*\(", header))
     L = _abi.lib()
     for name in NAMES:
-        assert name in declared and name in _abi.exported_names() and hasattr(L, name)
+        assert name in _abi.exported_names() and hasattr(L, name)
     assert L.wsmg_abi_version() == 1

@@ -2,13 +2,9 @@
 captured in a HIP graph follows schedules: the two entry points in the header and the binding, the constructor's and the
 `max_grad_norm` setter's refusals, and a default construction that is the object it was.  The kernels, `sync_hyper()` and the graph
 replay are tested in tests/test_gpu_adam_hyper.py."""
-import os
-import re
-
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("wsmg_adam_step_multi_hyper", "wsmg_grad_norm_multi_hyper")
 
 
@@ -17,16 +13,13 @@ def _param(n=5):
 
 
 def test_entry_points_are_declared_bound_and_exported():
+    """(Their declarations against the binding, and the record's layout documented next to the guard record's: tests/test_abi_cpu.py.)"""
     from wsmgmap import _abi
-    header = open(os.path.join(ROOT, "include", "wsmgmap.h")).read()
-    declared = set(re.findall(r"\b(wsmg_[a-z0-9_]+)\s*\(", header))
     L = _abi.lib()
     for name in NAMES:
-        assert name in declared and name in _abi.exported_names() and hasattr(L, name)
+        assert name in _abi.exported_names() and hasattr(L, name)
     assert len(getattr(L, NAMES[0]).argtypes) == 6 and len(getattr(L, NAMES[1]).argtypes) == 9
     assert L.wsmg_abi_version() == 1
-    # the record's layout is documented next to the guard record's
-    assert "{lr, beta1, beta2, eps, weight_decay, 0, 0, 0}" in header and header.index("guard[0] norm") < header.index("{lr, beta1,")
 
 
 def test_hyper_on_device_needs_a_step_count_on_the_device():

@@ -2,12 +2,9 @@
 the shared-set fp8 attention's backward (wsmg_attn_fp8_mfma_bwd): declared, exported, and refusing invalid arguments with WSMG_EINVAL
 before anything is enqueued.  The kernels are tested on the GPU (tests/test_gpu_attn_fp8_shared_bwd.py, test_gpu_fp8_text_attention.py)."""
 import ctypes
-import os
-import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL = -1
 NAME = "wsmg_attn_fp8_mfma_bwd"
 
@@ -55,15 +52,9 @@ def test_policy_carries_the_option_and_the_recurrent_gate_refuses_fp8():
 
 
 def test_backward_entry_point_is_declared_and_exported():
+    """(Every argument against the header's declaration, the stream last: tests/test_abi_cpu.py.)"""
     from wsmgmap import _abi
-    header = open(os.path.join(ROOT, "include", "wsmgmap.h")).read()
-    m = re.search(r"\bint\s+" + NAME + r"\s*\(([^)]*)\)\s*;", header)
-    assert m, f"{NAME} is not declared in include/wsmgmap.h"
-    params = [p.strip() for p in m.group(1).split(",")]
-    kinds = [ctypes.c_void_p if ("*" in p or p.startswith("wsmg_stream_t")) else ctypes.c_float if p.startswith("float ") else ctypes.c_int
-             for p in params]
-    assert _abi._SIG[NAME] == kinds
-    assert params[-1].startswith("wsmg_stream_t")
+    assert len(_abi._SIG[NAME]) == 22 and _abi._RESTYPE[NAME] is ctypes.c_int
     assert NAME in _abi.exported_names()
 
 

@@ -3,13 +3,10 @@ every refused argument (the checks precede the first launch, so no GPU is needed
 SemanticMapMeter.scores_from, the documented host form of the scores.  The kernels are tested in tests/test_gpu_sem_eval.py."""
 import ctypes
 import math
-import os
-import re
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL = -1
 NAMES = ("wsmg_sem_confusion_f32", "wsmg_sem_confusion_bf16", "wsmg_sem_scores")
 
@@ -26,18 +23,13 @@ def _confusion(L, name, **over):
 
 
 def test_entry_points_are_declared_bound_and_exported():
+    """(Their declarations against the binding: tests/test_abi_cpu.py.)"""
     from wsmgmap import _abi
-    header = open(os.path.join(ROOT, "include", "wsmgmap.h")).read()
-    declared = set(re.findall(r"\b(wsmg_[a-z0-9_]+)\s*\(", header))
     L = _abi.lib()
     for name in NAMES:
-        assert name in declared and name in _abi.exported_names() and hasattr(L, name)
+        assert name in _abi.exported_names() and hasattr(L, name)
         assert list(getattr(L, name).argtypes) == list(_abi._SIG[name]) and getattr(L, name).restype is ctypes.c_int
     assert len(_abi._SIG[NAMES[0]]) == 13 and _abi._SIG[NAMES[1]] == _abi._SIG[NAMES[0]] and len(_abi._SIG[NAMES[2]]) == 4
-    # the declared parameter lists have the bound lengths
-    for name in NAMES:
-        params = re.search(r"\bint %s\(([^;]*)\);" % name, header).group(1)
-        assert len(params.split(",")) == len(_abi._SIG[name]), name
     assert L.wsmg_abi_version() == 1
 
 

@@ -3,207 +3,82 @@
 This is the only place the shared library is touched.  There is NO fallback: if the
 library is missing, or a call returns non-zero, a WsmgError is raised — the product path
 never silently degrades to PyTorch or CPU code.
+
+No signature is written here: argtypes, restypes and the descriptor structures are read from the header's declarations, which
+the compiler holds to the definitions (every .hip file includes the header).  A new entry point needs nothing in this file.
 """
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libwsmgmap.so")
 if os.environ.get("WSMG_LIB"):       # experiments only: another build of the same library (read once, here)
     LIB_PATH = os.environ["WSMG_LIB"]
-
-c_p = ctypes.c_void_p
-c_i = ctypes.c_int
-c_l = ctypes.c_int64
-c_f = ctypes.c_float
+HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "wsmgmap.h")   # the checkout's; also for a WSMG_LIB
 
 
 class WsmgError(RuntimeError):
     pass
 
 
-class CopyDesc(ctypes.Structure):         # WsmgCopyDesc of include/wsmgmap.h
-    _fields_ = [("dst", ctypes.c_void_p), ("src", ctypes.c_void_p), ("bytes", ctypes.c_longlong)]
+# The binding is derived from the header: the closed tables of the types the ABI uses.  Anything else is an error, never a guess.
+_VALUE_TYPES = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "unsigned": ctypes.c_uint, "uint32_t": ctypes.c_uint,
+                "float": ctypes.c_float, "double": ctypes.c_double, "int64_t": ctypes.c_int64, "long long": ctypes.c_longlong,
+                "wsmg_stream_t": ctypes.c_void_p}
+_RETURN_TYPES = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "long long": ctypes.c_longlong, "const char*": ctypes.c_char_p}
 
 
-class RelayoutDesc(ctypes.Structure):     # WsmgRelayoutDesc of include/wsmgmap.h
-    _fields_ = [("w_oihw", c_p), ("w_ohwi", c_p), ("w_ihwo", c_p), ("O", c_i), ("I", c_i), ("KH", c_i), ("KW", c_i),
-                ("I_pad", c_i), ("reserved", c_i)]
+def _ctype(decl, where):
+    """The ctypes type of one `TYPE name` declaration: every pointer is a void pointer, a value type comes from the table."""
+    if "*" in decl:
+        return ctypes.c_void_p
+    ty = " ".join(decl.split()[:-1])
+    if ty not in _VALUE_TYPES:
+        raise WsmgError(f"{HEADER_PATH}: `{decl}` in {where} has a type outside the binding's table {sorted(_VALUE_TYPES)}")
+    return _VALUE_TYPES[ty]
 
 
-class ColsumDesc(ctypes.Structure):       # WsmgColsumDesc of include/wsmgmap.h (round 6)
-    _fields_ = [("x", c_p), ("out", c_p), ("rows", c_i), ("cols", c_i)]
+def parse_header(text):
+    """(name -> argtypes, name -> restype, struct name -> ctypes fields) of every `RET wsmg_name(PARAMS);` and every
+    `typedef struct { ... } Name;` of a header written as include/wsmgmap.h is."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    structs = {}
+    for body, name in re.findall(r"typedef\s+struct\s*\{(.*?)\}\s*(\w+)\s*;", text, flags=re.S):
+        fields = structs[name] = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            first, *more = (d.strip() for d in decl.split(","))          # `int rows, cols`: the names after the first share its type
+            if "*" in decl and more:
+                raise WsmgError(f"{HEADER_PATH}: `{decl}` in {name} declares several pointers at once")
+            fields += [(n.split()[-1].lstrip("*"), _ctype(first, name)) for n in [first] + more]
+    text = re.sub(r"typedef\s+struct\s*\{.*?\}\s*\w+\s*;", " ", text, flags=re.S)
+    sig, restype = {}, {}
+    for stmt in text.split(";"):
+        if "(" not in stmt:
+            continue                                                     # extern "C" {, typedef void* wsmg_stream_t, }
+        m = re.fullmatch(r"\s*([\w\s*]+?)\s*\b(wsmg_\w+)\s*\(([^()]*)\)\s*", stmt)
+        ret = re.sub(r"\s*\*", "*", " ".join(m.group(1).split())) if m else None
+        if ret not in _RETURN_TYPES:
+            raise WsmgError(f"{HEADER_PATH}: `{' '.join(stmt.split())}` is not a declaration returning one of {sorted(_RETURN_TYPES)}")
+        params = [" ".join(p.split()) for p in m.group(3).split(",")]
+        sig[m.group(2)] = [] if params == ["void"] else [_ctype(p, m.group(2)) for p in params]
+        restype[m.group(2)] = _RETURN_TYPES[ret]
+    return sig, restype, structs
 
 
-# name -> argtypes (all return int unless listed in _RESTYPE)
-_SIG = {
-    "wsmg_abi_version": [],
-    "wsmg_build_info": [],
-    "wsmg_bev_index": [c_p, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_f, c_p, c_p],
-    "wsmg_bev_scatter_max": [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p],
-    "wsmg_bev_rotate": [c_p, c_p, c_f, c_i, c_i, c_i, c_p, c_p],
-    "wsmg_map_fuse": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p],
-    "wsmg_map_retrieve": [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p],
-    "wsmg_map_retrieve_fused": [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p],
-    "wsmg_map_retrieve_tiled": [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p],
-    "wsmg_bev_scatter_rotate": [c_p, c_p, c_p, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p],
-    "wsmg_map_fuse_planes": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p],
-    "wsmg_conv2d_fwd": [c_p, c_p, c_p, c_p] + [c_i] * 11 + [c_p],
-    "wsmg_conv2d_bwd_data": [c_p, c_p, c_p] + [c_i] * 11 + [c_p],
-    "wsmg_conv2d_bwd_weight": [c_p, c_p, c_p] + [c_i] * 11 + [c_p],
-    "wsmg_channel_sum": [c_p, c_l, c_i, c_p, c_p, c_l, c_p],
-    "wsmg_channel_reduce_workspace_bytes": [c_l, c_i],
-    "wsmg_bn_act_fwd": [c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_i, c_i, c_l, c_i, c_p, c_p, c_p, c_p, c_l, c_p],
-    "wsmg_bn_act_bwd": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_l, c_p],
-    "wsmg_relu_fwd": [c_p, c_p, c_l, c_p],
-    "wsmg_relu_bwd": [c_p, c_p, c_p, c_l, c_p],
-    "wsmg_token_grad_merge": [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p],
-    "wsmg_maxpool3x3s2_fwd": [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p],
-    "wsmg_maxpool3x3s2_bwd": [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p],
-    "wsmg_upsample2x_fwd": [c_p, c_p, c_i, c_i, c_i, c_i, c_p],
-    "wsmg_upsample2x_bwd": [c_p, c_p, c_i, c_i, c_i, c_i, c_p],
-    "wsmg_avgpool2_fwd": [c_p, c_p, c_i, c_i, c_i, c_i, c_p],
-    "wsmg_avgpool2_bwd": [c_p, c_p, c_i, c_i, c_i, c_i, c_p],
-    "wsmg_nchw_to_nhwc": [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p],
-    "wsmg_nhwc_to_nchw": [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p],
-    "wsmg_attn_fwd": [c_p, c_p, c_p, c_p, c_f, c_i, c_i, c_i, c_p, c_p, c_p],
-    "wsmg_attn_bwd": [c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_i, c_i, c_i, c_p, c_p, c_p, c_p],
-}
-# bf16 storage variants: identical argument lists except the convs' extra `out_f32` int
-for _n in ["wsmg_token_grad_merge", "wsmg_channel_sum", "wsmg_bn_act_fwd", "wsmg_bn_act_bwd", "wsmg_relu_fwd", "wsmg_relu_bwd",
-           "wsmg_maxpool3x3s2_fwd", "wsmg_maxpool3x3s2_bwd", "wsmg_upsample2x_fwd", "wsmg_upsample2x_bwd",
-           "wsmg_avgpool2_fwd", "wsmg_avgpool2_bwd", "wsmg_nchw_to_nhwc", "wsmg_nhwc_to_nchw", "wsmg_attn_fwd",
-           "wsmg_attn_bwd", "wsmg_conv2d_bwd_weight"]:
-    _SIG[_n + "_bf16"] = list(_SIG[_n])
-_SIG["wsmg_conv2d_fwd_bf16"] = [c_p, c_p, c_p, c_p, c_i] + [c_i] * 11 + [c_p]
-_SIG["wsmg_conv2d_bwd_data_bf16"] = [c_p, c_p, c_p, c_i] + [c_i] * 11 + [c_p]
-_SIG["wsmg_conv_transpose2d_infer_bf16"] = [c_p, c_p, c_p, c_p, c_i] + [c_i] * 11 + [c_p]
-_SIG["wsmg_conv2d_splitk_plan"] = [c_i] * 7 + [c_p, c_p]
-_SIG["wsmg_conv2d_fwd_bf16_splitk"] = [c_p, c_p, c_p, c_p, c_i, c_i, c_p] + [c_i] * 11 + [c_p]
-_SIG["wsmg_conv2d_fwd_bf16_stats"] = [c_p, c_p, c_p, c_p, c_i, c_p, c_i] + [c_i] * 11 + [c_p]
-_SIG["wsmg_conv2d_bwd_data_bf16_stats"] = [c_p, c_p, c_p, c_i, c_p, c_i] + [c_i] * 11 + [c_p]
-_SIG["wsmg_bn_act_fwd_bf16_pre"] = [c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_i, c_l, c_i, c_p, c_p, c_p, c_p, c_i, c_p]
-_SIG["wsmg_attn_shared_fwd"] = [c_p, c_p, c_p, c_p, c_p, c_f, c_i, c_i, c_i, c_p, c_p, c_p]
-_SIG["wsmg_attn_shared_bwd"] = [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_i, c_i, c_i, c_p, c_p, c_p]
-_SIG["wsmg_attn_shared_fwd_bf16"] = list(_SIG["wsmg_attn_shared_fwd"])
-_SIG["wsmg_attn_shared_bwd_bf16"] = list(_SIG["wsmg_attn_shared_bwd"])
-_SIG["wsmg_attn_fp8_fold"] = [c_p, c_p, c_i, c_i, c_i, c_p, c_p]
-_SIG["wsmg_attn_fp8_splits"] = [c_i, c_i]
-_SIG["wsmg_attn_fp8_workspace_bytes"] = [c_i, c_i]
-_SIG["wsmg_attn_fp8_fwd"] = [c_p, c_p, c_p, c_p, c_f, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]
-_SIG["wsmg_attn_fp8_bwd"] = [c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_i, c_i, c_i, c_p, c_p, c_p]
-_SIG["wsmg_quantize_e4m3_dev"] = [c_p, c_l, c_p, c_p, c_p]
-_SIG["wsmg_quantize_e4m3"] = [c_p, c_l, c_f, c_p, c_p]
-_SIG["wsmg_weight_relayout"] = [c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p]
-_SIG["wsmg_weight_relayout_bf16"] = list(_SIG["wsmg_weight_relayout"])
-_SIG["wsmg_weight_relayout_multi"] = [c_p, c_i, c_i, c_p]
-_SIG["wsmg_weight_grad_to_oihw"] = [c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p]
-_SIG["wsmg_conv2d_bwd_weight_plan"] = [c_i] * 11 + [c_p, c_p]
-_SIG["wsmg_conv2d_bwd_weight_bf16_plan"] = list(_SIG["wsmg_conv2d_bwd_weight_plan"])
-_SIG["wsmg_conv2d_bwd_weight_slabs"] = [c_p, c_p, c_p, c_i, c_l] + [c_i] * 11 + [c_p]
-_SIG["wsmg_conv2d_bwd_weight_bf16_slabs"] = list(_SIG["wsmg_conv2d_bwd_weight_slabs"])
-_SIG["wsmg_weight_grad_reduce_oihw"] = [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p]
-_SIG["wsmg_update_heads_fwd"] = [c_p] * 6 + [c_i] * 3 + [c_p] * 3 + [c_p]
-_SIG["wsmg_update_heads_bwd"] = [c_p] * 8 + [c_i] * 3 + [c_p] * 5 + [c_p]
-_SIG["wsmg_aux_reduce_fwd"] = [c_p, c_p, c_i, c_p, c_i, c_p, c_p]
-_SIG["wsmg_aux_reduce_bwd"] = [c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_p]
-_SIG["wsmg_dagger_loss_fwd"] = [c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p]
-_SIG["wsmg_dagger_loss_bwd"] = [c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p]
-_SIG["wsmg_cls_tail_workspace_floats"] = [c_i]
-_SIG["wsmg_cls_tail_fwd_bf16"] = [c_p] * 7 + [c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]
-_SIG["wsmg_cls_tail_bwd_bf16"] = [c_p] * 7 + [c_i, c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_l, c_p, c_p, c_p, c_p, c_p]
-# scoring the semantic-map head (csrc/wsmg_sem_eval.hip): confusion counts per pixel, then accuracy / IoU / mIoU from the matrix
-_SIG["wsmg_sem_confusion_f32"] = [c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]
-_SIG["wsmg_sem_confusion_bf16"] = list(_SIG["wsmg_sem_confusion_f32"])
-_SIG["wsmg_sem_scores"] = [c_p, c_i, c_p, c_p]
-# scoring the waypoint attention, the action mean and the progress head (csrc/wsmg_nav_eval.hip): a float64 record per row, then the
-# row-ordered fold into counts and sums
-_SIG["wsmg_nav_rows"] = [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_f, c_p, c_i, c_p, c_p]
-_SIG["wsmg_nav_accumulate"] = [c_p, c_i, c_p, c_p, c_p]
-_SIG["wsmg_bn_stats_finalize"] = [c_p, c_i, c_i, c_l, c_f, c_f, c_p, c_p, c_p, c_p, c_p]
-_SIG["wsmg_bn_bwd_apply_bf16"] = [c_p] * 7 + [c_l, c_i, c_p, c_p]
-_SIG["wsmg_attn_fp8_mfma_fwd"] = [c_p] * 9 + [c_f, c_i, c_i, c_i, c_i, c_p, c_p, c_p]
-_SIG["wsmg_maxpool3x3s2_fwd_idx_bf16"] = [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p]
-_SIG["wsmg_maxpool3x3s2_bwd_idx_bf16"] = [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p]
-_SIG["wsmg_add3_bf16"] = [c_p, c_p, c_p, c_p, c_l, c_p]
-_SIG["wsmg_attn_fp8_prep"] = [c_p] * 4 + [c_i, c_i, c_i, c_i, c_f, c_f, c_f] + [c_p] * 8
-_SIG["wsmg_mean_rows"] = [c_p, c_l, c_i, c_p, c_p]
-_SIG["wsmg_bn_act_bwd_ld"] = [c_p, c_l] + _SIG["wsmg_bn_act_bwd"][1:]
-_SIG["wsmg_bn_act_bwd_ld_bf16"] = list(_SIG["wsmg_bn_act_bwd_ld"])
-_SIG["wsmg_bn_act_bwd_ld_bf16_lo"] = [c_p, c_l] + [c_p] * 6 + [c_i, c_l, c_i] + [c_p] * 6 + [c_l, c_p]
-_SIG["wsmg_upsample2x_bwd_ld"] = [c_p, c_l, c_p, c_i, c_i, c_i, c_i, c_p]
-_SIG["wsmg_upsample2x_bwd_ld_bf16"] = list(_SIG["wsmg_upsample2x_bwd_ld"])
-_SIG["wsmg_relu_bwd_rows_bf16"] = [c_p, c_l, c_p, c_p, c_l, c_i, c_p]
-_SIG["wsmg_cat_channels"] = [c_p, c_p, c_p, c_l, c_i, c_i, c_p]
-_SIG["wsmg_upsample2x_cat_bf16"] = [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]
-_SIG["wsmg_ce_nhwc_fwd"] = [c_p, c_p, c_l, c_i, c_p, c_p]
-_SIG["wsmg_ce_nhwc_bwd"] = [c_p, c_p, c_p, c_l, c_i, c_p, c_p]
-_SIG["wsmg_ce_nhwc_fwd_bf16"] = list(_SIG["wsmg_ce_nhwc_fwd"])
-_SIG["wsmg_ce_nhwc_bwd_bf16"] = list(_SIG["wsmg_ce_nhwc_bwd"])
-_SIG["wsmg_collate_pad"] = [c_p, c_p, c_i, c_i, c_l, c_i, c_f, c_p, c_p]
-_SIG["wsmg_collate_pad_nhwc_bf16"] = [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p]
-_SIG["wsmg_gru_workspace_bytes"] = [c_i]
-_SIG["wsmg_gru_fwd"] = [c_p] * 5 + [c_i] * 3 + [c_p] * 6 + [c_p]
-_SIG["wsmg_gru_bwd"] = [c_p] * 10 + [c_i] * 3 + [c_p] * 4 + [c_p]
-_SIG["wsmg_gru_fwd_owned"] = list(_SIG["wsmg_gru_fwd"])
-_SIG["wsmg_gru_bwd_owned"] = list(_SIG["wsmg_gru_bwd"])
-_SIG["wsmg_lstm_state_workspace_bytes"] = [c_i]
-_SIG["wsmg_lstm_state_fwd"] = [c_p] * 6 + [c_i] * 3 + [c_p] * 5 + [c_p]
-_SIG["wsmg_lstm_state_bwd"] = [c_p] * 8 + [c_i] * 3 + [c_p] * 4 + [c_p]
-_SIG["wsmg_lstm_workspace_bytes"] = [c_i]
-_SIG["wsmg_lstm_fwd"] = [c_p] * 4 + [c_i] * 3 + [c_p] * 4 + [c_p]
-_SIG["wsmg_lstm_bwd"] = [c_p] * 5 + [c_i] * 3 + [c_p] * 2 + [c_p]
-_SIG["wsmg_instr_rnn_workspace_bytes"] = [c_i] * 4
-_SIG["wsmg_instr_rnn_fwd"] = [c_i] + [c_p] * 4 + [c_i] * 4 + [c_p] * 4 + [c_p]
-_SIG["wsmg_instr_rnn_bwd"] = [c_i] + [c_p] * 6 + [c_i] * 4 + [c_p] * 3 + [c_p]
-_SIG["wsmg_group_norm_nhwc_bf16"] = [c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_p, c_p]
-_SIG["wsmg_rnn_status"] = [c_i]
-_SIG["wsmg_rnn_debug_spin_limit"] = [ctypes.c_uint]
-_SIG["wsmg_rnn_debug_inject"] = [ctypes.c_uint]
-_SIG["wsmg_instruction_dedup"] = [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p]
-_SIG["wsmg_conv_debug_win3_tile"] = [c_i]
-_SIG["wsmg_copy_multi"] = [c_p, c_i, c_p]
-_SIG["wsmg_copy_multi_guarded"] = [c_p, c_i, c_p, c_p]
-_SIG["wsmg_linear_rows"] = [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]
-_SIG["wsmg_act_heads"] = [c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]
-_SIG["wsmg_path_kl_fwd"] = [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p]
-_SIG["wsmg_path_kl_bwd"] = [c_p, c_p, c_p, c_i, c_i, c_p, c_p]
-_SIG["wsmg_adam_step_multi"] = [c_p, c_i, c_f, c_f, c_f, c_f, c_f, ctypes.c_double, ctypes.c_double, c_p]
-_SIG["wsmg_adam_step_multi_dev"] = [c_p, c_i, c_f, c_f, c_f, c_f, c_f, c_p, c_p]
-_SIG["wsmg_grad_norm_multi"] = [c_p, c_i, c_p, ctypes.c_longlong, c_f, c_i, c_p, c_p, c_p]
-_SIG["wsmg_adam_step_multi_guarded"] = [c_p, c_i, c_f, c_f, c_f, c_f, c_f, c_p, c_p, c_p]
-# the two steps of common_trainer.py:67-69 / dagger_trainer.py:536 with lr, betas, eps, weight_decay, max_grad_norm read from a device record
-_SIG["wsmg_adam_step_multi_hyper"] = [c_p, c_i, c_p, c_p, c_p, c_p]
-_SIG["wsmg_grad_norm_multi_hyper"] = [c_p, c_i, c_p, ctypes.c_longlong, c_p, c_i, c_p, c_p, c_p]
-# which tensor made the guard skip: the per-tensor report and its latch / the stand-alone statistics
-_SIG["wsmg_grad_report_multi"] = [c_p, c_i, c_p, ctypes.c_longlong, c_p, ctypes.c_longlong, c_p, c_p, c_p, c_p, c_p]
-_SIG["wsmg_grad_stats_multi"] = [c_p, c_i, c_p, ctypes.c_longlong, c_p, ctypes.c_longlong, c_p, c_p]
-_SIG["wsmg_rows_gemm_f32"] = ([c_p, c_i, c_i] * 3 + [c_p, c_i, c_i, c_p, c_p, c_i, c_i] + [c_p, c_i, c_i] * 3 + [c_p, c_i] * 3
-                              + [c_i, c_p, ctypes.c_uint, c_p, c_i, c_p, c_p])
-_SIG["wsmg_rows_gemm_workgroups"] = [c_i, c_i]
-_SIG["wsmg_rows_gemm_supported"] = [c_i]
-_SIG["wsmg_gru_fwd_chain"] = [c_p] * 5 + [c_i] * 3 + [c_p] * 6 + [c_i, c_p, ctypes.c_uint, c_p, c_p]
-_SIG["wsmg_gru_bwd_chain"] = [c_p] * 10 + [c_i] * 3 + [c_p] * 4 + [c_i, c_p, ctypes.c_uint, c_p, c_p]
-_SIG["wsmg_gru_chain_workgroups"] = []
-_SIG["wsmg_lstm_state_fwd_chain"] = [c_p] * 6 + [c_i] * 3 + [c_p] * 5 + [c_i, c_p, ctypes.c_uint, c_p, c_p]
-_SIG["wsmg_lstm_state_bwd_chain"] = [c_p] * 8 + [c_i] * 3 + [c_p] * 4 + [c_i, c_p, ctypes.c_uint, c_p, c_p]
-_SIG["wsmg_lstm_state_chain_workgroups"] = []
-_SIG["wsmg_attn_fp8_mfma_fused"] = [c_p] * 5 + [c_f] * 4 + [c_i] * 4 + [c_p, ctypes.c_uint, c_i, c_p, c_p, c_p, c_p]
-_SIG["wsmg_attn_fp8_mfma_fused_arrivals"] = [c_i] * 4
-_SIG["wsmg_attn_fp8_mfma_bwd"] = [c_p] * 12 + [c_f] + [c_i] * 4 + [c_p] * 5
-_SIG["wsmg_collate_ego_sparse_nhwc_bf16"] = [c_p] * 5 + [c_i] * 4 + [c_f, c_p, c_p]
-_SIG["wsmg_ego_sparse_pack"] = [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]
-_SIG["wsmg_debug_occupy"] = [c_i, c_i, c_i, c_p, c_p, c_p]
-_SIG["wsmg_conv2d_bwd_data_bf16_ex"] = [c_p] * 5 + [c_i] * 12 + [c_p]
-_SIG["wsmg_conv2d_fwd_bf16_ex"] = [c_p] * 4 + [c_i, c_p, c_i, c_i] + [c_i] * 11 + [c_p]
-_SIG["wsmg_bev_index_compact"] = [c_p, c_i, c_i, c_i, c_f, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p]
-_SIG["wsmg_bev_scatter_rotate_compact"] = [c_p, c_p, c_p, c_p, c_f] + [c_i] * 6 + [c_p, c_p]
-_SIG["wsmg_colsum_multi"] = [c_p, c_i, c_p]
-_SIG["wsmg_map_fuse_retrieve"] = [c_p] * 5 + [c_i] * 4 + [c_f, c_p, c_p]
-_SIG["wsmg_bev_project"] = [c_p, c_p, c_p, c_f, c_i, c_i, c_i, c_f] + [c_i] * 5 + [c_f, c_p, c_p, c_p]
-_SIG["wsmg_attn_fp8_row_fwd"] = [c_p] * 5 + [c_f, c_i, c_i, c_i] + [c_p] * 4
-_RESTYPE = {"wsmg_cls_tail_workspace_floats": c_l, "wsmg_attn_fp8_workspace_bytes": c_l, "wsmg_lstm_workspace_bytes": c_l, "wsmg_build_info": ctypes.c_char_p, "wsmg_channel_reduce_workspace_bytes": c_l, "wsmg_gru_workspace_bytes": c_l, "wsmg_lstm_state_workspace_bytes": c_l,
-            "wsmg_instr_rnn_workspace_bytes": c_l}
+def _read_header():
+    if not os.path.exists(HEADER_PATH):
+        raise WsmgError(f"{HEADER_PATH} not found: the binding of libwsmgmap.so is derived from the checkout's header, "
+                        "there is no second copy of the ABI")
+    with open(HEADER_PATH) as f:
+        return parse_header(f.read())
+
+
+# name -> argtypes, name -> restype and the host-array descriptors, all as include/wsmgmap.h declares them
+_SIG, _RESTYPE, _STRUCTS = _read_header()
+CopyDesc, RelayoutDesc, ColsumDesc, AdamDesc = (type(n, (ctypes.Structure,), {"_fields_": _STRUCTS[n]})
+                                                for n in ("WsmgCopyDesc", "WsmgRelayoutDesc", "WsmgColsumDesc", "WsmgAdamDesc"))
 
 _lib = None
 
@@ -226,7 +101,7 @@ def lib():
             except AttributeError as e:
                 raise WsmgError(f"{LIB_PATH} does not export {name}") from e
             fn.argtypes = args
-            fn.restype = _RESTYPE.get(name, c_i)
+            fn.restype = _RESTYPE[name]
         info = L.wsmg_build_info() or b""
         if b"rnn-nopk" not in info:
             # the GRU / LSTM gradient kernels are only correct when wsmg_rnn.hip was compiled without packed-fp32 instructions

@@ -32,10 +32,7 @@ import torch
 from . import _abi
 
 
-class _AdamDesc(ctypes.Structure):
-    _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p), ("exp_avg_sq", ctypes.c_void_p),
-                ("n", ctypes.c_longlong)]
-
+_AdamDesc = _abi.AdamDesc   # WsmgAdamDesc of include/wsmgmap.h: param, grad, exp_avg, exp_avg_sq, n
 
 ADAM_CHUNK = 4096         # elements per workgroup (csrc/wsmg_optim.hip): one float64 partial each in the norm's workspace
 ADAM_MAX = 48             # tensors (or copies) per launch (csrc/wsmg_common.h): longer lists are cut into several launches
