@@ -95,8 +95,7 @@ int wsmg_map_retrieve_fused(const float* global_map, const float* gps, const flo
                             float resolution, float* out, wsmg_stream_t stream);
 /* The same in one launch through LDS (round 5): a workgroup stages the box of global-map pixels its 8 x 8 output tile can touch
  * (<= 14 x 14 pixels x a slice of <= 40 channels) and takes the 16 taps of every element from there, the tap geometry computed once
- * per (pixel, rotation tap); bit-identical to wsmg_map_retrieve.  Any C % 4 == 0.  WSMG_RETRIEVE_TRACE=1 (diagnostic) prints
- * the phase boundaries of sampled workgroups in cycles and synchronises. */
+ * per (pixel, rotation tap); bit-identical to wsmg_map_retrieve.  Any C % 4 == 0. */
 int wsmg_map_retrieve_tiled(const float* global_map, const float* gps, const float* compass, int B, int C, int E, int G,
                             float resolution, float* out, wsmg_stream_t stream);
 
@@ -114,7 +113,7 @@ int wsmg_bev_project(const float* depth, const float* feat, const float* heading
  * and out are bit-identical to wsmg_map_fuse_planes followed by wsmg_map_retrieve_tiled — the episode reset of the sample's whole
  * G x G map, windows that leave the map, odd E, odd G and G == E included — for masks in {0, 1} and finite features.  Every map
  * element has one writer; a retrieval workgroup fuses what it reads itself, before or after that writer's store, which is exact
- * because the fuse is idempotent per element under those masks (csrc/wsmg_bev.hip, map_fuse_retrieve_kernel).  No workgroup
+ * because the fuse is idempotent per element under those masks (csrc/wsmg_bev_map.hip, map_fuse_retrieve_kernel).  No workgroup
  * waits for another: capturable, no residency requirement. */
 int wsmg_map_fuse_retrieve(const float* ego_rot_planes, float* global_map, const float* gps, const float* compass,
                            const float* masks, int B, int C, int E, int G, float resolution, float* out, wsmg_stream_t stream);
