@@ -311,7 +311,8 @@ int wsmg_path_kl_fwd(const float* dis, const float* lo, const float* hi, const f
 int wsmg_path_kl_bwd(const float* gkl, const float* target, const float* att, int B, int n, float* datt, wsmg_stream_t stream);
 
 /* One Adam step over a list of float32 parameter tensors (amsgrad = False, maximize = False; weight_decay is the L2 form
- * added to the gradient), arithmetic in torch.optim.Adam's order.  Replaces the optimizer step of the reference's update
+ * added to the gradient; the _ext entry points below take amsgrad, maximize and AdamW's decoupled decay as flags), arithmetic in
+ * torch.optim.Adam's order.  Replaces the optimizer step of the reference's update
  * (torch.optim.Adam built at common_trainer.py:67-69, stepped at dagger_trainer.py:540-541): 3 launches for the policy's 102
  * live tensors instead of 15.  descs is a HOST array; bias_correction{1,2} = 1 - beta{1,2}^step, computed by the caller. */
 typedef struct {
@@ -360,6 +361,31 @@ int wsmg_adam_step_multi_hyper(const WsmgAdamDesc* descs, int n, const float* hy
 int wsmg_grad_norm_multi_hyper(const WsmgAdamDesc* descs, int n, double* partials, long long partials_cap,
                                const float* hyper_guard_row, int skip_nonfinite, float* guard, float* step_dev,
                                wsmg_stream_t stream);
+/* The four steps above with torch.optim.Adam's remaining options and torch.optim.AdamW's weight decay, chosen by `flags`:
+ *   WSMG_ADAM_AMSGRAD       a fifth array per tensor, max_exp_avg_sq: after exp_avg_sq is updated, max = (v > max || v != v) ? v : max
+ *                           (a NaN propagates, as torch.maximum's does), and the step divides by sqrt(max) / sqrt(bc2) + eps
+ *   WSMG_ADAM_MAXIMIZE      the step reads -grad (behind the guard's grad * coef: the clip acts on the same norm)
+ *   WSMG_ADAM_DECOUPLED_WD  a non-zero weight_decay multiplies the parameter by (float)(1.0 - (double)lr * (double)weight_decay)
+ *                           in front of the moments (AdamW's param.mul_(1 - lr * weight_decay)) and is not added to the gradient;
+ *                           the _hyper form takes lr and weight_decay from the row and forms the factor with the same expression
+ * max_exp_avg_sq is a HOST array of n device pointers, parallel to descs (WsmgAdamDesc keeps its layout), read only with
+ * WSMG_ADAM_AMSGRAD; its tensors join the alignment test of the 16-byte path.  Every other argument, and every check, is that of the
+ * entry point of the same name without `_ext`; in addition WSMG_EINVAL for a bit of flags outside the three, and with
+ * WSMG_ADAM_AMSGRAD for a NULL max_exp_avg_sq (n > 0) or a NULL or not 4-byte aligned entry of a non-empty descriptor — every
+ * descriptor of every launch is checked before the first launch, a rejected call launches nothing.  A guarded step whose record says
+ * skip writes nothing at all, max_exp_avg_sq included.  flags = 0 gives the bits of the entry point without `_ext` (through
+ * kernels of this family: the kernels behind the four entry points above do not know the options). */
+enum { WSMG_ADAM_AMSGRAD = 1, WSMG_ADAM_MAXIMIZE = 2, WSMG_ADAM_DECOUPLED_WD = 4 };
+int wsmg_adam_step_multi_ext(const WsmgAdamDesc* descs, int n, float* const* max_exp_avg_sq, int flags, float lr, float beta1,
+                             float beta2, float eps, float weight_decay, double bias_correction1, double bias_correction2,
+                             wsmg_stream_t stream);
+int wsmg_adam_step_multi_dev_ext(const WsmgAdamDesc* descs, int n, float* const* max_exp_avg_sq, int flags, float lr, float beta1,
+                                 float beta2, float eps, float weight_decay, const float* step_dev, wsmg_stream_t stream);
+int wsmg_adam_step_multi_guarded_ext(const WsmgAdamDesc* descs, int n, float* const* max_exp_avg_sq, int flags, float lr, float beta1,
+                                     float beta2, float eps, float weight_decay, const float* step_dev, const float* guard,
+                                     wsmg_stream_t stream);
+int wsmg_adam_step_multi_hyper_ext(const WsmgAdamDesc* descs, int n, float* const* max_exp_avg_sq, int flags, const float* hyper_row,
+                                   const float* step_dev, const float* guard, wsmg_stream_t stream);
 /* WHICH tensor made the guard skip: a per-tensor report of the gradients, and a latch that keeps the report of a skipped step until
  * the host reads it (the reference has no counterpart: its trainer checks nothing, dagger_trainer.py:536-541).  Only grad and n of a
  * descriptor are read; a descriptor with n == 0 owns no chunk, may have a NULL grad, and gets an all-zero row.

@@ -13,6 +13,10 @@ per step, arms interleaved over --rounds rounds of --steps steps:
     wsmg-guarded-report          wsmg-guarded with grad_report=True: the per-tensor report and its latch behind the norm (steps taken:
                                  the latch's launch returns at once)
     clip+wsmg                    torch.nn.utils.clip_grad_norm_ in front of the unguarded step (what the guard replaces)
+    wsmg-amsgrad                 wsmgmap.optim.Adam(amsgrad=True): a fifth array, max_exp_avg_sq, read and written (nine streamed arrays
+                                 against seven)
+    wsmg-adamw-amsgrad           wsmgmap.optim.AdamW(amsgrad=True, weight_decay=1e-2): the same with the decoupled decay
+    wsmg-maximize                wsmgmap.optim.Adam(maximize=True): the plain step's arrays through the kernels that take the options
 
 WSMG_LIB=<another build of libwsmgmap.so> times that library's unguarded step (an older build has no guarded arm: --arms wsmg)."""
 import argparse
@@ -25,7 +29,7 @@ import bench
 from wsmgmap.common.aux_losses import AuxLosses
 from wsmgmap.config import default_model_config
 from wsmgmap.models.policy import BasePolicy
-from wsmgmap.optim import Adam as WsmgAdam
+from wsmgmap.optim import Adam as WsmgAdam, AdamW as WsmgAdamW
 ap = argparse.ArgumentParser()
 ap.add_argument("--arms", default="torch-foreach,torch-fused,wsmg,wsmg-guarded,clip+wsmg")
 ap.add_argument("--rounds", type=int, default=3)
@@ -55,6 +59,12 @@ for name in args.arms.split(","):
         opt = WsmgAdam(policy.parameters(), lr=1e-6)
     elif name in ("wsmg-dev", "wsmg-dev-hyper"):
         opt = WsmgAdam(policy.parameters(), lr=1e-6, capturable=True, **({"hyper_on_device": True} if name.endswith("-hyper") else {}))
+    elif name == "wsmg-amsgrad":
+        opt = WsmgAdam(policy.parameters(), lr=1e-6, amsgrad=True)
+    elif name == "wsmg-adamw-amsgrad":
+        opt = WsmgAdamW(policy.parameters(), lr=1e-6, amsgrad=True, weight_decay=1e-2)
+    elif name == "wsmg-maximize":
+        opt = WsmgAdam(policy.parameters(), lr=1e-6, maximize=True)
     elif name == "wsmg-guarded":
         opt = WsmgAdam(policy.parameters(), lr=1e-6, max_grad_norm=0.5 * norm, skip_nonfinite=True)
     elif name == "wsmg-guarded-hyper":

@@ -7,6 +7,9 @@
 // of one tensor (16-byte accesses when all four pointers are 16-byte aligned) and finds its tensor by a search over the
 // table's block prefix.  Arithmetic as torch.optim.Adam (amsgrad = False, maximize = False), in its order:
 //     g' = g + wd p;  m += (1 - b1) (g' - m);  v = b2 v + (1 - b2) g' g';  p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)
+// and, through the _ext entry points (flags WSMG_ADAM_*), torch's amsgrad = True (a fifth array, max_exp_avg_sq, whose running
+// maximum of v replaces v under the root), maximize = True (g' = -g) and the decoupled weight decay of torch.optim.AdamW
+// (p *= 1 - lr wd in front of the moments, no wd p in g').
 //
 // ONE element step (adam1), ONE table of chunks (ChunkTable, chunk_tensor + locate_chunk, for_each_batch on the host), ONE descriptor check
 // (check_descs, before an entry point's first launch), and four front ends that differ in where the step's inputs come from:
@@ -20,6 +23,10 @@
 //   wsmg_adam_step_multi_hyper    the _dev / _guarded form with lr, betas, eps, weight_decay (and wsmg_grad_norm_multi_hyper with
 //                                 max_grad_norm) read from a float32 record in device memory that the host refreshes between replays
 //                                 (wsmgmap.optim.Adam(hyper_on_device=True).sync_hyper()); no kernel writes the record
+//   wsmg_adam_step_multi{,_dev,_guarded,_hyper}_ext   the same four behind kernels of their own (adam_multi_ext_kernel<GUARD, HYPER,
+//                                 AMSGRAD>): `flags` and the decay factor travel as wave-uniform kernel arguments, max_exp_avg_sq as
+//                                 a parallel host array of pointers.  The four kernels above are compiled from the same element step
+//                                 and chunk walk with the options off at compile time: not one of their instructions knows of them.
 // No host synchronisation anywhere.
 #include "wsmg_common.h"
 
@@ -92,67 +99,116 @@ struct AdamBatch {
   const float* hyper;      // or null: this group's row of the hyper record {lr, beta1, beta2, eps, weight_decay, 0, 0, 0} (read by the
 };                         //          _hyper kernels only)
 
+// What the _ext kernels add to a batch: the fifth array of every table entry (read only when AMSGRAD) and the options, the same for
+// every lane.  decay = (float)(1.0 - (double)lr * (double)wd), by value (the _hyper kernels form theirs from the record's row).
+struct AdamExt {
+  float* vmax[ADAM_MAX];
+  int flags;               // WSMG_ADAM_MAXIMIZE | WSMG_ADAM_DECOUPLED_WD (WSMG_ADAM_AMSGRAD chose the kernel)
+  float decay;
+};
+
+struct AdamExtBatch {
+  AdamBatch b;
+  AdamExt e;
+};
+
+struct AdamOpts {          // the element step's view of them
+  bool maximize, decoupled;
+  float decay;
+};
+
 // THE element step.  These forms define it, rounding by rounding, for every front end; nothing else may be contracted:
-//     g' = coef g (GUARD only: a product of its own);  g' = fma(wd, p, g') unless wd == 0
+//     g' = coef g (GUARD only: a product of its own)
+//     g' = -g' (maximize: exact; behind the guard's product, so the clip acts on the same norm)
+//     wd != 0, the L2 form:        g' = fma(wd, p, g'), behind the negation as in torch
+//     wd != 0, the decoupled form: p  = p * decay, decay = (float)(1.0 - (double)lr * (double)wd): one product, in front of the
+//                                  moments (torch.optim.AdamW's param.mul_(1 - lr * weight_decay)); g' is left alone
 //     m  = fma(1 - b1, g' - m, m)
 //     v  = fma(v, b2, ((1 - b2) g') g') in the 16-byte loop (VEC),  fma(g', (1 - b2) g', v b2) in the two scalar loops
+//     amsgrad: vmax = (v > vmax || v != v) ? v : vmax (exact; a NaN in v or in vmax stays, as torch.maximum keeps it and fmaxf
+//              would not), and vmax stands for v in the next line
 //     p  = fma(-lr_bc1, m / (sqrt(v) / sqrt_bc2 + eps), p)
 // The two forms of v round differently and which loop an element meets is fixed by its address and index, so both are part of the
 // definition: a step's bits do not depend on the front end, the compiler's contraction choices or the layout of AdamBatch.
-// tests/test_gpu_adam_hyper.py compares the front ends' bits on every path.
-template <bool GUARD, bool VEC>
-__device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, const AdamHyper& h, float lr_bc1, float sqrt_bc2,
-                                      float coef) {
+// tests/test_gpu_adam_hyper.py compares the front ends' bits on every path, tests/test_gpu_adam_variants.py those of the options.
+// EXT = false (the four kernels without options) compiles the three options out: `o` and `vmax` are then not read.
+template <bool GUARD, bool VEC, bool EXT, bool AMSGRAD>
+__device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, float& vmax, const AdamHyper& h, float lr_bc1,
+                                      float sqrt_bc2, float coef, const AdamOpts& o) {
 #pragma clang fp contract(off)
   if (GUARD) g *= coef;
-  if (h.wd != 0.f) g = fmaf(h.wd, p, g);
+  if (EXT && o.maximize) g = -g;
+  if (h.wd != 0.f) {
+    if (EXT && o.decoupled) p = p * o.decay;
+    else g = fmaf(h.wd, p, g);
+  }
   m = fmaf(h.beta1c, g - m, m);
   const float gc = h.beta2c * g;
   v = VEC ? fmaf(v, h.beta2, gc * g) : fmaf(g, gc, v * h.beta2);
-  const float denom = sqrtf(v) / sqrt_bc2 + h.eps;
+  float s = v;
+  if (AMSGRAD) {
+    vmax = (v > vmax || v != v) ? v : vmax;
+    s = vmax;
+  }
+  const float denom = sqrtf(s) / sqrt_bc2 + h.eps;
   p = fmaf(-lr_bc1, m / denom, p);
 }
 
-// One workgroup's 4 096 elements of its tensor (a loop nest of its own: it loads and stores four arrays).
-template <bool GUARD>
-__device__ __forceinline__ void adam_chunk(const AdamBatch& b, const AdamHyper& h, float lr_bc1, float sqrt_bc2, float coef) {
+// One workgroup's 4 096 elements of its tensor (a loop nest of its own: it loads and stores four arrays, five with AMSGRAD, whose
+// address then joins the test for the 16-byte loop).  e is read only when EXT.
+template <bool GUARD, bool EXT, bool AMSGRAD>
+__device__ __forceinline__ void adam_chunk(const AdamBatch& b, const AdamExt* e, const AdamHyper& h, float lr_bc1, float sqrt_bc2,
+                                           float coef, const AdamOpts& o) {
   const int t = chunk_tensor(b.tab);
   float* __restrict__ p = b.p[t];
   const float* __restrict__ g = b.g[t];
   float* __restrict__ m = b.m[t];
   float* __restrict__ v = b.v[t];
+  float* __restrict__ x = AMSGRAD ? e->vmax[t] : nullptr;
   const Chunk c = locate_chunk(b.tab, t);
   const long long i0 = c.i0, i1 = c.i1;
-  const bool vec = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0);
+  const bool vec = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)x) & 15) == 0);
+  float none = 0.f;        // vmax of a step without AMSGRAD: never read
   if (vec) {
     const long long nv = i0 + ((i1 - i0) & ~3ll);
     for (long long i = i0 + 4 * (long long)threadIdx.x; i < nv; i += 4 * 256) {
-      f32x4 pp = ld4(p + i), mm = ld4(m + i), vv = ld4(v + i);
+      f32x4 pp = ld4(p + i), mm = ld4(m + i), vv = ld4(v + i), xx = {};
+      if (AMSGRAD) xx = ld4(x + i);
       const f32x4 gg = ld4(g + i);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        float pj = pp[j], mj = mm[j], vj = vv[j];
-        adam1<GUARD, true>(pj, gg[j], mj, vj, h, lr_bc1, sqrt_bc2, coef);
-        pp[j] = pj; mm[j] = mj; vv[j] = vj;
+        float pj = pp[j], mj = mm[j], vj = vv[j], xj = xx[j];
+        adam1<GUARD, true, EXT, AMSGRAD>(pj, gg[j], mj, vj, xj, h, lr_bc1, sqrt_bc2, coef, o);
+        pp[j] = pj; mm[j] = mj; vv[j] = vj; xx[j] = xj;
       }
       st4(p + i, pp); st4(m + i, mm); st4(v + i, vv);
+      if (AMSGRAD) st4(x + i, xx);
     }
-    for (long long i = nv + threadIdx.x; i < i1; i += 256) adam1<GUARD, false>(p[i], g[i], m[i], v[i], h, lr_bc1, sqrt_bc2, coef);
+    for (long long i = nv + threadIdx.x; i < i1; i += 256)
+      adam1<GUARD, false, EXT, AMSGRAD>(p[i], g[i], m[i], v[i], AMSGRAD ? x[i] : none, h, lr_bc1, sqrt_bc2, coef, o);
   } else {
-    for (long long i = i0 + threadIdx.x; i < i1; i += 256) adam1<GUARD, false>(p[i], g[i], m[i], v[i], h, lr_bc1, sqrt_bc2, coef);
+    for (long long i = i0 + threadIdx.x; i < i1; i += 256)
+      adam1<GUARD, false, EXT, AMSGRAD>(p[i], g[i], m[i], v[i], AMSGRAD ? x[i] : none, h, lr_bc1, sqrt_bc2, coef, o);
   }
 }
 
 // The front ends.  GUARD reads skip and coef once, before anything else (otherwise the guard pointer is not read).  HYPER reads its
 // group's row once, here, through a wave-uniform address, and derives 1 - beta in float as adam_launch does (otherwise the hyper
 // pointer is not read and the values are the kernel arguments).  With a device step count the bias corrections are 1 - beta^step in
-// double, the host's expressions: equal values give equal bits.
-template <bool GUARD, bool HYPER>
-__device__ __forceinline__ void adam_multi(const AdamBatch& b) {
+// double, the host's expressions: equal values give equal bits.  EXT reads the options from e (otherwise e is not read); with HYPER
+// the decay factor is formed here from the row's lr and weight_decay, with adam_launch's expression.
+template <bool GUARD, bool HYPER, bool EXT = false, bool AMSGRAD = false>
+__device__ __forceinline__ void adam_multi(const AdamBatch& b, const AdamExt* e = nullptr) {
   float coef = 1.f;
   if (GUARD) {
-    if (b.guard[GUARD_SKIP] != 0.f) return;     // a skipped step: no load of p / m / v, nothing written
+    if (b.guard[GUARD_SKIP] != 0.f) return;     // a skipped step: no load of p / m / v / vmax, nothing written
     coef = b.guard[GUARD_COEF];
+  }
+  AdamOpts o = {false, false, 1.f};
+  if (EXT) {
+    o.maximize = (e->flags & WSMG_ADAM_MAXIMIZE) != 0;
+    o.decoupled = (e->flags & WSMG_ADAM_DECOUPLED_WD) != 0;
+    o.decay = e->decay;
   }
   if (HYPER) {
     const float* __restrict__ row = b.hyper;
@@ -166,7 +222,8 @@ __device__ __forceinline__ void adam_multi(const AdamBatch& b) {
     const double st = (double)*b.step_dev;
     const float lr_bc1 = (float)((double)lr / (1.0 - pow((double)beta1, st)));
     const float sqrt_bc2 = (float)sqrt(1.0 - pow((double)h.beta2, st));
-    adam_chunk<GUARD>(b, h, lr_bc1, sqrt_bc2, coef);
+    if (EXT) o.decay = (float)(1.0 - (double)lr * (double)h.wd);
+    adam_chunk<GUARD, EXT, AMSGRAD>(b, e, h, lr_bc1, sqrt_bc2, coef, o);
     return;
   }
   float lr_bc1 = b.lr_bc1, sqrt_bc2 = b.sqrt_bc2;
@@ -176,13 +233,18 @@ __device__ __forceinline__ void adam_multi(const AdamBatch& b) {
     sqrt_bc2 = (float)sqrt(1.0 - pow((double)b.h.beta2, st));
   }
   const AdamHyper h = b.h;
-  adam_chunk<GUARD>(b, h, lr_bc1, sqrt_bc2, coef);
+  adam_chunk<GUARD, EXT, AMSGRAD>(b, e, h, lr_bc1, sqrt_bc2, coef, o);
 }
 
 __global__ __launch_bounds__(256) void adam_multi_kernel(AdamBatch b) { adam_multi<false, false>(b); }
 __global__ __launch_bounds__(256) void adam_multi_guarded_kernel(AdamBatch b) { adam_multi<true, false>(b); }
 __global__ __launch_bounds__(256) void adam_multi_hyper_kernel(AdamBatch b) { adam_multi<false, true>(b); }
 __global__ __launch_bounds__(256) void adam_multi_guarded_hyper_kernel(AdamBatch b) { adam_multi<true, true>(b); }
+
+// The same four front ends with the options: 2 x 2 x 2 kernels (amsgrad changes the number of arrays; maximize and the decay form are
+// wave-uniform branches on kernel arguments).
+template <bool GUARD, bool HYPER, bool AMSGRAD>
+__global__ __launch_bounds__(256) void adam_multi_ext_kernel(AdamExtBatch x) { adam_multi<GUARD, HYPER, true, AMSGRAD>(x.b, &x.e); }
 
 // ---- the guard: global gradient norm -> {norm, coef, skip, skipped}
 
@@ -408,19 +470,23 @@ __global__ __launch_bounds__(256) void grad_report_latch_kernel(const uint32_t* 
 // ---- the host side: one descriptor check, one batching loop
 
 // What an entry point needs of a descriptor with n > 0 (of every one: 0 <= n <= max_n).
-enum { DESC_GRAD = 0, DESC_ALL = 1, DESC_ALIGN4 = 2 };   // grad only / all four pointers; | DESC_ALIGN4: each a multiple of 4
+enum { DESC_GRAD = 0, DESC_ALL = 1, DESC_ALIGN4 = 2, DESC_VMAX = 4 };   // grad only / all four pointers; | DESC_ALIGN4: each a multiple of 4
 constexpr long long DESC_MAX_N = (1ll << 30) * ADAM_CHUNK;
 
 // THE descriptor check, run by every entry point before its first launch: the list's chunk total (>= 0; at most 2^30, the grid's
 // bound), or WSMG_EINVAL (the error codes are negative, so one return value carries both: callers test `< 0`).
-static long long check_descs(const WsmgAdamDesc* descs, int n, int need, long long max_n) {
+// DESC_VMAX: vmax[i], the parallel host array of the _ext entry points, is a fifth pointer of descriptor i: not null and, whatever
+// the entry point, a multiple of 4.
+static long long check_descs(const WsmgAdamDesc* descs, int n, int need, long long max_n, float* const* vmax = nullptr) {
   if (n < 0 || (n > 0 && !descs)) return WSMG_EINVAL;
+  if ((need & DESC_VMAX) && n > 0 && !vmax) return WSMG_EINVAL;
   long long total = 0;
   for (int i = 0; i < n; ++i) {
     const WsmgAdamDesc& d = descs[i];
     if (d.n < 0 || d.n > max_n) return WSMG_EINVAL;
     if (d.n == 0) continue;
     if (!d.grad || ((need & DESC_ALL) && (!d.param || !d.exp_avg || !d.exp_avg_sq))) return WSMG_EINVAL;
+    if ((need & DESC_VMAX) && (!vmax[i] || ((uintptr_t)vmax[i] & 3))) return WSMG_EINVAL;
     uintptr_t bits = (uintptr_t)d.grad;
     if (need & DESC_ALL) bits |= (uintptr_t)d.param | (uintptr_t)d.exp_avg | (uintptr_t)d.exp_avg_sq;
     if ((need & DESC_ALIGN4) && (bits & 3)) return WSMG_EINVAL;
@@ -455,12 +521,30 @@ static int for_each_batch(const WsmgAdamDesc* descs, int n, ChunkTable& tb, Slot
   return base;
 }
 
+// What an _ext entry point adds to adam_launch's arguments (null: the entry points without options and their four kernels).
+struct AdamExtArgs {
+  float* const* vmax;      // host array parallel to descs, read when flags has WSMG_ADAM_AMSGRAD
+  int flags;
+};
+constexpr int ADAM_FLAGS = WSMG_ADAM_AMSGRAD | WSMG_ADAM_MAXIMIZE | WSMG_ADAM_DECOUPLED_WD;
+
+template <bool AMSGRAD>
+static void adam_ext_launch(const AdamExtBatch& x, bool hyper, bool guard, dim3 grid, wsmg_stream_t s) {
+  if (hyper && guard) hipLaunchKernelGGL((adam_multi_ext_kernel<true, true, AMSGRAD>), grid, dim3(256), 0, wsmg_s(s), x);
+  else if (hyper) hipLaunchKernelGGL((adam_multi_ext_kernel<false, true, AMSGRAD>), grid, dim3(256), 0, wsmg_s(s), x);
+  else if (guard) hipLaunchKernelGGL((adam_multi_ext_kernel<true, false, AMSGRAD>), grid, dim3(256), 0, wsmg_s(s), x);
+  else hipLaunchKernelGGL((adam_multi_ext_kernel<false, false, AMSGRAD>), grid, dim3(256), 0, wsmg_s(s), x);
+}
+
 static int adam_launch(const WsmgAdamDesc* descs, int n, int need, float lr, float beta1, float beta2, float eps, float weight_decay,
                        double bias_correction1, double bias_correction2, const float* step_dev, const float* guard,
-                       const float* hyper, wsmg_stream_t s) {
+                       const float* hyper, wsmg_stream_t s, const AdamExtArgs* ext = nullptr) {
   if (!step_dev && (!(bias_correction1 > 0.0) || !(bias_correction2 > 0.0))) return WSMG_EINVAL;
-  if (check_descs(descs, n, need, DESC_MAX_N) < 0) return WSMG_EINVAL;
-  AdamBatch b;
+  if (ext && (ext->flags & ~ADAM_FLAGS)) return WSMG_EINVAL;
+  const bool amsgrad = ext && (ext->flags & WSMG_ADAM_AMSGRAD);
+  if (check_descs(descs, n, need | (amsgrad ? DESC_VMAX : 0), DESC_MAX_N, amsgrad ? ext->vmax : nullptr) < 0) return WSMG_EINVAL;
+  AdamExtBatch x;
+  AdamBatch& b = x.b;
   b.h = {1.f - beta1, beta2, 1.f - beta2, eps, weight_decay};
   b.lr_bc1 = step_dev ? 0.f : (float)((double)lr / bias_correction1);
   b.sqrt_bc2 = step_dev ? 1.f : (float)sqrt(bias_correction2);
@@ -469,11 +553,21 @@ static int adam_launch(const WsmgAdamDesc* descs, int n, int need, float lr, flo
   b.beta1 = beta1;
   b.guard = guard;
   b.hyper = hyper;
+  for (int k = 0; k < ADAM_MAX; ++k) x.e.vmax[k] = nullptr;
+  x.e.flags = ext ? ext->flags : 0;
+  x.e.decay = (float)(1.0 - (double)lr * (double)weight_decay);   // (the _hyper kernels form theirs from the row, with this expression)
   for_each_batch(descs, n, b.tab,
-                 [&](int k, const WsmgAdamDesc& d) { b.p[k] = d.param; b.g[k] = d.grad; b.m[k] = d.exp_avg; b.v[k] = d.exp_avg_sq; },
+                 [&](int k, const WsmgAdamDesc& d) {
+                   b.p[k] = d.param; b.g[k] = d.grad; b.m[k] = d.exp_avg; b.v[k] = d.exp_avg_sq;
+                   if (amsgrad) x.e.vmax[k] = ext->vmax[&d - descs];
+                 },
                  [&](int blocks, int) {
                    const dim3 grid((unsigned)blocks);
-                   if (hyper && guard) hipLaunchKernelGGL(adam_multi_guarded_hyper_kernel, grid, dim3(256), 0, wsmg_s(s), b);
+                   if (ext) {
+                     if (amsgrad) adam_ext_launch<true>(x, hyper != nullptr, guard != nullptr, grid, s);
+                     else adam_ext_launch<false>(x, hyper != nullptr, guard != nullptr, grid, s);
+                   }
+                   else if (hyper && guard) hipLaunchKernelGGL(adam_multi_guarded_hyper_kernel, grid, dim3(256), 0, wsmg_s(s), b);
                    else if (hyper) hipLaunchKernelGGL(adam_multi_hyper_kernel, grid, dim3(256), 0, wsmg_s(s), b);
                    else if (guard) hipLaunchKernelGGL(adam_multi_guarded_kernel, grid, dim3(256), 0, wsmg_s(s), b);
                    else hipLaunchKernelGGL(adam_multi_kernel, grid, dim3(256), 0, wsmg_s(s), b);
@@ -510,6 +604,43 @@ extern "C" int wsmg_adam_step_multi_hyper(const WsmgAdamDesc* descs, int n, cons
   if (!hyper_row || !step_dev) return WSMG_EINVAL;
   if (((uintptr_t)hyper_row & 3) || ((uintptr_t)step_dev & 3) || ((uintptr_t)guard & 3)) return WSMG_EINVAL;
   return adam_launch(descs, n, DESC_ALL | DESC_ALIGN4, 0.f, 0.f, 0.f, 0.f, 0.f, 0.0, 0.0, step_dev, guard, hyper_row, s);
+}
+
+// The four front ends with the options of `flags` (WSMG_ADAM_AMSGRAD | WSMG_ADAM_MAXIMIZE | WSMG_ADAM_DECOUPLED_WD; any other bit:
+// WSMG_EINVAL), each with the checks of the entry point it mirrors.  max_exp_avg_sq is a HOST array of n device pointers, parallel to
+// descs; it is read only with WSMG_ADAM_AMSGRAD, and then a null or not 4-byte aligned entry of a non-empty descriptor is
+// WSMG_EINVAL, found before the first launch.  flags = 0 steps as the entry point without `_ext` does, bit for bit, through the
+// kernels of this family.
+extern "C" int wsmg_adam_step_multi_ext(const WsmgAdamDesc* descs, int n, float* const* max_exp_avg_sq, int flags, float lr, float beta1,
+                                        float beta2, float eps, float weight_decay, double bias_correction1, double bias_correction2,
+                                        wsmg_stream_t s) {
+  const AdamExtArgs ext = {max_exp_avg_sq, flags};
+  return adam_launch(descs, n, DESC_ALL, lr, beta1, beta2, eps, weight_decay, bias_correction1, bias_correction2, nullptr, nullptr,
+                     nullptr, s, &ext);
+}
+
+extern "C" int wsmg_adam_step_multi_dev_ext(const WsmgAdamDesc* descs, int n, float* const* max_exp_avg_sq, int flags, float lr,
+                                            float beta1, float beta2, float eps, float weight_decay, const float* step_dev,
+                                            wsmg_stream_t s) {
+  if (!step_dev) return WSMG_EINVAL;
+  const AdamExtArgs ext = {max_exp_avg_sq, flags};
+  return adam_launch(descs, n, DESC_ALL, lr, beta1, beta2, eps, weight_decay, 0.0, 0.0, step_dev, nullptr, nullptr, s, &ext);
+}
+
+extern "C" int wsmg_adam_step_multi_guarded_ext(const WsmgAdamDesc* descs, int n, float* const* max_exp_avg_sq, int flags, float lr,
+                                                float beta1, float beta2, float eps, float weight_decay, const float* step_dev,
+                                                const float* guard, wsmg_stream_t s) {
+  if (!step_dev || !guard) return WSMG_EINVAL;
+  const AdamExtArgs ext = {max_exp_avg_sq, flags};
+  return adam_launch(descs, n, DESC_ALL, lr, beta1, beta2, eps, weight_decay, 0.0, 0.0, step_dev, guard, nullptr, s, &ext);
+}
+
+extern "C" int wsmg_adam_step_multi_hyper_ext(const WsmgAdamDesc* descs, int n, float* const* max_exp_avg_sq, int flags,
+                                              const float* hyper_row, const float* step_dev, const float* guard, wsmg_stream_t s) {
+  if (!hyper_row || !step_dev) return WSMG_EINVAL;
+  if (((uintptr_t)hyper_row & 3) || ((uintptr_t)step_dev & 3) || ((uintptr_t)guard & 3)) return WSMG_EINVAL;
+  const AdamExtArgs ext = {max_exp_avg_sq, flags};
+  return adam_launch(descs, n, DESC_ALL | DESC_ALIGN4, 0.f, 0.f, 0.f, 0.f, 0.f, 0.0, 0.0, step_dev, guard, hyper_row, s, &ext);
 }
 
 // The sum-of-squares launches over checked descs: chunk c of the list -> partials[c].  Returns the chunk total.

@@ -2,7 +2,8 @@
 
 The reference builds `torch.optim.Adam(self.actor_critic.parameters(), lr=...)` (common_trainer.py:67-69) and steps it after
 `loss.backward()` (dagger_trainer.py:540-541).  This class is that optimizer — same constructor arguments, same arithmetic
-in the same order, `state_dict()` interchangeable with torch.optim.Adam's (`step`, `exp_avg`, `exp_avg_sq`) — with the step
+in the same order, `state_dict()` interchangeable with torch.optim.Adam's (`step`, `exp_avg`, `exp_avg_sq`, and `max_exp_avg_sq`
+with amsgrad=True) — with the step
 issued as 3 kernel launches for the policy's 102 live tensors instead of the stock multi-tensor path's 15 (0.25 ms of GPU time
 per update -> 0.06 ms).  float32 CUDA parameters only: anything else raises (there is no fallback path).
 
@@ -22,9 +23,15 @@ cannot.  `sync_hyper()` refreshes the record, outside the graph; an eager `step(
 `Adam(a guard option, grad_report=True)` names the tensor behind a skipped step: behind the norm, wsmg_grad_report_multi writes one
 row per parameter {norm, max |g| over the finite elements, NaN count, Inf count} and, only when the guard skips, copies the rows and a
 header into a latch that keeps them until the host reads it, however many clean steps (or graph replays) follow.  `grad_report()`
-and `last_skipped()` read them back; `grad_stats(params)` is the table alone, beside `global_grad_norm`."""
+and `last_skipped()` read them back; `grad_stats(params)` is the table alone, beside `global_grad_norm`.
+
+`Adam(amsgrad=True)`, `Adam(maximize=True)` and `AdamW(...)` (torch.optim.AdamW's decoupled weight decay, default 1e-2) step through
+the `_ext` entry points (wsmg_adam_step_multi_ext and its three siblings): the same element step with the option's roundings added,
+behind kernels of their own.  They combine with each other and with every option above.  With none of the three set, `step()` calls
+the entry points without `_ext`, as it always did."""
 import collections
 import ctypes
+import inspect
 import math
 
 import torch
@@ -36,6 +43,9 @@ _AdamDesc = _abi.AdamDesc   # WsmgAdamDesc of include/wsmgmap.h: param, grad, ex
 
 ADAM_CHUNK = 4096         # elements per workgroup (csrc/wsmg_optim.hip): one float64 partial each in the norm's workspace
 ADAM_MAX = 48             # tensors (or copies) per launch (csrc/wsmg_common.h): longer lists are cut into several launches
+FLAG_AMSGRAD, FLAG_MAXIMIZE, FLAG_DECOUPLED_WD = 1, 2, 4      # WSMG_ADAM_* of include/wsmgmap.h
+# torch.optim.Adam grew the keyword in 2.7: where it exists `param_groups` carries it, as torch's do
+_TORCH_HAS_DECOUPLED = "decoupled_weight_decay" in inspect.signature(torch.optim.Adam.__init__).parameters
 HYPER_ROW = 8             # floats per row of the hyper record (include/wsmgmap.h): {lr, beta1, beta2, eps, weight_decay, 0, 0, 0} per
 #                           parameter group, then the guard's row {max_grad_norm or 0, 0, ...}
 
@@ -86,11 +96,19 @@ def _stream(dev):
 
 
 def _adam_descs(items):
-    """The _AdamDesc array of [(p, g, exp_avg, exp_avg_sq)]."""
+    """The _AdamDesc array of [(p, g, exp_avg, exp_avg_sq, max_exp_avg_sq or None)]."""
     descs = (_AdamDesc * len(items))()
-    for d, (p, g, m, v) in zip(descs, items):
+    for d, (p, g, m, v, _) in zip(descs, items):
         d.param, d.grad, d.exp_avg, d.exp_avg_sq, d.n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
     return descs
+
+
+def _vmax_ptrs(items):
+    """The host array of max_exp_avg_sq addresses parallel to `_adam_descs(items)` (what the _ext entry points take beside the
+    descriptors), or None when no item has one."""
+    if not items or items[0][4] is None:
+        return None
+    return (ctypes.c_void_p * len(items))(*[it[4].data_ptr() for it in items])
 
 
 def _grad_descs(grads):
@@ -147,8 +165,16 @@ def global_grad_norm(params):
 class Adam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, maximize=False,
                  capturable=False, max_grad_norm=None, skip_nonfinite=False, guard_buffers=None, hyper_on_device=False,
-                 grad_report=False):
-        """capturable=True: the step count also lives in a device scalar (one per parameter group, incremented on the device)
+                 grad_report=False, decoupled_weight_decay=False):
+        """amsgrad=True: the state gains `max_exp_avg_sq`, the running maximum of `exp_avg_sq` (a NaN propagates, as torch.maximum's
+        does), allocated with the moments, and the step divides by its root; the parameters must be CUDA tensors (anything else is
+        refused at construction: the variant exists on the device only).  maximize=True: the step reads -grad; the guard's norm
+        and clip coefficient are those of grad.  decoupled_weight_decay=True (accepted where the installed torch.optim.Adam has the
+        keyword; `AdamW` is this class with it set): a non-zero weight_decay multiplies the parameter by 1 - lr * weight_decay in
+        front of the moments and is not added to the gradient.  All three are torch's arithmetic in torch's order, and combine with
+        each other and with every option below.
+
+        capturable=True: the step count also lives in a device scalar (one per parameter group, incremented on the device)
         and the kernel computes the bias corrections from it — the form `wsmgmap.graph.GraphedUpdate` captures into a HIP graph
         (kernel arguments are frozen at capture).  All stepped parameters of a group must then share one step count.
 
@@ -171,7 +197,9 @@ class Adam(torch.optim.Optimizer):
         hyper_on_device=True (needs capturable=True or the guarded step: only those keep the step count on the device): the
         kernels read `lr`, `betas`, `eps`, `weight_decay` of their parameter group, and `max_grad_norm`, from a float32 record in
         device memory, not from their launch arguments, so a step captured in a HIP graph follows later `param_groups` edits,
-        `torch.optim.lr_scheduler` steps and assignments to `max_grad_norm`.  `sync_hyper()` compares those values with a host
+        `torch.optim.lr_scheduler` steps and assignments to `max_grad_norm`.  `amsgrad`, `maximize` and the form of the weight decay
+        are not in the record: they are structural (they choose the kernel and its arguments), are passed by value at each eager
+        step, and a capture freezes them like any other argument.  `sync_hyper()` compares those values with a host
         mirror and, if one changed, refreshes the record with one asynchronous copy on the current stream: an eager `step()` and
         `GraphedUpdate` call it; around a graph of your own (`torch.cuda.graph`) call it before each replay.  Under capture
         nothing can be copied: a `step()` whose values differ from the mirror raises there.  Same arithmetic, bit for bit, as
@@ -221,10 +249,15 @@ class Adam(torch.optim.Optimizer):
         self._latch = None         # (4 words per chunk), all int32 (allocated by _reset_guard, never by a default construction)
         self._scan = None
         self._report_fixed = False  # the report's rows are laid out: no further parameter group
-        if amsgrad or maximize:
-            raise ValueError("wsmgmap.optim.Adam implements amsgrad=False, maximize=False (what the reference trains with)")
+        if decoupled_weight_decay and not (_TORCH_HAS_DECOUPLED or isinstance(self, AdamW)):
+            raise ValueError("decoupled_weight_decay is a keyword of wsmgmap.optim.Adam only where the installed torch.optim.Adam has "
+                             "it; wsmgmap.optim.AdamW is the decoupled form everywhere")
+        self._decoupled = bool(decoupled_weight_decay)      # of a group without the key (a torch that has no such keyword)
         _check_hyper(lr, betas, eps, weight_decay)
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False))
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=bool(amsgrad), maximize=bool(maximize))
+        if _TORCH_HAS_DECOUPLED:
+            defaults["decoupled_weight_decay"] = self._decoupled
+        super().__init__(params, defaults)
         if self._guarded:
             self._reset_guard()
         if self._hyper_on_device:
@@ -365,6 +398,11 @@ class Adam(torch.optim.Optimizer):
                              "one row per parameter and captured graphs hold its tables' addresses; pass every group to the "
                              "constructor")
         super().add_param_group(param_group)
+        group = self.param_groups[-1]
+        if group.get("amsgrad", False) and not all(p.is_cuda for p in group["params"]):
+            self.param_groups.pop()
+            raise ValueError("wsmgmap.optim.Adam(amsgrad=True) needs CUDA parameters: max_exp_avg_sq is a fifth array of the device "
+                             "step, and this optimizer has no CPU path")
 
     def _protected_buffers(self):
         """[(qualified name, tensor)]: running_mean, running_var and num_batches_tracked of every BatchNorm layer below the
@@ -431,11 +469,17 @@ class Adam(torch.optim.Optimizer):
         if self._guard_buffers is not None:
             self.snapshot_buffers()
 
+    def _flags(self, group):
+        """WSMG_ADAM_* of a parameter group: 0 steps through the entry points without `_ext`."""
+        return ((FLAG_AMSGRAD if group.get("amsgrad", False) else 0) | (FLAG_MAXIMIZE if group.get("maximize", False) else 0) |
+                (FLAG_DECOUPLED_WD if group.get("decoupled_weight_decay", self._decoupled) else 0))
+
     def _stepped_items(self, group, guarded=False, dev=None):
         """The parameters of `group` that have a gradient, checked, their state created and their step count advanced ->
-        ([(p, g, exp_avg, exp_avg_sq)], [step count of each], dev).  guarded: they must all sit on `dev` (None: the first one's
-        device), and moments that do not exist yet are refused under stream capture."""
+        ([(p, g, exp_avg, exp_avg_sq, max_exp_avg_sq or None)], [step count of each], dev).  guarded: they must all sit on `dev`
+        (None: the first one's device), and moments that do not exist yet are refused under stream capture."""
         items, steps = [], []
+        amsgrad = bool(group.get("amsgrad", False))
         for p in group["params"]:
             g = p.grad
             if g is None:
@@ -461,25 +505,34 @@ class Adam(torch.optim.Optimizer):
                 #                   state_dict() / load_state_dict() convert from / to torch.optim.Adam's float32 tensor
                 st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            if amsgrad and "max_exp_avg_sq" not in st:      # with the moments, or at the first step after amsgrad was turned on
+                if torch.cuda.is_current_stream_capturing():
+                    raise _abi.WsmgError("wsmgmap.optim.Adam(amsgrad=True): max_exp_avg_sq does not exist yet; take a step (or "
+                                         "load_state_dict) before capturing step() into a graph")
+                st["max_exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
             st["step"] += 1       # guarded: ATTEMPTED steps; the device count (attempted - skipped) is what the kernel uses
-            items.append((p, g, st["exp_avg"], st["exp_avg_sq"]))
+            items.append((p, g, st["exp_avg"], st["exp_avg_sq"], st["max_exp_avg_sq"] if amsgrad else None))
             steps.append(st["step"])
         return items, steps, dev
 
-    def _launch_step(self, descs, n, gi, group, stream, step=None, sd=None, guard=None):
+    def _launch_step(self, descs, n, gi, group, stream, step=None, sd=None, guard=None, vmax=None):
         """The step's entry point for this optimizer: the record's row (hyper_on_device), else by value behind the guard record,
-        with the device step count `sd` (capturable), or with the host's bias corrections of `step`."""
+        with the device step count `sd` (capturable), or with the host's bias corrections of `step`.  A group with amsgrad,
+        maximize or the decoupled decay goes through the `_ext` form of the same entry point, with its flags and `vmax`, the array
+        of max_exp_avg_sq addresses parallel to descs (None without amsgrad); any other group through the entry points without it."""
+        flags = self._flags(group)
+        ext, more = ("_ext", (vmax, flags)) if flags else ("", ())
         if self._hyper_on_device:
-            _abi.call("wsmg_adam_step_multi_hyper", descs, n, self._hyper_row(gi), sd, guard, stream)
+            _abi.call("wsmg_adam_step_multi_hyper" + ext, descs, n, *more, self._hyper_row(gi), sd, guard, stream)
             return
         b1, b2 = group["betas"]
         by_value = (float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]))
         if guard is not None:
-            _abi.call("wsmg_adam_step_multi_guarded", descs, n, *by_value, sd, guard, stream)
+            _abi.call("wsmg_adam_step_multi_guarded" + ext, descs, n, *more, *by_value, sd, guard, stream)
         elif sd is not None:
-            _abi.call("wsmg_adam_step_multi_dev", descs, n, *by_value, sd, stream)
+            _abi.call("wsmg_adam_step_multi_dev" + ext, descs, n, *more, *by_value, sd, stream)
         else:
-            _abi.call("wsmg_adam_step_multi", descs, n, *by_value, 1.0 - b1 ** step, 1.0 - b2 ** step, stream)
+            _abi.call("wsmg_adam_step_multi" + ext, descs, n, *more, *by_value, 1.0 - b1 ** step, 1.0 - b2 ** step, stream)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -511,7 +564,8 @@ class Adam(torch.optim.Optimizer):
                             self._step_dev[key] = torch.full((), float(step - 1), device=dev, dtype=torch.float32)
                         self._step_dev[key].add_(1.0)      # on the device: a replayed graph advances it without the host
                         sd = _ptr(self._step_dev[key])
-                    self._launch_step(_adam_descs(items), len(items), gi, group, _stream(dev), step=step, sd=sd)
+                    self._launch_step(_adam_descs(items), len(items), gi, group, _stream(dev), step=step, sd=sd,
+                                      vmax=_vmax_ptrs(items))
                 # the kernel wrote the parameters through raw pointers: advance their autograd version counters, which is what
                 # caches of derived operands (FoldCache, InstructionEncoder.packed_rnn_weights) compare
                 torch.autograd.graph.increment_version([it[0] for it in items])
@@ -562,7 +616,8 @@ class Adam(torch.optim.Optimizer):
                           self._scan.numel() // 4, guard, sd, _ptr(self._report), _ptr(self._latch), stream)
             at = 0
             for gi, group, items in groups:
-                self._launch_step(ctypes.byref(descs, at * ctypes.sizeof(_AdamDesc)), len(items), gi, group, stream, sd=sd, guard=guard)
+                self._launch_step(ctypes.byref(descs, at * ctypes.sizeof(_AdamDesc)), len(items), gi, group, stream, sd=sd, guard=guard,
+                                  vmax=_vmax_ptrs(items))
                 at += len(items)
             written = [it[0] for it in every]
             if self._guard_buffers is not None:
@@ -650,3 +705,16 @@ class Adam(torch.optim.Optimizer):
             self._reset_guard()   # the guard record (skipped = 0) and its step count, from the loaded step counts; the report, zeroed
         if self._hyper_on_device:
             self._reset_hyper()   # the hyper record and its mirror, from the loaded param_groups
+
+
+class AdamW(Adam):
+    """torch.optim.AdamW on the same multi-tensor step: `Adam` with the decoupled weight decay (a non-zero `weight_decay` multiplies the
+    parameter by 1 - lr * weight_decay in front of the moments and is not added to the gradient) and torch.optim.AdamW's default
+    `weight_decay=1e-2`.  Every other argument, option and method is `Adam`'s; `state_dict()` is interchangeable with
+    torch.optim.AdamW's."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, maximize=False, **options):
+        if "decoupled_weight_decay" in options:
+            raise TypeError("wsmgmap.optim.AdamW is the decoupled form: it takes no decoupled_weight_decay argument")
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize,
+                         decoupled_weight_decay=True, **options)
