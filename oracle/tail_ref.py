@@ -1,7 +1,7 @@
 """The float64 yardstick of the update's loss tail (TEST INFRASTRUCTURE — part of oracle/).
 
 Plain torch restatements of the reference's lines that the small float32 kernels at the end of every update compute
-(csrc/wsmg_heads.hip, wsmg_loss.hip, and the ce_nhwc kernels of wsmg_pool.hip):
+(csrc/wsmg_heads.hip and wsmg_loss.hip, which holds path_kl and the ce_nhwc kernels):
 
     update_heads   models/policy.py:58-59,86-88,96-97   action mean, tanh progress head, its squared error per row
     aux_reduce     common/aux_losses.py:24-35            sum_k alpha_k * masked_select(loss_k, mask).mean()

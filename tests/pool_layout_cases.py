@@ -1,6 +1,6 @@
 """Inputs, float64 references and derived bars shared by test_pool_layout_cases_cpu.py and test_gpu_pool_layout_edges.py: the
-kernels of csrc/wsmg_pool.hip away from the square, even 3 x 64 x 12 x 12 case on which their older tests stand.  Nothing here touches a
-GPU.  Inputs are oracle.detfill values under tags of their own; every arithmetic reference is evaluated in float64 by torch / numpy
+kernels of csrc/wsmg_pool.hip and csrc/wsmg_layout.hip away from the square, even 3 x 64 x 12 x 12 case on which their older tests
+stand.  Nothing here touches a GPU.  Inputs are oracle.detfill values under tags of their own; every arithmetic reference is evaluated in float64 by torch / numpy
 on the CPU, for bf16 from the bf16-rounded operands; a reference that only moves values (a transpose, a weight re-layout) keeps its
 operand's type, because it has no arithmetic to round."""
 import functools

@@ -469,7 +469,7 @@ def test_maxpool_bwd_bf16_from_the_input():
 
 
 def test_upsample_bwd_bf16_twelve_channels():
-    """upsample_bwd_kernel<bf16>: 12 channels (not a multiple of 8), the gradient read in place as a channel slice of a 16-wide tensor
+    """upsample_bwdn_kernel<bf16, 4>: 12 channels (not a multiple of 8), the gradient read in place as a channel slice of a 16-wide tensor
     (wsmg_upsample2x_bwd_ld_bf16), against the float64 gradient of the bilinear align_corners upsampling; bar as
     test_small_ops_and_layout_bf16."""
     from wsmgmap import _abi, ops

@@ -1,5 +1,5 @@
 """GPU: the chain of small float32 kernels that ends every update in the scalar loss — update_heads, aux_reduce, dagger_loss
-(csrc/wsmg_heads.hip), path_kl (csrc/wsmg_loss.hip), ce_nhwc (csrc/wsmg_pool.hip) — beyond the bench shape and on bad batches:
+(csrc/wsmg_heads.hip), path_kl (csrc/wsmg_loss.hip), ce_nhwc (csrc/wsmg_loss.hip) — beyond the bench shape and on bad batches:
 the second chunk of the DAgger loss, the optional-gradient branches and the ragged last workgroup of the heads' backward, empty
 and single-row selections of the auxiliary reduction, non-square and degenerate geometries of the contrastive monitor's KL,
 extreme logits and out-of-range labels of the unfused cross-entropy.

@@ -1,5 +1,5 @@
-"""GPU: the pooling and layout kernels of csrc/wsmg_pool.hip away from the square, even 3 x 64 x 12 x 12 case on which their older tests
-stand: H != W in both orientations, odd sizes, channel counts that are no multiple of 8, every branch of the transpose dispatcher,
+"""GPU: the pooling kernels of csrc/wsmg_pool.hip and the layout kernels of csrc/wsmg_layout.hip away from the square, even
+3 x 64 x 12 x 12 case on which their older tests stand: H != W in both orientations, odd sizes, channel counts that are no multiple of 8, every branch of the transpose dispatcher,
 KH != KW weights.  Inputs, float64 references and derived bars are those of tests/pool_layout_cases.py (checked on the CPU by
 tests/test_pool_layout_cases_cpu.py); a bar copied from an older test is quoted at its assert.  Direct C-ABI calls write into buffers
 with NaN guards on both sides: only the tensor's own extent may change.
@@ -9,9 +9,10 @@ Section, kernels it pins, and the test that held them before:
                — test_gpu_kernels.py::test_small_nhwc_ops / test_small_ops_and_layout_bf16 (12 x 12, through autograd) and
                test_gpu_kernel_instances.py::test_maxpool_bwd_bf16_from_the_input (12 x 12); nothing read the index words
 2. avg-pool    avgpool_fwd_kernel / avgpool_bwd_kernel <f32 | bf16> — the same two 12 x 12 tests
-   upsampling  upsample_fwd_kernel<f32 | bf16> — the same two; upsample_bwd_kernel<f32 | bf16> and upsample_bwd8_kernel at H = 1 / W = 1
+   upsampling  upsample_fwd_kernel<f32 | bf16> — the same two; upsample_bwdn_kernel<f32, 4 | bf16, 4 | bf16, 8> at H = 1 / W = 1
                — test_gpu_round6.py::test_upsample_backward_with_eight_channels_per_thread and
-               test_gpu_kernel_instances.py::test_upsample_bwd_bf16_twelve_channels hold them at other non-square sizes
+               test_gpu_kernel_instances.py::test_upsample_bwd_bf16_twelve_channels hold them at other non-square sizes;
+               test_upsample_backward_is_the_same_bits_at_either_channel_width holds the 4- and the 8-channel form to each other
 3. transposes  nchw_to_nhwc64_kernel<f32 | bf16>, transpose_kernel<true, f32, f32 | bf16>, transpose_kernel<false, f32 | bf16, f32>
                — test_gpu_kernels.py::test_layout_roundtrip_and_padding / test_small_ops_and_layout_bf16 (27 -> 32 at 48 x 48, 64 at 100 x 100)
 4. merge       token_grad_merge_kernel<f32 | bf16> — no test of its own (whole-policy gradients of test_gpu_policy.py / test_gpu_round2.py)
@@ -29,6 +30,7 @@ import pytest
 import torch
 
 import pool_layout_cases as pc
+from oracle import detfill as df
 from pool_layout_cases import BF16_EPS, T, nchw, nhwc
 
 pytestmark = pytest.mark.gpu
@@ -258,6 +260,40 @@ def test_upsample_forward_and_the_one_row_one_column_backward(ops, geom, dtype):
     one input row / column) — other non-square backward sizes are held by test_upsample_backward_with_eight_channels_per_thread and
     test_upsample_bwd_bf16_twelve_channels."""
     _smooth(ops, "upsample", ops.upsample2x, geom, dtype, geom[1] == 1 or geom[2] == 1)
+
+
+# (B, H, W, C, ld_dy), the smallest sizes at which the lists of candidate output rows / columns differ: one source with both scales 0;
+# H = 2, where an input row is read by six output rows; a 16-channel slice of a 24-channel gradient read in place; 5 x 4
+UPSAMPLE_BWD_WIDTH_GEOMS = [(1, 1, 1, 8, 8), (1, 2, 3, 8, 8), (2, 3, 2, 16, 24), (1, 5, 4, 8, 8)]
+
+
+@pytest.mark.parametrize("geom", UPSAMPLE_BWD_WIDTH_GEOMS, ids=pc.geom_id)
+def test_upsample_backward_is_the_same_bits_at_either_channel_width(geom):
+    """wsmg_upsample2x_bwd_ld_bf16 called directly, twice on the same 16-byte-aligned dy: into a 16-byte-aligned dx (8 channels per
+    thread) and into a dx that starts 8 bytes into a larger buffer (4 channels per thread).  The two results are the same bits, and
+    each is the float64 gradient of F.interpolate(scale_factor=2, mode="bilinear", align_corners=True) under the bf16 bar of this
+    module's other upsample tests, so an error the two widths share cannot hide.  Where ld_dy > C the slice is the gradient's LAST C
+    channels (its first channel is 16 bytes in, still aligned); the others are never read."""
+    B, H, W, C, ld = geom
+    n, c0 = B * H * W * C, ld - C
+    full = T(df.uniform("pledge.upsample_bwd_width." + pc.geom_id(geom), (B, 2 * H, 2 * W, ld), 2.0)).to(torch.bfloat16)
+    dy = full.cuda()
+    dyp = ctypes.c_void_p(dy.data_ptr() + 2 * c0)
+    assert dyp.value % 16 == 0
+    wide = Guarded((B, H, W, C), torch.bfloat16)
+    call("wsmg_upsample2x_bwd_ld_bf16", dyp, ld, P(wide.t), B, H, W, C, S())
+    room = Guarded((n + 8,), torch.bfloat16)
+    narrow = room.t[4:4 + n].view(B, H, W, C)
+    assert narrow.data_ptr() % 16 == 8
+    call("wsmg_upsample2x_bwd_ld_bf16", dyp, ld, P(narrow), B, H, W, C, S())
+    assert wide.guards_intact() and room.guards_intact()
+    assert bool(torch.isnan(room.t[:4]).all()) and bool(torch.isnan(room.t[4 + n:]).all())
+    name = "upsample_bwd_width." + pc.geom_id(geom)
+    exact(name + ".8_against_4", wide.t, narrow)
+    xr = torch.zeros(B, C, H, W, dtype=torch.float64, requires_grad=True)
+    pc._up(xr).backward(nchw(full[..., c0:].double()))
+    close(name + ".dx(8 per thread)", nchw(wide.t.float()), xr.grad, BF16_EPS, 1e-6)
+    close(name + ".dx(4 per thread)", nchw(narrow.float()), xr.grad, BF16_EPS, 1e-6)
 
 
 # ============================================================================= 3. transposes

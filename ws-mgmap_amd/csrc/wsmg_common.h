@@ -58,6 +58,14 @@ static inline int wsmg_tune_read(const char* name, int dflt) {
 
 static inline int64_t wsmg_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// workgroups of a grid-stride launch of 256 threads over n items (wsmg_pool.hip, wsmg_layout.hip): 1 .. 16384
+static inline int wsmg_sgrid(int64_t n) {
+  int64_t g = wsmg_cdiv(n, 256);
+  if (g > 16384) g = 16384;
+  if (g < 1) g = 1;
+  return (int)g;
+}
+
 // Multi-tensor launches (wsmg_optim.hip's Adam / norm kernels, wsmg_small.hip's guarded copy): tensors per launch — the table lives
 // in the kernel arguments, a longer list is cut into several launches — and the guard record of wsmg_grad_norm_multi, four float32.
 constexpr int ADAM_MAX = 48;

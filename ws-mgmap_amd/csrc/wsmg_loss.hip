@@ -1,4 +1,7 @@
-// The contrastive-monitor auxiliary loss of the update path (policy.py:72-82 of the reference) in one launch per direction:
+// The update path's two dense losses, each one launch per direction: path_kl, the contrastive-monitor auxiliary loss (below), and
+// ce_nhwc, the per-pixel cross-entropy of the semantic-map head over NHWC logits (second half of the file).
+//
+// path_kl (policy.py:72-82 of the reference):
 //
 //   t  = (hi - dis) / (hi - lo)                 dis = gt_path [B][H][W]; lo, hi = its batch-global min / max (device scalars)
 //   a  = area-resize(t, S x S)                  = adaptive average pooling: bin i = [floor(i H / S), ceil((i + 1) H / S))
@@ -75,6 +78,90 @@ __global__ __launch_bounds__(256) void path_kl_bwd_kernel(const float* __restric
   datt[i] = -gkl[i / n] * target[i] / att[i] / (float)n;
 }
 
+// ---- fused per-pixel cross-entropy over NHWC logits (policy.py:61-66: F.cross_entropy(pred_sem_map, target,
+// reduction='none')): the 27 classes of a pixel are one 64/128-byte run of the 32-channel-padded conv output, so the
+// loss needs no NHWC->NCHW transpose and no materialised log-softmax.  One thread per pixel row.
+// A label outside [0, classes) — F.cross_entropy of the reference faults on it — makes that row's loss and its whole 32-wide
+// gradient row NaN, as the fused classifier tail does (wsmg_cls_tail.hip): loud, not a finite wrong number.  The int64 label
+// itself is compared (2^40 truncates to 0); -100 is not an ignore_index.
+template <class T>
+__device__ __forceinline__ void ce_row_load(const T* __restrict__ row, float (&v)[32]) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    f32x4 q = ld4(row + 4 * j);
+    v[4 * j] = q[0]; v[4 * j + 1] = q[1]; v[4 * j + 2] = q[2]; v[4 * j + 3] = q[3];
+  }
+}
+// v: the row's logits in, exp(v[c] - mx) out (0 for the padded classes c >= classes); mx the maximum over the classes, sum the sum
+// of the exponentials in c order
+__device__ __forceinline__ void ce_row_softmax(float (&v)[32], int classes, float& mx, float& sum) {
+  mx = -INFINITY;
+#pragma unroll
+  for (int c = 0; c < 32; ++c) if (c < classes) mx = fmaxf(mx, v[c]);
+  sum = 0.f;
+#pragma unroll
+  for (int c = 0; c < 32; ++c) { v[c] = c < classes ? expf(v[c] - mx) : 0.f; sum += v[c]; }
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void ce_nhwc_fwd_kernel(const T* __restrict__ logits, const int64_t* __restrict__ target,
+                                                          int64_t rows, int classes, float* __restrict__ loss) {
+  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (r >= rows) return;
+  float v[32], mx, sum;
+  ce_row_load(logits + r * 32, v);
+  const int64_t lab = target[r];
+  const bool in_range = (uint64_t)lab < (uint64_t)classes;
+  const int t = in_range ? (int)lab : -1;
+  float vt = 0.f;
+#pragma unroll
+  for (int c = 0; c < 32; ++c) if (c == t) vt = v[c];
+  ce_row_softmax(v, classes, mx, sum);
+  loss[r] = in_range ? (mx + logf(sum)) - vt : __builtin_nanf("");
+}
+
+// dlogits[r][c] = (softmax(logits[r])[c] - [c == target[r]]) * gloss[r]; padded channels get 0; a row whose label is outside
+// [0, classes) gets NaN in all 32 channels
+template <class T>
+__global__ __launch_bounds__(256) void ce_nhwc_bwd_kernel(const T* __restrict__ logits, const int64_t* __restrict__ target,
+                                                          const float* __restrict__ gloss, int64_t rows, int classes,
+                                                          T* __restrict__ dlogits) {
+  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (r >= rows) return;
+  float v[32], mx, sum;
+  ce_row_load(logits + r * 32, v);
+  ce_row_softmax(v, classes, mx, sum);
+  const float g = gloss[r], inv = 1.f / sum;
+  const int64_t lab = target[r];
+  const bool in_range = (uint64_t)lab < (uint64_t)classes;
+  const int t = in_range ? (int)lab : -1;
+  const float nan = __builtin_nanf("");
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    f32x4 q;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int c = 4 * j + e;
+      const float d = c < classes ? (v[c] * inv - (c == t ? 1.f : 0.f)) * g : 0.f;
+      q[e] = in_range ? d : nan;
+    }
+    st4(dlogits + r * 32 + 4 * j, q);
+  }
+}
+
+template <class T>
+int ce_nhwc_fwd_t(const T* logits, const int64_t* target, int64_t rows, int classes, float* loss, wsmg_stream_t s) {
+  if (rows <= 0 || classes <= 0 || classes > 32) return WSMG_EINVAL;
+  hipLaunchKernelGGL(ce_nhwc_fwd_kernel<T>, dim3((unsigned)wsmg_cdiv(rows, 256)), dim3(256), 0, wsmg_s(s), logits, target, rows, classes, loss);
+  WSMG_RETURN_LAUNCH();
+}
+template <class T>
+int ce_nhwc_bwd_t(const T* logits, const int64_t* target, const float* gloss, int64_t rows, int classes, T* dlogits, wsmg_stream_t s) {
+  if (rows <= 0 || classes <= 0 || classes > 32) return WSMG_EINVAL;
+  hipLaunchKernelGGL(ce_nhwc_bwd_kernel<T>, dim3((unsigned)wsmg_cdiv(rows, 256)), dim3(256), 0, wsmg_s(s), logits, target, gloss, rows, classes, dlogits);
+  WSMG_RETURN_LAUNCH();
+}
+
 }  // namespace
 
 extern "C" int wsmg_path_kl_fwd(const float* dis, const float* lo, const float* hi, const float* att, int B, int H, int W, int S, float tau,
@@ -90,3 +177,8 @@ extern "C" int wsmg_path_kl_bwd(const float* gkl, const float* target, const flo
   hipLaunchKernelGGL(path_kl_bwd_kernel, dim3((unsigned)wsmg_cdiv(total, 256)), dim3(256), 0, wsmg_s(s), gkl, target, att, total, n, datt);
   WSMG_RETURN_LAUNCH();
 }
+
+extern "C" int wsmg_ce_nhwc_fwd(const float* logits, const int64_t* target, int64_t rows, int classes, float* loss, wsmg_stream_t s) { return ce_nhwc_fwd_t<float>(logits, target, rows, classes, loss, s); }
+extern "C" int wsmg_ce_nhwc_fwd_bf16(const void* logits, const int64_t* target, int64_t rows, int classes, float* loss, wsmg_stream_t s) { return ce_nhwc_fwd_t<bf16_t>((const bf16_t*)logits, target, rows, classes, loss, s); }
+extern "C" int wsmg_ce_nhwc_bwd(const float* logits, const int64_t* target, const float* gloss, int64_t rows, int classes, float* dlogits, wsmg_stream_t s) { return ce_nhwc_bwd_t<float>(logits, target, gloss, rows, classes, dlogits, s); }
+extern "C" int wsmg_ce_nhwc_bwd_bf16(const void* logits, const int64_t* target, const float* gloss, int64_t rows, int classes, void* dlogits, wsmg_stream_t s) { return ce_nhwc_bwd_t<bf16_t>((const bf16_t*)logits, target, gloss, rows, classes, (bf16_t*)dlogits, s); }

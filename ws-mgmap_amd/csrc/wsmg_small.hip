@@ -7,6 +7,8 @@
 // in front of the GEMM, and the heads are ~20 element-wise launches on two numbers per row: the rollout step is bound by its
 // launch count (≈200 launches of ≈5 us), not by arithmetic.  Here a layer is ONE launch — one workgroup per output feature,
 // the weight row read once with 16-byte loads and reused for up to 8 rows at a time — and the heads are one launch per step.
+// Beside them the other small launches that stand for a list of torch ops: a list of device-to-device copies (plain and guarded),
+// mean_rows (the mean over a short innermost axis), and the column sums behind the recurrent core's bias gradients.
 #include "wsmg_common.h"
 
 namespace {
@@ -184,7 +186,33 @@ __global__ __launch_bounds__(256) void copy_multi_guarded_kernel(GuardedCopyBatc
   for (long long i = v1 + threadIdx.x; i < i1; i += 256) d[i] = s[i];
 }
 
+// ---- mean over a short innermost axis: out[r] = mean(x[r][0..n)), x [R][n] float32 contiguous (rgb_linear's AdaptiveAvgPool1d(1)
+// over the 7 x 7 positions of the cached RGB feature, mg_map_policy.py:90-96: R = B * 512 rows of n = 49).  A thread per row would
+// read 196-byte rows 196 bytes apart; here a workgroup loads its 256 rows as one contiguous, coalesced run into LDS and every
+// thread adds its row from there (row pitch n floats: conflict-free for odd n).
+__global__ __launch_bounds__(256) void mean_rows_kernel(const float* __restrict__ x, int64_t R, int n, float* __restrict__ out) {
+  extern __shared__ float rows_lds[];
+  const int64_t r0 = (int64_t)blockIdx.x * 256;
+  const int nr = R - r0 < 256 ? (int)(R - r0) : 256;
+  const float* src = x + r0 * n;
+  const int total = nr * n;
+  for (int i = threadIdx.x; i < total; i += 256) rows_lds[i] = src[i];
+  __syncthreads();
+  if ((int)threadIdx.x < nr) {
+    float s = 0.f;
+    const float* p = rows_lds + threadIdx.x * n;
+    for (int j = 0; j < n; ++j) s += p[j];
+    out[r0 + threadIdx.x] = s / (float)n;
+  }
+}
+
 }  // namespace
+
+extern "C" int wsmg_mean_rows(const float* x, int64_t R, int n, float* out, wsmg_stream_t s) {
+  if (!x || !out || R <= 0 || n <= 0 || n > 160) return WSMG_EINVAL;       // 256 rows x n floats of LDS
+  hipLaunchKernelGGL(mean_rows_kernel, dim3((unsigned)wsmg_cdiv(R, 256)), dim3(256), (size_t)256 * n * sizeof(float), wsmg_s(s), x, R, n, out);
+  WSMG_RETURN_LAUNCH();
+}
 
 extern "C" int wsmg_copy_multi_guarded(const WsmgCopyDesc* descs, int n, const float* guard, wsmg_stream_t stream) {
   if (!descs || !guard || n <= 0 || ((uintptr_t)guard & 3)) return WSMG_EINVAL;
