@@ -812,6 +812,39 @@ int wsmg_dagger_loss_fwd(const float* pred, const float* waypoint, int ld_waypoi
 int wsmg_dagger_loss_bwd(const float* pred, const float* waypoint, int ld_waypoint, const float* weights, const float* den,
                          const float* dloss, int T, int N, int A, float* dpred, wsmg_stream_t stream);
 
+/* ---- the policy-gradient heads and the PPO loss (csrc/wsmg_pg_heads.hip) ---------------------------------------------------
+ * What habitat's `Policy.evaluate_actions` / `PPO.update` compute after the second recurrence (habitat's interface: the reference's
+ * policy has `act` only), each as ONE launch per direction; float32, every sum in a fixed order (bit-reproducible), no atomics.
+ *   wsmg_eval_heads_*: on x [B][K] (K % 4 == 0, B >= 1) with wm [A][K], bm [A], logstd [A] (A <= 4), wc [K], bc [1], action [B][A]:
+ *       mean = x wm^T + bm (kept for the backward), value = x wc^T + bc, sigma = exp(logstd),
+ *       logp[b] = sum_a( -(action - mean)^2 / (2 sigma^2) - logstd_a - 0.5 log(2 pi) ) (common/distributions.py:21-29,42-57),
+ *       entropy[0] = sum_a( 0.5 + 0.5 log(2 pi) + logstd_a ), the same for every row and so also the batch mean.
+ *       backward: dvalue [B] / dlogp [B] / dentropy [1] may each be NULL (zero); dx, dwm, dbm, dlogstd, dwc, dbc are overwritten;
+ *       d mean = dlogp (action - mean) / sigma^2, dlogstd_a = sum_b dlogp_b ((action - mean)^2 / sigma^2 - 1) + dentropy.
+ *   wsmg_ppo_loss_*: the clipped-surrogate loss of habitat-baselines' PPO.update over rows logp, old_logp, adv, value, old_value,
+ *       ret [B] (1 <= B <= 2^20: one workgroup walks them), mask [B] (bool) or NULL, entropy [1]:
+ *       ratio = exp(logp - old_logp), action_loss = -mean(min(ratio adv, clamp(ratio, 1 - clip, 1 + clip) adv)),
+ *       value_loss = 0.5 mean(max((value - ret)^2, (vc - ret)^2)) with vc = old_value + clamp(value - old_value, -clip, clip) when
+ *       clipped_value != 0, else 0.5 mean((ret - value)^2); loss = value_coef value_loss + action_loss - entropy_coef entropy.
+ *       Means run over the rows with mask[b] != 0 (dropped, not multiplied; none selected: NaN).
+ *       out5 = {loss, action_loss, value_loss, mean(|ratio - 1| > clip), mean(old_logp - logp)}; nsel [1] = the number of selected
+ *       rows, kept for the backward, which writes dlogp [B], dvalue [B], dentropy [1] from dloss [1] with torch autograd's
+ *       conventions: min / max of two equal terms give each term half (inside the clip range the two halves meet again), clamp
+ *       passes the gradient on its closed interval; a row left out gets 0 * dloss / nsel (NaN when no row is selected). */
+int wsmg_eval_heads_fwd(const float* x, const float* wm, const float* bm, const float* logstd, const float* wc, const float* bc,
+                        const float* action, int B, int K, int A, float* value, float* logp, float* mean, float* entropy,
+                        wsmg_stream_t stream);
+int wsmg_eval_heads_bwd(const float* x, const float* wm, const float* wc, const float* logstd, const float* action, const float* mean,
+                        const float* dvalue, const float* dlogp, const float* dentropy, int B, int K, int A, float* dx, float* dwm,
+                        float* dbm, float* dlogstd, float* dwc, float* dbc, wsmg_stream_t stream);
+int wsmg_ppo_loss_fwd(const float* logp, const float* old_logp, const float* adv, const float* value, const float* old_value,
+                      const float* ret, const unsigned char* mask, const float* entropy, float clip, float value_coef,
+                      float entropy_coef, int clipped_value, int B, float* out5, float* nsel, wsmg_stream_t stream);
+int wsmg_ppo_loss_bwd(const float* logp, const float* old_logp, const float* adv, const float* value, const float* old_value,
+                      const float* ret, const unsigned char* mask, const float* nsel, const float* dloss, float clip,
+                      float value_coef, float entropy_coef, int clipped_value, int B, float* dlogp, float* dvalue, float* dentropy,
+                      wsmg_stream_t stream);
+
 /* ---- the semantic classifier's tail in one pass per direction (csrc/wsmg_cls_tail.hip) -----------------------------------
  * Reference: `map_classfier[4:7]` = BatchNorm2d(32) + ReLU + Conv2d(32, 27, 1) (mg_map_policy.py:78-86), the prediction monitor's
  * `F.cross_entropy(pred_sem_map, F.interpolate(gt_semantic_map, size=(48, 48)).long(), reduction='none').mean([1, 2])`

@@ -78,6 +78,38 @@ class BasePolicy(nn.Module):
         action = distribution.mode() if deterministic else distribution.sample()
         return value, action, distribution.log_probs(action), rnn_hidden_states
 
+    # -- policy-gradient surface (habitat's Policy interface; the reference's policy has `act` only) ------------
+    def get_value(self, observations, rnn_hidden_states, prev_actions, masks):
+        """habitat's `Policy.get_value`: the critic on the net's features, [B, 1]."""
+        features, _, _ = self.net(observations, rnn_hidden_states, prev_actions, masks)
+        if ops.rows_route(features):
+            return ops.linear_rows(features, self.critic.fc.weight, self.critic.fc.bias)
+        return self.critic(features)
+
+    def evaluate_actions(self, observations, rnn_hidden_states, prev_actions, masks, action):
+        """habitat's `Policy.evaluate_actions` -> (value [B,1], action_log_probs [B], distribution_entropy 0-dim,
+        rnn_hidden_states): what a PPO / A2C update differentiates.  The net runs as in `forward()` with no auxiliary loss
+        active; nothing is registered with AuxLosses and `self.prog` is left alone."""
+        self.net.skip_pred_map_nchw = True   # pred_sem_map has no consumer here
+        self.net._gt_semantic_map = None
+        self.net._cls_tail_allowed = True
+        try:
+            features, rnn_hidden_states, _ = self.net(observations, rnn_hidden_states, prev_actions, masks)
+        finally:
+            self.net.skip_pred_map_nchw = False
+            self.net._gt_semantic_map = None
+            self.net._cls_tail_allowed = False
+        ad = self.action_distribution
+        if ops.eval_heads_ok(features, ad.fc_mean.out_features) and action.is_cuda and action.dtype == torch.float32:
+            # critic, action mean, log-probability and entropy in one launch per direction (≈45 each way otherwise)
+            value, logp, entropy = ops.eval_heads(features, ad.fc_mean, ad.logstd._bias, self.critic.fc, action)
+        else:
+            distribution = ad(features)
+            value = self.critic(features)
+            logp = distribution.log_probs(action)
+            entropy = distribution.entropy().mean()
+        return value, logp, entropy, rnn_hidden_states
+
     # -- auxiliary heads -------------------------------------------------------------
     def aux_prediction(self, features, observations, pred_map, prog=None, prog_rows=None):
         """prog: the progress head's output when the caller already has it (the fused heads of act / forward); prog_rows: the

@@ -416,6 +416,124 @@ def dagger_loss(pred, aux_loss, waypoint, weights):
     return loss, action
 
 
+# ----------------------------------------------------------------------------- policy-gradient heads and the PPO loss
+EVAL_HEADS_MAX_A = 4      # the limits of csrc/wsmg_pg_heads.hip (and of update_heads): A <= 4, K % 4 == 0
+PPO_MAX_ROWS = 1 << 20
+
+
+class _EvalHeads(torch.autograd.Function):
+    """(value [B,1], logp [B], entropy 0-dim) of habitat's `Policy.evaluate_actions` in one launch per direction
+    (csrc/wsmg_pg_heads.hip): `CriticHead`, `DiagGaussian` and the patched Normal's `log_probs` / `entropy().mean()`
+    (common/distributions.py:21-29,42-57 of the reference)."""
+
+    @staticmethod
+    def forward(ctx, x, wm, bm, logstd, wc, bc, action):
+        _req(x, wm, bm, logstd, wc, bc, action)
+        _f32(x, wm, bm, logstd, wc, bc, action)
+        if x.dim() != 2 or wm.dim() != 2:
+            raise _abi.WsmgError("eval_heads: features [B, K] and an fc_mean weight [A, K]")
+        B, K = x.shape
+        A = wm.shape[0]
+        if (wm.shape != (A, K) or bm.numel() != A or logstd.numel() != A or wc.numel() != K or bc.numel() != 1
+                or tuple(action.shape) != (B, A)):
+            raise _abi.WsmgError("eval_heads: head shapes do not fit the features, or action is not [B, A]")
+        if B < 1 or K % 4 or not 1 <= A <= EVAL_HEADS_MAX_A:
+            raise _abi.WsmgError(f"eval_heads: B >= 1, K % 4 == 0 and 1 <= A <= {EVAL_HEADS_MAX_A}, got B = {B}, K = {K}, A = {A}")
+        if any(t.data_ptr() % 16 for t in (x, wm, wc)):     # the forward reads them four floats at a time
+            raise _abi.WsmgError("eval_heads: features, fc_mean.weight and critic.fc.weight must start on a 16-byte boundary "
+                                 "(a view with a storage offset that is no multiple of 4 floats: clone it)")
+        dev = x.device
+        value, logp = torch.empty(B, 1, device=dev), torch.empty(B, device=dev)
+        mean, ent = torch.empty(B, A, device=dev), torch.empty(1, device=dev)
+        _abi.call("wsmg_eval_heads_fwd", _p(x), _p(wm), _p(bm), _p(logstd), _p(wc), _p(bc), _p(action), B, K, A, _p(value), _p(logp),
+                  _p(mean), _p(ent), _stream())
+        ctx.save_for_backward(x, wm, wc, logstd, action, mean)
+        ctx.set_materialize_grads(False)
+        return value, logp, ent[0]
+
+    @staticmethod
+    def backward(ctx, dvalue, dlogp, dent):
+        x, wm, wc, logstd, action, mean = ctx.saved_tensors
+        B, K = x.shape
+        A = wm.shape[0]
+        c = lambda t: None if t is None else t.contiguous().float()   # noqa: E731
+        dvalue, dlogp, dent = c(dvalue), c(dlogp), c(dent)
+        dev = x.device
+        dx, dwm, dwc = torch.empty_like(x), torch.empty_like(wm), torch.empty_like(wc)
+        dbm, dbc, dls = torch.empty(A, device=dev), torch.empty(1, device=dev), torch.empty_like(logstd)
+        _abi.call("wsmg_eval_heads_bwd", _p(x), _p(wm), _p(wc), _p(logstd), _p(action), _p(mean), _p(dvalue), _p(dlogp), _p(dent), B, K, A,
+                  _p(dx), _p(dwm), _p(dbm), _p(dls), _p(dwc), _p(dbc), _stream())
+        return dx, dwm, dbm, dls, dwc, dbc, None
+
+
+def eval_heads_ok(features, action_dim):
+    """Can `eval_heads` take these features?  float32 [B >= 1, K % 4 == 0] on the GPU, at most 4 action dimensions."""
+    return (features.is_cuda and features.dtype == torch.float32 and features.dim() == 2 and features.shape[0] >= 1
+            and features.shape[1] % 4 == 0 and 1 <= action_dim <= EVAL_HEADS_MAX_A)
+
+
+def eval_heads(features, fc_mean, logstd, critic_fc, action):
+    """-> (value [B,1], logp [B], entropy 0-dim): the critic, sum_a Normal(fc_mean(f), exp(logstd)).log_prob(action) and the
+    distribution's entropy (the same for every row, so also its batch mean), one launch per direction.  fc_mean / critic_fc: the
+    nn.Linear modules; logstd: the [A, 1] parameter of DiagGaussian.logstd (its gradient comes back in that shape); action [B, A]
+    takes no gradient."""
+    return _EvalHeads.apply(features.contiguous(), fc_mean.weight, fc_mean.bias, logstd, critic_fc.weight, critic_fc.bias,
+                            action.contiguous())
+
+
+class _PpoLoss(torch.autograd.Function):
+    """The clipped-surrogate loss of habitat-baselines' PPO.update in one launch per direction (csrc/wsmg_pg_heads.hip)."""
+
+    @staticmethod
+    def forward(ctx, logp, value, entropy, old_logp, adv, old_value, returns, mask, clip, value_coef, entropy_coef, clipped_value):
+        rows = (logp, old_logp, adv, value, old_value, returns)
+        _req(*rows, entropy, mask)
+        _f32(*rows, entropy)
+        B = logp.numel()
+        if B < 1 or B > PPO_MAX_ROWS or any(r.numel() != B for r in rows) or entropy.numel() != 1:
+            raise _abi.WsmgError(f"ppo_loss: six float32 row vectors of one length in [1, {PPO_MAX_ROWS}] and a one-element entropy, got "
+                                 f"{[tuple(r.shape) for r in rows]} and {tuple(entropy.shape)}")
+        if mask is not None and (mask.dtype not in (torch.bool, torch.uint8) or mask.numel() != B):
+            raise _abi.WsmgError(f"ppo_loss: mask must be bool or uint8 with one entry per row ({B})")
+        out = torch.empty(5, device=logp.device, dtype=torch.float32)
+        nsel = torch.empty(1, device=logp.device, dtype=torch.float32)
+        _abi.call("wsmg_ppo_loss_fwd", _p(logp), _p(old_logp), _p(adv), _p(value), _p(old_value), _p(returns), _p(mask), _p(entropy),
+                  clip, value_coef, entropy_coef, int(clipped_value), B, _p(out), _p(nsel), _stream())
+        ctx.save_for_backward(logp, old_logp, adv, value, old_value, returns, mask, nsel)
+        ctx.hyper = (clip, value_coef, entropy_coef, int(clipped_value))
+        ctx.shapes = (logp.shape, value.shape, entropy.shape)
+        outs = tuple(out[i] for i in range(5))
+        ctx.mark_non_differentiable(*outs[1:])
+        return outs
+
+    @staticmethod
+    def backward(ctx, dloss, *_):
+        logp, old_logp, adv, value, old_value, returns, mask, nsel = ctx.saved_tensors
+        B = logp.numel()
+        dloss = dloss.contiguous().float().reshape(1)
+        dev = logp.device
+        dlogp, dvalue, dent = torch.empty(B, device=dev), torch.empty(B, device=dev), torch.empty(1, device=dev)
+        _abi.call("wsmg_ppo_loss_bwd", _p(logp), _p(old_logp), _p(adv), _p(value), _p(old_value), _p(returns), _p(mask), _p(nsel),
+                  _p(dloss), *ctx.hyper, B, _p(dlogp), _p(dvalue), _p(dent), _stream())
+        s_logp, s_value, s_ent = ctx.shapes
+        return (dlogp.view(s_logp), dvalue.view(s_value), dent.view(s_ent)) + (None,) * 9
+
+
+def ppo_loss(logp, old_logp, adv, value, old_value, returns, entropy, clip, value_coef, entropy_coef, clipped_value=True, mask=None):
+    """-> (loss, action_loss, value_loss, clip_frac, approx_kl), 0-dim tensors; only `loss` is differentiable, towards logp,
+    value and entropy (old_logp, adv, old_value and returns take no gradient).
+        ratio = exp(logp - old_logp);  action_loss = -mean(min(ratio adv, clamp(ratio, 1 - clip, 1 + clip) adv))
+        value_loss = 0.5 mean(max((value - returns)^2, (vc - returns)^2)), vc = old_value + clamp(value - old_value, -clip, clip)
+                     (clipped_value=False: 0.5 mean((returns - value)^2))
+        loss = value_coef value_loss + action_loss - entropy_coef entropy
+        clip_frac = mean(|ratio - 1| > clip);  approx_kl = mean(old_logp - logp)
+    The rows are float32 GPU tensors with B elements each ([B] or [B, 1]); entropy has one element; mask [B] bool or uint8 selects
+    the rows the means run over (none selected: NaN, as `aux_reduce`)."""
+    c = lambda t: t.contiguous()    # noqa: E731
+    return _PpoLoss.apply(c(logp), c(value), c(entropy), c(old_logp), c(adv), c(old_value), c(returns),
+                          None if mask is None else c(mask), float(clip), float(value_coef), float(entropy_coef), bool(clipped_value))
+
+
 ROWS_MAX = 16     # rollout-size dense layers: up to this many rows go through linear_rows / act_heads
 
 
