@@ -154,6 +154,31 @@ def test_update_heads_without_progress_returns_no_rows():
         assert _err(got, leaf.grad) <= 2e-6 * max(float(leaf.grad.abs().max()), 1e-3), name
 
 
+def test_update_heads_is_repeatable_to_the_bit():
+    """B % 32 != 0 (row groups of unequal length), K % 8 != 0 (a half-dead last column workgroup) and the widest A through the
+    column-owned backward, all three outputs used: two runs give the same bits in every output and every gradient."""
+    import copy
+    from wsmgmap import ops
+    B, K, A = 33, 516, 4
+    x, fc, pp, progress, gs = _heads_inputs(B, K, A)
+
+    def run():
+        xg = x.cuda().requires_grad_(True)
+        fcg, ppg = copy.deepcopy(fc).cuda(), copy.deepcopy(pp).cuda()
+        outs = ops.update_heads(xg, fcg, ppg, progress.cuda())
+        _heads_loss("all_three", outs, [g.cuda() for g in gs]).backward()
+        torch.cuda.synchronize()
+        named = dict(zip(("pred", "prog", "prog_rows"), (o.detach() for o in outs)))
+        named.update(dx=xg.grad, dWm=fcg.weight.grad, dbm=fcg.bias.grad, dWp=ppg.weight.grad, dbp=ppg.bias.grad)
+        return named
+
+    a, b = run(), run()
+    assert len(a) == 8
+    for k in a:
+        assert a[k] is not None and torch.isfinite(a[k]).all(), k
+        assert torch.equal(a[k], b[k]), k
+
+
 # ----------------------------------------------------------------------------- aux_reduce
 def _aux_both(rows, alphas, mask):
     from wsmgmap import ops

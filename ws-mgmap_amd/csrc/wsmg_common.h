@@ -86,6 +86,22 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+// The sum over a workgroup of 256 threads, valid in every thread, in a fixed order: the wave's xor tree, then the four waves in
+// index order.  red: four LDS words.  The float form may be called again on the same red at once (it waits before it writes);
+// the double form does not wait: a kernel gives each of its sums a red of its own.
+__device__ __forceinline__ float block_sum(float v, float* red) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return red[0] + red[1] + red[2] + red[3];
+}
+__device__ __forceinline__ double block_sum_d(double v, double* red) {
+  v = wave_sum_d(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return red[0] + red[1] + red[2] + red[3];
+}
 
 // wsmg_conv_win.hip: direct convolution with an LDS-resident input window (64 -> 64 channels, k8 s2 p3); WSMG_EINVAL for
 // any other shape

@@ -14,12 +14,12 @@
 //   update_heads_bwd_kernel   d loss rows, d features, d Wm, d bm, d Wp, d bp — every sum in a fixed order (no atomics)
 //
 // float32 throughout; the masked rows are DROPPED (selected), not multiplied by zero, as the reference's masked_select does.
-#include "wsmg_common.h"
+// The two heads kernels' row projection and column-owned backward are wsmg_heads_common.h's, shared with wsmg_pg_heads.hip.
+#include "wsmg_heads_common.h"
 
 namespace {
 
-constexpr int MAXA = 4;     // action dimensions (the reference's waypoint head has 2)
-constexpr int MAXL = 4;     // auxiliary loss vectors in one reduction (the reference registers 3)
+constexpr int MAXL = 4;    // auxiliary loss vectors in one reduction (the reference registers 3)
 
 struct HeadsFwd {
   const float* x;      // [B][K]
@@ -34,47 +34,24 @@ struct HeadsFwd {
   int B, K, A;
 };
 
-// one wave per row: lane l holds 8 consecutive features per 512-feature pass
+// one wave per row (heads_row_dots); lane 0 adds the biases, the tanh and the progress loss row
 __global__ __launch_bounds__(256) void update_heads_fwd_kernel(HeadsFwd a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int b = blockIdx.x * 4 + wave;
   if (b >= a.B) return;
-  float s[MAXA + 1];
-#pragma unroll
-  for (int o = 0; o <= MAXA; ++o) s[o] = 0.f;
-  const float* __restrict__ xr = a.x + (size_t)b * a.K;
-  for (int k = lane * 4; k < a.K; k += 256) {
-    const f32x4 xv = *reinterpret_cast<const f32x4*>(xr + k);
-#pragma unroll
-    for (int o = 0; o < MAXA; ++o)
-      if (o < a.A) {
-        const f32x4 wv = *reinterpret_cast<const f32x4*>(a.wm + (size_t)o * a.K + k);
-        s[o] += xv[0] * wv[0] + xv[1] * wv[1] + xv[2] * wv[2] + xv[3] * wv[3];
-      }
-    const f32x4 pv = *reinterpret_cast<const f32x4*>(a.wp + k);
-    s[MAXA] += xv[0] * pv[0] + xv[1] * pv[1] + xv[2] * pv[2] + xv[3] * pv[3];
-  }
-#pragma unroll
-  for (int o = 0; o <= MAXA; ++o) s[o] = wave_sum(s[o]);
+  float s[HEADS_MAXA + 1];
+  heads_row_dots(a.x + (size_t)b * a.K, a.wm, a.wp, a.K, a.A, lane, s);
   if (lane == 0) {
 #pragma unroll
-    for (int o = 0; o < MAXA; ++o)
+    for (int o = 0; o < HEADS_MAXA; ++o)
       if (o < a.A) a.pred[(size_t)b * a.A + o] = s[o] + a.bm[o];
-    const float p = tanhf(s[MAXA] + a.bp[0]);
+    const float p = tanhf(s[HEADS_MAXA] + a.bp[0]);
     a.prog[b] = p;
     if (a.prog_rows) {
       const float d = p - a.progress[b];
       a.prog_rows[b] = d * d;
     }
   }
-}
-
-__device__ __forceinline__ float block_sum(float v, float* red) {   // 256 threads; result valid in every thread
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
 }
 
 struct AuxReduce {
@@ -124,7 +101,6 @@ constexpr int DL_CHUNK = 2048;   // rows per chunk
 __global__ __launch_bounds__(256) void dagger_loss_fwd_kernel(DaggerLoss a) {
   __shared__ float red[4];
   __shared__ float term[DL_CHUNK], wrow[DL_CHUNK];
-  const int rows = a.T * a.N;
   // chunks hold whole steps: tpc >= 8 steps of N rows (the entry point refuses N > 256: phase 2 gives every episode a thread)
   const int tpc = DL_CHUNK / a.N;
   float num = 0.f, den = 0.f;        // thread n < N: its episode
@@ -146,7 +122,6 @@ __global__ __launch_bounds__(256) void dagger_loss_fwd_kernel(DaggerLoss a) {
       for (int t = 0; t < nt; ++t) { num += term[t * a.N + n]; den += wrow[t * a.N + n]; }
     __syncthreads();
   }
-  (void)rows;
   float tot = 0.f;
   if (threadIdx.x < a.N) {
     a.den[threadIdx.x] = den;
@@ -190,77 +165,26 @@ struct HeadsBwd {
   int B, K, A;
 };
 
-// A workgroup owns 32 features (columns) for ALL rows: thread = (feature f, row group g of 8); row b belongs to group b % 8.
-// d x[b][f] = sum_o g_o[b] w_o[f] is written directly; d w_o[f] = sum_b g_o[b] x[b][f] is accumulated per thread over its rows
-// in row order and the 32 groups are added in group order — no atomics, the same bits every run.  g_o[b] (A + 1 numbers per row)
-// is recomputed by every workgroup: it is a handful of flops.
-__global__ __launch_bounds__(256) void update_heads_bwd_kernel(HeadsBwd a) {
-  // (round 5, end: 8 feature columns x 32 row groups per workgroup instead of 32 x 8 — 64 workgroups of 16-row loops instead of 16 of
-  //  64-row loops: the kernel sits alone between the recurrent core's forward and backward, 45 us of dependent loads)
-  constexpr int FC = 8, RG = 32;
-  __shared__ float part[RG][MAXA + 1][FC];
-  const int f = threadIdx.x & (FC - 1), g = threadIdx.x / FC;
-  const int col = blockIdx.x * FC + f;
-  const bool live = col < a.K;
-  float wv[MAXA + 1], acc[MAXA + 1], bacc[MAXA + 1];
+// The column-owned backward (heads_bwd_columns) with this row: g_o[b] = d pred[b][o], and the progress head's gradient through its
+// tanh from d prog and the progress loss rows.  The row sums are the bias gradients.
+struct UpdateHeadsRow {
+  static constexpr int NX = 0;
+  __device__ explicit UpdateHeadsRow(const HeadsBwd&) {}
+  __device__ void fill(const HeadsBwd& a, int b, float (&go)[HEADS_MAXA + 1], float*) const {
 #pragma unroll
-  for (int o = 0; o <= MAXA; ++o) { wv[o] = 0.f; acc[o] = 0.f; bacc[o] = 0.f; }
-  if (live) {
-#pragma unroll
-    for (int o = 0; o < MAXA; ++o)
-      if (o < a.A) wv[o] = a.wm[(size_t)o * a.K + col];
-    wv[MAXA] = a.wp[col];
-  }
-#pragma unroll 4
-  for (int b = g; b < a.B; b += RG) {       // (independent rows: several in flight)
-    float go[MAXA + 1];
-#pragma unroll
-    for (int o = 0; o < MAXA; ++o) go[o] = (o < a.A && a.dpred) ? a.dpred[(size_t)b * a.A + o] : 0.f;
+    for (int o = 0; o < HEADS_MAXA; ++o) go[o] = (o < a.A && a.dpred) ? a.dpred[(size_t)b * a.A + o] : 0.f;
     const float p = a.prog[b];
     float gp = a.dprog ? a.dprog[b] : 0.f;
     if (a.dprows && a.progress) gp += a.dprows[b] * 2.f * (p - a.progress[b]);
-    go[MAXA] = gp * (1.f - p * p);
-    if (live) {
-      const float xv = a.x[(size_t)b * a.K + col];
-      float d = 0.f;
-#pragma unroll
-      for (int o = 0; o <= MAXA; ++o) {
-        d += go[o] * wv[o];
-        acc[o] += go[o] * xv;
-      }
-      a.dx[(size_t)b * a.K + col] = d;
-    }
-#pragma unroll
-    for (int o = 0; o <= MAXA; ++o) bacc[o] += go[o];
+    go[HEADS_MAXA] = gp * (1.f - p * p);
   }
-#pragma unroll
-  for (int o = 0; o <= MAXA; ++o) part[g][o][f] = acc[o];
-  __syncthreads();
-  if (g == 0 && live) {
-#pragma unroll
-    for (int o = 0; o <= MAXA; ++o) {
-      float s = 0.f;
-#pragma unroll
-      for (int q = 0; q < RG; ++q) s += part[q][o][f];
-      if (o < MAXA) { if (o < a.A) a.dwm[(size_t)o * a.K + col] = s; }
-      else a.dwp[col] = s;
-    }
+  static __device__ void store(const HeadsBwd& a, int o, float s) {
+    if (o < HEADS_MAXA) { if (o < a.A) a.dbm[o] = s; }
+    else a.dbp[0] = s;
   }
-  if (blockIdx.x == 0) {      // bias gradients: the groups' row sums, in group order (every feature lane holds the same numbers)
-    __syncthreads();
-#pragma unroll
-    for (int o = 0; o <= MAXA; ++o) part[g][o][f] = bacc[o];
-    __syncthreads();
-    if (threadIdx.x <= MAXA) {
-      const int o = threadIdx.x;
-      float s = 0.f;
-#pragma unroll
-      for (int q = 0; q < RG; ++q) s += part[q][o][0];
-      if (o < MAXA) { if (o < a.A) a.dbm[o] = s; }
-      else a.dbp[0] = s;
-    }
-  }
-}
+};
+
+__global__ __launch_bounds__(256) void update_heads_bwd_kernel(HeadsBwd a) { heads_bwd_columns<UpdateHeadsRow>(a, a.wp, a.dwp); }
 
 // d rows_k[b] = [mask_b] daux * alpha_k / nsel  (the masked mean's gradient), for the L loss vectors of aux_reduce_fwd
 __global__ __launch_bounds__(256) void aux_reduce_bwd_kernel(const unsigned char* __restrict__ mask, const float* __restrict__ nsel,
@@ -276,7 +200,7 @@ __global__ __launch_bounds__(256) void aux_reduce_bwd_kernel(const unsigned char
 extern "C" int wsmg_update_heads_fwd(const float* x, const float* wm, const float* bm, const float* wp, const float* bp,
                                      const float* progress, int B, int K, int A, float* pred, float* prog, float* prog_rows,
                                      wsmg_stream_t stream) {
-  if (!x || !wm || !bm || !wp || !bp || !pred || !prog || B <= 0 || K <= 0 || (K & 3) || A <= 0 || A > MAXA) return WSMG_EINVAL;
+  if (!x || !wm || !bm || !wp || !bp || !pred || !prog || B <= 0 || K <= 0 || (K & 3) || A <= 0 || A > HEADS_MAXA) return WSMG_EINVAL;
   if (prog_rows && !progress) return WSMG_EINVAL;
   HeadsFwd a{x, wm, bm, wp, bp, progress, pred, prog, prog_rows, B, K, A};
   hipLaunchKernelGGL(update_heads_fwd_kernel, dim3((unsigned)wsmg_cdiv(B, 4)), dim3(256), 0, wsmg_s(stream), a);
@@ -311,7 +235,7 @@ extern "C" int wsmg_aux_reduce_bwd(const float* alpha, int L, const unsigned cha
 extern "C" int wsmg_update_heads_bwd(const float* x, const float* wm, const float* wp, const float* prog, const float* progress,
                                      const float* dpred, const float* dprog, const float* dprog_rows, int B, int K, int A, float* dx,
                                      float* dwm, float* dbm, float* dwp, float* dbp, wsmg_stream_t stream) {
-  if (!x || !wm || !wp || !prog || !dx || !dwm || !dbm || !dwp || !dbp || B <= 0 || K <= 0 || A <= 0 || A > MAXA) return WSMG_EINVAL;
+  if (!x || !wm || !wp || !prog || !dx || !dwm || !dbm || !dwp || !dbp || B <= 0 || K <= 0 || A <= 0 || A > HEADS_MAXA) return WSMG_EINVAL;
   if (dprog_rows && !progress) return WSMG_EINVAL;
   HeadsBwd a{x, wm, wp, prog, progress, dpred, dprog, dprog_rows, dx, dwm, dbm, dwp, dbp, B, K, A};
   hipLaunchKernelGGL(update_heads_bwd_kernel, dim3((unsigned)wsmg_cdiv(K, 8)), dim3(256), 0, wsmg_s(stream), a);

@@ -254,14 +254,6 @@ struct GradBatch {         // the table's gradients and this launch's slice of t
   double* partials;
 };
 
-// fixed order: the wave's xor tree, then the four waves in index order (thread 0 returns the sum)
-__device__ __forceinline__ double block_sum_d(double acc, double* red) {
-  acc = wave_sum_d(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
-
 __global__ __launch_bounds__(256) void grad_sumsq_multi_kernel(GradBatch b) {
   __shared__ double red[4];
   const int t = chunk_tensor(b.tab);

@@ -7,7 +7,7 @@
 //                           logp[b]  = sum_a( -(action - mean)^2 / (2 sigma^2) - logstd_a - 0.5 log(2 pi) )   (distributions.py:21-29)
 //                           entropy  = sum_a( 0.5 + 0.5 log(2 pi) + logstd_a )        (the same for every row: also the batch mean)
 //   eval_heads_bwd_kernel   d mean = d logp (action - mean) / sigma^2,   d logstd_a = sum_b d logp_b ((action - mean)^2 / sigma^2 - 1) + d entropy,
-//                           d x, d Wm, d bm, d Wc, d bc as update_heads_bwd_kernel forms them (wsmg_heads.hip)
+//                           d x, d Wm, d bm, d Wc, d bc as update_heads_bwd_kernel forms them (wsmg_heads_common.h)
 //   ppo_loss_fwd_kernel     habitat-baselines' PPO.update: ratio = exp(logp - old_logp), action_loss = -mean(min(ratio adv, clamp(ratio) adv)),
 //                           value_loss = 0.5 mean(max((v - ret)^2, (v_clipped - ret)^2)) or 0.5 mean((ret - v)^2),
 //                           loss = value_coef value_loss + action_loss - entropy_coef entropy;  + clip fraction and approximate KL
@@ -15,13 +15,12 @@
 //
 // float32 throughout; every sum in a fixed order, no atomics (the same bits every run); the rows a mask leaves out are DROPPED from
 // the means (selected), not multiplied by zero, as aux_reduce_fwd_kernel does.
-#include "wsmg_common.h"
+// The two heads kernels' row projection and column-owned backward are wsmg_heads_common.h's, shared with wsmg_heads.hip.
+#include "wsmg_heads_common.h"
 
 namespace {
 
-constexpr int MAXA = 4;                    // action dimensions, as wsmg_heads.hip
 constexpr int PPO_MAXB = 1 << 20;          // rows one workgroup walks (4096 per thread); a PPO minibatch is 10^2 .. 10^4
-constexpr float HALF_LOG_2PI = 0.91893853320467274178f;
 
 struct EvalFwd {
   const float* x;        // [B][K]
@@ -38,7 +37,7 @@ struct EvalFwd {
   int B, K, A;
 };
 
-// one wave per row: lane l holds 4 consecutive features per 256-feature pass (update_heads_fwd_kernel's walk)
+// one wave per row (heads_row_dots); lane 0 adds the biases and the log-probability, thread 0 of the grid the entropy
 __global__ __launch_bounds__(256) void eval_heads_fwd_kernel(EvalFwd a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -48,27 +47,12 @@ __global__ __launch_bounds__(256) void eval_heads_fwd_kernel(EvalFwd a) {
   }
   const int b = blockIdx.x * 4 + wave;
   if (b >= a.B) return;
-  float s[MAXA + 1];
-#pragma unroll
-  for (int o = 0; o <= MAXA; ++o) s[o] = 0.f;
-  const float* __restrict__ xr = a.x + (size_t)b * a.K;
-  for (int k = lane * 4; k < a.K; k += 256) {
-    const f32x4 xv = *reinterpret_cast<const f32x4*>(xr + k);
-#pragma unroll
-    for (int o = 0; o < MAXA; ++o)
-      if (o < a.A) {
-        const f32x4 wv = *reinterpret_cast<const f32x4*>(a.wm + (size_t)o * a.K + k);
-        s[o] += xv[0] * wv[0] + xv[1] * wv[1] + xv[2] * wv[2] + xv[3] * wv[3];
-      }
-    const f32x4 cv = *reinterpret_cast<const f32x4*>(a.wc + k);
-    s[MAXA] += xv[0] * cv[0] + xv[1] * cv[1] + xv[2] * cv[2] + xv[3] * cv[3];
-  }
-#pragma unroll
-  for (int o = 0; o <= MAXA; ++o) s[o] = wave_sum(s[o]);
+  float s[HEADS_MAXA + 1];
+  heads_row_dots(a.x + (size_t)b * a.K, a.wm, a.wc, a.K, a.A, lane, s);
   if (lane == 0) {
     float lp = 0.f;
 #pragma unroll
-    for (int o = 0; o < MAXA; ++o)
+    for (int o = 0; o < HEADS_MAXA; ++o)
       if (o < a.A) {
         const float m = s[o] + a.bm[o];
         a.mean[(size_t)b * a.A + o] = m;
@@ -78,7 +62,7 @@ __global__ __launch_bounds__(256) void eval_heads_fwd_kernel(EvalFwd a) {
         lp += (-(d * d) / (2.f * (sigma * sigma)) - ls) - HALF_LOG_2PI;
       }
     a.logp[b] = lp;
-    a.value[b] = s[MAXA] + a.bc[0];
+    a.value[b] = s[HEADS_MAXA] + a.bc[0];
   }
 }
 
@@ -101,39 +85,22 @@ struct EvalBwd {
   int B, K, A;
 };
 
-// The column ownership of update_heads_bwd_kernel: a workgroup owns 8 features for ALL rows, thread = (feature f, row group g of
-// 32), row b belongs to group b % 32.  Per row the A + 1 head gradients g_o[b] (d mean, d value) are recomputed by every workgroup;
-// d x is written directly, d W is accumulated per thread over its rows in row order and the 32 groups are added in group order.
-// Workgroup 0 adds the row sums that have no feature axis the same way: d bm, d bc and d logstd.
-__global__ __launch_bounds__(256) void eval_heads_bwd_kernel(EvalBwd a) {
-  constexpr int FC = 8, RG = 32, NB = 2 * MAXA + 1;      // NB row sums: d bm [MAXA], d bc, d logstd [MAXA]
-  __shared__ float part[RG][MAXA + 1][FC];
-  __shared__ float bpart[RG][NB];
-  const int f = threadIdx.x & (FC - 1), g = threadIdx.x / FC;
-  const int col = blockIdx.x * FC + f;
-  const bool live = col < a.K;
-  float wv[MAXA + 1], acc[MAXA + 1], bacc[NB], ivar[MAXA];
+// The column-owned backward (heads_bwd_columns) with this row: g_o[b] = d mean[b][o] and d value[b]; HEADS_MAXA extra row sums, the
+// rows' terms of d logstd.  Row sums: d bm [HEADS_MAXA], d bc, d logstd [HEADS_MAXA] (+ d entropy, the same for every dimension).
+struct EvalHeadsRow {
+  static constexpr int NX = HEADS_MAXA;
+  float ivar[HEADS_MAXA];        // 1 / sigma^2
+  __device__ explicit EvalHeadsRow(const EvalBwd& a) {
 #pragma unroll
-  for (int o = 0; o <= MAXA; ++o) { wv[o] = 0.f; acc[o] = 0.f; }
-#pragma unroll
-  for (int o = 0; o < NB; ++o) bacc[o] = 0.f;
-#pragma unroll
-  for (int o = 0; o < MAXA; ++o) {
-    const float sigma = o < a.A ? expf(a.logstd[o]) : 1.f;
-    ivar[o] = 1.f / (sigma * sigma);
+    for (int o = 0; o < HEADS_MAXA; ++o) {
+      const float sigma = o < a.A ? expf(a.logstd[o]) : 1.f;
+      ivar[o] = 1.f / (sigma * sigma);
+    }
   }
-  if (live) {
-#pragma unroll
-    for (int o = 0; o < MAXA; ++o)
-      if (o < a.A) wv[o] = a.wm[(size_t)o * a.K + col];
-    wv[MAXA] = a.wc[col];
-  }
-#pragma unroll 4
-  for (int b = g; b < a.B; b += RG) {       // (independent rows: several in flight)
-    float go[MAXA + 1], gl[MAXA];
+  __device__ void fill(const EvalBwd& a, int b, float (&go)[HEADS_MAXA + 1], float (&gl)[HEADS_MAXA]) const {
     const float dl = a.dlogp ? a.dlogp[b] : 0.f;
 #pragma unroll
-    for (int o = 0; o < MAXA; ++o) {
+    for (int o = 0; o < HEADS_MAXA; ++o) {
       go[o] = 0.f; gl[o] = 0.f;
       if (o < a.A && a.dlogp) {
         const float d = a.action[(size_t)b * a.A + o] - a.mean[(size_t)b * a.A + o];
@@ -141,57 +108,16 @@ __global__ __launch_bounds__(256) void eval_heads_bwd_kernel(EvalBwd a) {
         gl[o] = dl * (d * d * ivar[o] - 1.f);
       }
     }
-    go[MAXA] = a.dvalue ? a.dvalue[b] : 0.f;
-    if (live) {
-      const float xv = a.x[(size_t)b * a.K + col];
-      float d = 0.f;
-#pragma unroll
-      for (int o = 0; o <= MAXA; ++o) {
-        d += go[o] * wv[o];
-        acc[o] += go[o] * xv;
-      }
-      a.dx[(size_t)b * a.K + col] = d;
-    }
-#pragma unroll
-    for (int o = 0; o <= MAXA; ++o) bacc[o] += go[o];
-#pragma unroll
-    for (int o = 0; o < MAXA; ++o) bacc[MAXA + 1 + o] += gl[o];
+    go[HEADS_MAXA] = a.dvalue ? a.dvalue[b] : 0.f;
   }
-#pragma unroll
-  for (int o = 0; o <= MAXA; ++o) part[g][o][f] = acc[o];
-  if (blockIdx.x == 0 && f == 0) {          // (every feature lane of a group holds the same row sums)
-#pragma unroll
-    for (int o = 0; o < NB; ++o) bpart[g][o] = bacc[o];
+  static __device__ void store(const EvalBwd& a, int o, float s) {
+    if (o < HEADS_MAXA) { if (o < a.A) a.dbm[o] = s; }
+    else if (o == HEADS_MAXA) a.dbc[0] = s;
+    else if (o - HEADS_MAXA - 1 < a.A) a.dlogstd[o - HEADS_MAXA - 1] = s + (a.dentropy ? a.dentropy[0] : 0.f);
   }
-  __syncthreads();
-  if (g == 0 && live) {
-#pragma unroll
-    for (int o = 0; o <= MAXA; ++o) {
-      float s = 0.f;
-#pragma unroll
-      for (int q = 0; q < RG; ++q) s += part[q][o][f];
-      if (o < MAXA) { if (o < a.A) a.dwm[(size_t)o * a.K + col] = s; }
-      else a.dwc[col] = s;
-    }
-  }
-  if (blockIdx.x == 0 && threadIdx.x < NB) {
-    const int o = threadIdx.x;
-    float s = 0.f;
-#pragma unroll
-    for (int q = 0; q < RG; ++q) s += bpart[q][o];
-    if (o < MAXA) { if (o < a.A) a.dbm[o] = s; }
-    else if (o == MAXA) a.dbc[0] = s;
-    else if (o - MAXA - 1 < a.A) a.dlogstd[o - MAXA - 1] = s + (a.dentropy ? a.dentropy[0] : 0.f);
-  }
-}
+};
 
-__device__ __forceinline__ float block_sum(float v, float* red) {   // 256 threads; result valid in every thread
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
+__global__ __launch_bounds__(256) void eval_heads_bwd_kernel(EvalBwd a) { heads_bwd_columns<EvalHeadsRow>(a, a.wc, a.dwc); }
 
 struct PpoRows {
   const float* logp;       // [B]
@@ -287,7 +213,7 @@ extern "C" int wsmg_eval_heads_fwd(const float* x, const float* wm, const float*
                                    const float* bc, const float* action, int B, int K, int A, float* value, float* logp, float* mean,
                                    float* entropy, wsmg_stream_t stream) {
   if (!x || !wm || !bm || !logstd || !wc || !bc || !action || !value || !logp || !mean || !entropy) return WSMG_EINVAL;
-  if (B <= 0 || K <= 0 || (K & 3) || A <= 0 || A > MAXA) return WSMG_EINVAL;
+  if (B <= 0 || K <= 0 || (K & 3) || A <= 0 || A > HEADS_MAXA) return WSMG_EINVAL;
   EvalFwd a{x, wm, bm, logstd, wc, bc, action, value, logp, mean, entropy, B, K, A};
   hipLaunchKernelGGL(eval_heads_fwd_kernel, dim3((unsigned)wsmg_cdiv(B, 4)), dim3(256), 0, wsmg_s(stream), a);
   WSMG_RETURN_LAUNCH();
@@ -298,7 +224,7 @@ extern "C" int wsmg_eval_heads_bwd(const float* x, const float* wm, const float*
                                    int A, float* dx, float* dwm, float* dbm, float* dlogstd, float* dwc, float* dbc,
                                    wsmg_stream_t stream) {
   if (!x || !wm || !wc || !logstd || !action || !mean || !dx || !dwm || !dbm || !dlogstd || !dwc || !dbc) return WSMG_EINVAL;
-  if (B <= 0 || K <= 0 || (K & 3) || A <= 0 || A > MAXA) return WSMG_EINVAL;
+  if (B <= 0 || K <= 0 || (K & 3) || A <= 0 || A > HEADS_MAXA) return WSMG_EINVAL;
   EvalBwd a{x, wm, wc, logstd, action, mean, dvalue, dlogp, dentropy, dx, dwm, dbm, dlogstd, dwc, dbc, B, K, A};
   hipLaunchKernelGGL(eval_heads_bwd_kernel, dim3((unsigned)wsmg_cdiv(K, 8)), dim3(256), 0, wsmg_s(stream), a);
   WSMG_RETURN_LAUNCH();

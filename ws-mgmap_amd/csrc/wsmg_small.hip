@@ -9,19 +9,11 @@
 // the weight row read once with 16-byte loads and reused for up to 8 rows at a time — and the heads are one launch per step.
 // Beside them the other small launches that stand for a list of torch ops: a list of device-to-device copies (plain and guarded),
 // mean_rows (the mean over a short innermost axis), and the column sums behind the recurrent core's bias gradients.
-#include "wsmg_common.h"
+#include "wsmg_heads_common.h"
 
 namespace {
 
 constexpr int ROWS = 8;   // rows sharing one pass over a weight row
-
-__device__ __forceinline__ float block_sum_256(float v, float* red) {   // result valid in every thread
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
 
 // y[r][o] = act(sum_k x[r][k] * w[o][k] + b[o]), act: 0 none, 1 ReLU, 2 tanh.  pool > 1: x is [B][K][pool] and the layer reads
 // its mean over the last axis (rgb_linear's AdaptiveAvgPool1d(1) + Flatten in front of the Linear).
@@ -63,7 +55,7 @@ __global__ __launch_bounds__(256) void linear_rows_kernel(const float* __restric
 #pragma unroll
     for (int r = 0; r < ROWS; ++r) {
       if (r >= nr) break;      // (uniform)
-      float v = block_sum_256(acc[r], red);
+      float v = block_sum(acc[r], red);
       if (tid == 0) {
         v += bias ? bias[o] : 0.f;
         if (act == 1) v = v > 0.f ? v : 0.f;
@@ -111,7 +103,7 @@ __global__ __launch_bounds__(256) void act_heads_kernel(HeadsArgs a) {
     // Normal.log_prob: -((x - loc)^2) / (2 var) - log(scale) - log(sqrt(2 pi))
     const float d = __fsub_rn(act, mean);
     const float var = __fmul_rn(scale, scale);
-    lp += __fsub_rn(__fsub_rn(-__fmul_rn(d, d) / __fmul_rn(2.f, var), logf(scale)), 0.91893853320467274178f);
+    lp += __fsub_rn(__fsub_rn(-__fmul_rn(d, d) / __fmul_rn(2.f, var), logf(scale)), HALF_LOG_2PI);
   }
   a.logp[b] = lp;
 }

@@ -295,6 +295,15 @@ def nav_accumulate(rows, counts=None, sums=None):
 
 
 # ----------------------------------------------------------------------------- update-path heads, auxiliary reduction, trainer loss
+HEADS_MAX_A = 4           # HEADS_MAXA of csrc/wsmg_heads_common.h: the action dimensions update_heads and eval_heads take
+EVAL_HEADS_MAX_A = HEADS_MAX_A      # (the name it had while only eval_heads checked it on the host)
+
+
+def _grad_f32(t):
+    """An upstream gradient as the backward kernels read it (contiguous float32); None — nothing reached that output — stays None."""
+    return None if t is None else t.contiguous().float()
+
+
 class _UpdateHeads(torch.autograd.Function):
     """(pred [B,A], prog [B,1], progress-loss rows [B]) of the update path in one launch per direction (csrc/wsmg_heads.hip):
     `action_distribution.fc_mean`, `tanh(prog_pred(.))` and `mse_loss(prog, progress, 'none').mean(-1)` of the reference's
@@ -321,8 +330,7 @@ class _UpdateHeads(torch.autograd.Function):
         x, wm, wp, prog, progress = ctx.saved_tensors
         B, K = x.shape
         A = wm.shape[0]
-        c = lambda t: None if t is None else t.contiguous().float()   # noqa: E731
-        dpred, dprog, drows = c(dpred), c(dprog), c(drows)
+        dpred, dprog, drows = _grad_f32(dpred), _grad_f32(dprog), _grad_f32(drows)
         dx = torch.empty_like(x)
         dwm, dbm = torch.empty_like(wm), torch.empty(A, device=x.device, dtype=torch.float32)
         dwp, dbp = torch.empty_like(wp), torch.empty(1, device=x.device, dtype=torch.float32)
@@ -417,7 +425,6 @@ def dagger_loss(pred, aux_loss, waypoint, weights):
 
 
 # ----------------------------------------------------------------------------- policy-gradient heads and the PPO loss
-EVAL_HEADS_MAX_A = 4      # the limits of csrc/wsmg_pg_heads.hip (and of update_heads): A <= 4, K % 4 == 0
 PPO_MAX_ROWS = 1 << 20
 
 
@@ -437,8 +444,8 @@ class _EvalHeads(torch.autograd.Function):
         if (wm.shape != (A, K) or bm.numel() != A or logstd.numel() != A or wc.numel() != K or bc.numel() != 1
                 or tuple(action.shape) != (B, A)):
             raise _abi.WsmgError("eval_heads: head shapes do not fit the features, or action is not [B, A]")
-        if B < 1 or K % 4 or not 1 <= A <= EVAL_HEADS_MAX_A:
-            raise _abi.WsmgError(f"eval_heads: B >= 1, K % 4 == 0 and 1 <= A <= {EVAL_HEADS_MAX_A}, got B = {B}, K = {K}, A = {A}")
+        if B < 1 or K % 4 or not 1 <= A <= HEADS_MAX_A:
+            raise _abi.WsmgError(f"eval_heads: B >= 1, K % 4 == 0 and 1 <= A <= {HEADS_MAX_A}, got B = {B}, K = {K}, A = {A}")
         if any(t.data_ptr() % 16 for t in (x, wm, wc)):     # the forward reads them four floats at a time
             raise _abi.WsmgError("eval_heads: features, fc_mean.weight and critic.fc.weight must start on a 16-byte boundary "
                                  "(a view with a storage offset that is no multiple of 4 floats: clone it)")
@@ -456,8 +463,7 @@ class _EvalHeads(torch.autograd.Function):
         x, wm, wc, logstd, action, mean = ctx.saved_tensors
         B, K = x.shape
         A = wm.shape[0]
-        c = lambda t: None if t is None else t.contiguous().float()   # noqa: E731
-        dvalue, dlogp, dent = c(dvalue), c(dlogp), c(dent)
+        dvalue, dlogp, dent = _grad_f32(dvalue), _grad_f32(dlogp), _grad_f32(dent)
         dev = x.device
         dx, dwm, dwc = torch.empty_like(x), torch.empty_like(wm), torch.empty_like(wc)
         dbm, dbc, dls = torch.empty(A, device=dev), torch.empty(1, device=dev), torch.empty_like(logstd)
@@ -469,7 +475,7 @@ class _EvalHeads(torch.autograd.Function):
 def eval_heads_ok(features, action_dim):
     """Can `eval_heads` take these features?  float32 [B >= 1, K % 4 == 0] on the GPU, at most 4 action dimensions."""
     return (features.is_cuda and features.dtype == torch.float32 and features.dim() == 2 and features.shape[0] >= 1
-            and features.shape[1] % 4 == 0 and 1 <= action_dim <= EVAL_HEADS_MAX_A)
+            and features.shape[1] % 4 == 0 and 1 <= action_dim <= HEADS_MAX_A)
 
 
 def eval_heads(features, fc_mean, logstd, critic_fc, action):
