@@ -1,5 +1,5 @@
 // BatchNorm2d (+residual, +ReLU) forward/backward and per-channel column sums for NHWC
-// float32 activations viewed as a [rows][C] matrix (rows = B*H*W, C in {32,64,128,256}).
+// float32 or bf16 activations viewed as a [rows][C] matrix (rows = B*H*W, C in {32,64,128,256,512}: chan_ok).
 //
 // Replaces nn.BatchNorm2d / F.relu (cuDNN batch-norm + elementwise kernels) at
 // map_encoder.py:10-12,21-28,94-112, mg_map_policy.py:80-85 and the torchvision BasicBlock

@@ -64,14 +64,22 @@ def _sfx(t):
     raise _abi.WsmgError(f"wsmgmap activations are float32 or bfloat16, got {t.dtype}")
 
 
-def _workspace(device):
-    """float64 scratch for the chip-wide column reductions (4 MiB covers 1024 blocks x 2 x 256)."""
+_WS_MIN = 1024 * 2 * 256      # doubles: 4 MiB, every reduction of up to 256 channels at any row count
+
+
+def _workspace(device, rows, C):
+    """float64 scratch for the chip-wide column reduction of a [rows][C] matrix: at least what the library asks for
+    (wsmg_channel_reduce_workspace_bytes: 1024 blocks x 2 x 512 doubles at most), never less than 4 MiB."""
     # one buffer per STREAM: launches of one stream use it one after the other, but reductions on two streams (the decoder's
-    # side-stream branch, the instruction branch's bias gradient) run at the same time
+    # side-stream branch, the instruction branch's bias gradient) run at the same time.  A buffer only grows: the one it
+    # replaces goes back to the allocator, which hands it out again in the order of the stream that allocated it — this one
     key = (device.type, device.index, _raw_stream())
     ws = _ws_cache.get(key)
-    if ws is None:
-        ws = torch.empty(1024 * 2 * 256, dtype=torch.float64, device=device)
+    if ws is not None and ws.numel() >= 1024 * 2 * C:     # holds C channels at any row count: no need to ask (the hot path)
+        return ws
+    need = int(_abi.lib().wsmg_channel_reduce_workspace_bytes(rows, C)) // 8
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(max(need, _WS_MIN), dtype=torch.float64, device=device)
         _ws_cache[key] = ws
     return ws
 

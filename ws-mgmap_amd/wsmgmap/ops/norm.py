@@ -14,7 +14,7 @@ def channel_sum(x2d):
     _req(x2d)
     rows, C = x2d.shape
     out = torch.empty(C, device=x2d.device, dtype=torch.float32)
-    ws = _workspace(x2d.device)
+    ws = _workspace(x2d.device, rows, C)
     _abi.call("wsmg_channel_sum" + _sfx(x2d), _p(x2d), rows, C, _p(out), _p(ws), ws.numel() * 8, _stream())
     return out
 
@@ -53,7 +53,7 @@ class _BnAct(torch.autograd.Function):
                       float(momentum), float(eps), int(relu), rows, C, _p(y), _p(mean), _p(invstd), _p(stats), stats.shape[0],
                       _stream())
         else:
-            ws = _workspace(x.device)
+            ws = _workspace(x.device, rows, C)
             _abi.call("wsmg_bn_act_fwd" + sfx, _p(x), _p(residual), _p(gamma), _p(beta), _p(running_mean), _p(running_var),
                       float(momentum), float(eps), int(train), int(relu), rows, C, _p(y), _p(mean), _p(invstd),
                       _p(ws), ws.numel() * 8, _stream())
@@ -78,7 +78,7 @@ class _BnAct(torch.autograd.Function):
         dres = torch.empty_like(x) if has_res else None
         dgamma = torch.empty(C, device=x.device, dtype=torch.float32)
         dbeta = torch.empty(C, device=x.device, dtype=torch.float32)
-        ws = _workspace(x.device)
+        ws = _workspace(x.device, rows, C)
         if ctx.lo_sink is not None:    # + the low half of the float32 gradient for the convolution's weight gradient (GradLoSink)
             lo = torch.empty_like(x)
             _abi.call("wsmg_bn_act_bwd_ld_bf16_lo", _p(dy), ld, _p(x), _p(y), _p(gamma), _p(beta), _p(mean), _p(invstd), relu, rows, C,
