@@ -845,6 +845,29 @@ int wsmg_ppo_loss_bwd(const float* logp, const float* old_logp, const float* adv
                       float value_coef, float entropy_coef, int clipped_value, int B, float* dlogp, float* dvalue, float* dentropy,
                       wsmg_stream_t stream);
 
+/* ---- the rollout's returns and advantages in one launch (csrc/wsmg_pg_rollout.hip) ---------------------------------------------
+ * habitat-baselines' `RolloutStorage.compute_returns` and `PPO.get_advantages`, restated (habitat is not a dependency; the
+ * reference has neither): what wsmg_ppo_loss_fwd takes as `ret` and `adv`.  ONE launch of one workgroup, a thread per environment;
+ * float32 data, no atomics, no allocation, no synchronisation.  rewards [T][N]; value_preds, masks (0 / 1 as float), returns
+ * [T+1][N]; next_value [N]; adv / adv_norm [T][N] or NULL; stats {mean, std} (float64) or NULL.
+ *   use_gae != 0:  value_preds[T] = next_value (WRITTEN);  g = 0;  for s = T-1 .. 0:
+ *                      d = ((rewards[s] + (gamma * value_preds[s+1]) * masks[s+1]) - value_preds[s])
+ *                      g = d + (gamma_tau * masks[s+1]) * g;   returns[s] = g + value_preds[s]        (returns[T] is left as it was)
+ *   use_gae == 0:  returns[T] = next_value;  for s = T-1 .. 0:  returns[s] = ((returns[s+1] * gamma) * masks[s+1]) + rewards[s]
+ *   adv[s] = returns[s] - value_preds[s] (s < T);  adv_norm = (adv - mean(adv)) / (std(adv) + eps), std unbiased (T N - 1) over all.
+ * Every operation of the scan is one float32 operation rounded on its own, in this parenthesisation and this order over s:
+ * returns, adv and value_preds[T] are bit-identical to the float32 torch loop on the CPU.  gamma_tau is gamma * tau formed in double
+ * by the caller and rounded to float32 once (what `gamma * tau * masks` does in torch): hence the product, not tau.
+ * The statistics are float64 sums in a fixed order (bit-reproducible), the mean first, then sum (adv - mean)^2; adv_norm is formed
+ * in double and rounded once.  T N == 1: std and adv_norm are NaN, as torch's.  With adv_norm and stats both NULL the statistics
+ * passes are skipped.  adv_norm does NOT need adv (the kernel forms the difference again from returns and value_preds): any of
+ * adv, adv_norm, stats may be NULL on its own.  The five outputs and the inputs must not overlap one another.
+ * WSMG_EINVAL, before anything is enqueued: T < 1, N < 1, N > 1024, T N >= 2^24, or NULL rewards, value_preds, masks, next_value
+ * or returns. */
+int wsmg_gae_returns(const float* rewards, float* value_preds, const float* masks, const float* next_value, float gamma,
+                     float gamma_tau, int use_gae, int T, int N, float* returns, float* adv, float* adv_norm, double* stats,
+                     float eps, wsmg_stream_t stream);
+
 /* ---- the semantic classifier's tail in one pass per direction (csrc/wsmg_cls_tail.hip) -----------------------------------
  * Reference: `map_classfier[4:7]` = BatchNorm2d(32) + ReLU + Conv2d(32, 27, 1) (mg_map_policy.py:78-86), the prediction monitor's
  * `F.cross_entropy(pred_sem_map, F.interpolate(gt_semantic_map, size=(48, 48)).long(), reduction='none').mean([1, 2])`

@@ -1,0 +1,169 @@
+"""Rollout storage for a PPO / A2C update after DAgger: habitat-baselines' `RolloutStorage` by attribute and method name, restated
+(habitat-baselines is not a dependency and no version of it is pinned: DESIGN.md §2), plus `PPO.get_advantages`.
+
+What is new against the stock class: on float32 GPU storage `compute_returns` is ONE launch (ops.gae_returns,
+csrc/wsmg_pg_rollout.hip) over the rows in use, which also fills the raw and the normalised advantages that `get_advantages` then
+hands out as views — no Python loop over steps, and after the first call no allocation and no synchronisation, so the pair can be
+captured in a HIP graph on one stream.  `returns`, the raw advantages and `value_preds[step]` are the bits of the torch loop.
+CPU storage, other dtypes, more than ops.GAE_MAX_ENVS environments or `fused=False` run that torch loop (the stock arm of the tests),
+as `evaluate_actions` composes stock modules outside its kernels' limits.
+
+`insert`, `after_update` and `recurrent_generator` are torch indexing.  A rollout may be partial: everything works on the rows
+`[:step]` that `insert` has filled."""
+import numpy as np
+import torch
+
+from . import ops
+
+EPS_PPO = 1e-5
+
+
+def _torch_dtype(dt):
+    if isinstance(dt, torch.dtype):
+        return dt
+    return torch.from_numpy(np.zeros(0, dtype=dt)).dtype
+
+
+def _shapes_of(observation_shapes):
+    """name -> (shape, torch dtype) from a dict of (shape, dtype) pairs, or from a gym `Dict` space if one happens to be passed."""
+    spaces = getattr(observation_shapes, "spaces", None)
+    if spaces is not None:
+        return {k: (tuple(sp.shape), _torch_dtype(sp.dtype)) for k, sp in spaces.items()}
+    return {k: (tuple(shape), _torch_dtype(dt)) for k, (shape, dt) in observation_shapes.items()}
+
+
+class RolloutStorage:
+    """Tensors (T = num_steps, N = num_envs): observations[k] [T+1, N, *shape] in its own dtype; recurrent_hidden_states
+    [T+1, layers, N, H] (the layout `BasePolicy.act` takes a row of); rewards, action_log_probs [T, N, 1]; value_preds, returns, masks
+    [T+1, N, 1]; actions [T, N, A]; prev_actions [T+1, N, A]; `step`: rows filled so far (a host int)."""
+
+    def __init__(self, num_steps, num_envs, observation_shapes, action_dim, recurrent_hidden_state_size, num_recurrent_layers=1,
+                 fused=True):
+        T, N = int(num_steps), int(num_envs)
+        self.observations = {k: torch.zeros(T + 1, N, *shape, dtype=dt) for k, (shape, dt) in _shapes_of(observation_shapes).items()}
+        self.recurrent_hidden_states = torch.zeros(T + 1, num_recurrent_layers, N, recurrent_hidden_state_size)
+        self.rewards = torch.zeros(T, N, 1)
+        self.value_preds = torch.zeros(T + 1, N, 1)
+        self.returns = torch.zeros(T + 1, N, 1)
+        self.action_log_probs = torch.zeros(T, N, 1)
+        self.actions = torch.zeros(T, N, action_dim)
+        self.prev_actions = torch.zeros(T + 1, N, action_dim)
+        self.masks = torch.zeros(T + 1, N, 1)
+        self.num_steps, self.num_envs = T, N
+        self.step = 0
+        self.fused = bool(fused)
+        # the one launch's other outputs: raw and normalised advantages and {mean, std}; `_adv_step`: the rows they hold, and the eps
+        self._adv = self._adv_norm = self._stats = None
+        self._adv_step, self._adv_eps = None, None
+
+    _TENSORS = ("recurrent_hidden_states", "rewards", "value_preds", "returns", "action_log_probs", "actions", "prev_actions", "masks")
+
+    def to(self, device):
+        self.observations = {k: v.to(device) for k, v in self.observations.items()}
+        for name in self._TENSORS:
+            setattr(self, name, getattr(self, name).to(device))
+        self._adv = self._adv_norm = self._stats = None
+        self._adv_step = None
+        return self
+
+    # -- plumbing ----------------------------------------------------------------------------------------------------------------
+    def insert(self, observations, recurrent_hidden_states, actions, action_log_probs, value_preds, rewards, masks):
+        """Observations, hidden state, `prev_actions` (= actions) and masks go to row step + 1, the rest to row step."""
+        s = self.step
+        if s >= self.num_steps:
+            raise ValueError(f"RolloutStorage.insert: the storage is full ({self.num_steps} steps): call after_update() first")
+        for k, v in observations.items():
+            self.observations[k][s + 1].copy_(v)
+        put = lambda dst, src: dst.copy_(src.reshape(dst.shape))     # noqa: E731   ([N] log-probabilities into [N, 1])
+        put(self.recurrent_hidden_states[s + 1], recurrent_hidden_states)
+        put(self.actions[s], actions)
+        put(self.prev_actions[s + 1], actions)
+        put(self.action_log_probs[s], action_log_probs)
+        put(self.value_preds[s], value_preds)
+        put(self.rewards[s], rewards)
+        put(self.masks[s + 1], masks)
+        self.step = s + 1
+        self._adv_step = None
+
+    def after_update(self):
+        """Row `step` of observations, hidden state, masks and prev_actions becomes row 0 of the next rollout."""
+        s = self.step
+        for v in self.observations.values():
+            v[0].copy_(v[s])
+        self.recurrent_hidden_states[0].copy_(self.recurrent_hidden_states[s])
+        self.masks[0].copy_(self.masks[s])
+        self.prev_actions[0].copy_(self.prev_actions[s])
+        self.step = 0
+        self._adv_step = None
+
+    # -- returns and advantages --------------------------------------------------------------------------------------------------
+    def _fused_route(self):
+        return (self.fused and self.step >= 1 and ops.gae_returns_ok(self.rewards, self.step)
+                and all(t.is_cuda and t.dtype == torch.float32 for t in (self.value_preds, self.returns, self.masks)))
+
+    def compute_returns(self, next_value, use_gae, gamma, tau):
+        """habitat-baselines' `compute_returns` over the rows [:step]: under GAE `value_preds[step] = next_value` and returns[s] =
+        gae[s] + value_preds[s]; else `returns[step] = next_value` and the discounted sum.  next_value: [N, 1] (or N elements)."""
+        T = self.step
+        if self._fused_route():
+            if self._adv is None:
+                self._adv, self._adv_norm = torch.empty_like(self.rewards), torch.empty_like(self.rewards)
+                self._stats = torch.empty(2, device=self.rewards.device, dtype=torch.float64)
+            if not (next_value.is_cuda and next_value.dtype == torch.float32 and next_value.is_contiguous()):
+                next_value = next_value.to(device=self.rewards.device, dtype=torch.float32).contiguous()
+            ops.gae_returns(self.rewards[:T], self.value_preds[:T + 1], self.masks[:T + 1], next_value, gamma, tau, use_gae=use_gae,
+                            eps=EPS_PPO, out=(self.returns[:T + 1], self._adv[:T], self._adv_norm[:T], self._stats))
+            self._adv_step, self._adv_eps = T, EPS_PPO
+            return
+        self._adv_step = None
+        with torch.no_grad():
+            next_value = next_value.reshape(self.value_preds[T].shape)
+            if use_gae:
+                self.value_preds[T] = next_value
+                gae = 0
+                for s in reversed(range(T)):
+                    delta = self.rewards[s] + gamma * self.value_preds[s + 1] * self.masks[s + 1] - self.value_preds[s]
+                    gae = delta + gamma * tau * self.masks[s + 1] * gae
+                    self.returns[s] = gae + self.value_preds[s]
+            else:
+                self.returns[T] = next_value
+                for s in reversed(range(T)):
+                    self.returns[s] = self.returns[s + 1] * gamma * self.masks[s + 1] + self.rewards[s]
+
+    def get_advantages(self, use_normalized_advantage=True, eps=EPS_PPO):
+        """habitat-baselines' `PPO.get_advantages` over the rows [:step]: returns - value_preds, normalised to (a - mean) / (std + eps)
+        with the unbiased std over all entries.  After a fused `compute_returns` this is a view of what that launch wrote (valid until
+        the next insert / after_update / compute_returns; the stored tensors must not have been edited in between)."""
+        T = self.step
+        if self._adv_step == T and T >= 1:
+            if not use_normalized_advantage:
+                return self._adv[:T]
+            if eps == self._adv_eps:
+                return self._adv_norm[:T]
+            a = self._adv[:T].double()        # another eps than the launch's: from its statistics, still no loop over steps
+            return ((a - self._stats[0]) / (self._stats[1] + eps)).float()
+        with torch.no_grad():
+            advantages = self.returns[:T] - self.value_preds[:T]
+            if not use_normalized_advantage:
+                return advantages
+            return (advantages - advantages.mean()) / (advantages.std() + eps)
+
+    # -- minibatches -------------------------------------------------------------------------------------------------------------
+    def recurrent_generator(self, advantages, num_mini_batch):
+        """Minibatches of whole environments, habitat-baselines' order of fields: (observations, recurrent_hidden_states, actions,
+        prev_actions, value_preds, returns, masks, old_action_log_probs, advantages).  A `torch.randperm` over the environments is cut
+        into num_mini_batch chunks of num_envs // num_mini_batch (environments beyond the last whole chunk sit this epoch out);
+        each batch is the [:step] rows of its columns flattened to [step * n, ...] (row t * n + j: step t of the chunk's j-th
+        environment) and the hidden state of row 0 as [layers, n, H]."""
+        N, T = self.num_envs, self.step
+        if N < num_mini_batch:
+            raise ValueError(f"RolloutStorage.recurrent_generator: {N} environments cannot fill {num_mini_batch} minibatches")
+        per = N // num_mini_batch
+        perm = torch.randperm(N)
+        for b in range(num_mini_batch):
+            ind = perm[b * per:(b + 1) * per].to(self.rewards.device)
+            cols = lambda t, rows=T: t[:rows].index_select(1, ind).flatten(0, 1)      # noqa: E731
+            obs = {k: cols(v) for k, v in self.observations.items()}
+            hidden = self.recurrent_hidden_states[0].index_select(1, ind)
+            yield (obs, hidden, cols(self.actions), cols(self.prev_actions), cols(self.value_preds), cols(self.returns),
+                   cols(self.masks), cols(self.action_log_probs), cols(advantages))
