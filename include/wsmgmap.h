@@ -868,6 +868,20 @@ int wsmg_gae_returns(const float* rewards, float* value_preds, const float* mask
                      float gamma_tau, int use_gae, int T, int N, float* returns, float* adv, float* adv_norm, double* stats,
                      float eps, wsmg_stream_t stream);
 
+/* A PPO minibatch in one launch (habitat-baselines' `RolloutStorage.recurrent_generator`, restated; no reference counterpart): the
+ * columns `ind` of a list of stored tensors,  dst_f[r][j][:] = src_f[r][ind[j]][:]  for every field f, r < rows_f, j < n  — per
+ * field what `src[:rows].index_select(1, ind)` gives.  src_f is [>= rows][N][row_bytes], dst_f [rows][n][row_bytes]; bytes are
+ * copied, whatever the dtype.  dst, src, rows and row_bytes are parallel HOST arrays of n_fields entries (field f: dst[f], src[f],
+ * rows[f], row_bytes[f]), ind a DEVICE array of n column indices; 32 fields per launch, a longer list is several launches; a field
+ * with rows == 0 owns no workgroup.  A field moves in 16-byte units when row_bytes is a multiple of 16
+ * and both its bases are 16-byte aligned, else in 4-byte units.  An index outside [0, N) copies nothing: its destination column
+ * keeps what it held.  Sources and destinations must not overlap.
+ * WSMG_EINVAL, before anything is enqueued: n < 1, N < 1, n_fields < 0, a NULL array (with n_fields > 0) or ind, an ind that is not
+ * 8-byte aligned; in a field: negative rows, a row_bytes that is not a positive multiple of 4, a base that is not 4-byte aligned,
+ * a NULL base with rows > 0, rows n or row_bytes / 4 beyond 2^31 - 1. */
+int wsmg_rollout_gather(void* const* dst, const void* const* src, const long long* rows, const long long* row_bytes, int n_fields,
+                        const int64_t* ind, int n, int N, wsmg_stream_t stream);
+
 /* ---- the semantic classifier's tail in one pass per direction (csrc/wsmg_cls_tail.hip) -----------------------------------
  * Reference: `map_classfier[4:7]` = BatchNorm2d(32) + ReLU + Conv2d(32, 27, 1) (mg_map_policy.py:78-86), the prediction monitor's
  * `F.cross_entropy(pred_sem_map, F.interpolate(gt_semantic_map, size=(48, 48)).long(), reduction='none').mean([1, 2])`

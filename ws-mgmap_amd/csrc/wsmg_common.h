@@ -69,6 +69,8 @@ static inline int wsmg_sgrid(int64_t n) {
 // Multi-tensor launches (wsmg_optim.hip's Adam / norm kernels, wsmg_small.hip's guarded copy): tensors per launch — the table lives
 // in the kernel arguments, a longer list is cut into several launches — and the guard record of wsmg_grad_norm_multi, four float32.
 constexpr int ADAM_MAX = 48;
+// Fields per launch of the grouped column gather (wsmg_rollout_gather.hip): its table, 32 x 28 bytes, is in the kernel arguments too.
+constexpr int GATHER_MAX = 32;
 enum { GUARD_NORM = 0, GUARD_COEF = 1, GUARD_SKIP = 2, GUARD_SKIPPED = 3 };
 
 __device__ __forceinline__ float wave_sum(float v) {

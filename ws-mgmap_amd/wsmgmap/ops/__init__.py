@@ -5,7 +5,7 @@ operator family (round 4: the 1 981-line ops.py, split) —
     conv       the map stack's convolutions (operator 2)            norm    BatchNorm / GroupNorm / channel sums
     nhwc       ReLU, pools, upsampling, layout changes, concatenation   attention   operator 3 (+ e4m3 forms)
     heads      fused losses and heads                                rnn     persistent GRU / LSTM / bi-LSTM
-    bev        operator 1                                            rollout one-launch returns / advantages (GAE)
+    bev        operator 1                                            rollout one-launch returns / advantages (GAE), minibatch gather
 
 PyTorch is used only for device memory, streams and the autograd tape; every FLOP of the three named operators runs in the
 hand-written gfx950 kernels.  All tensors are contiguous and resident on the GPU; anything else raises (there is no CPU or eager

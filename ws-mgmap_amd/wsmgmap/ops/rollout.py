@@ -1,6 +1,9 @@
 """wsmgmap.ops.rollout — the rollout's returns and advantages in one launch (csrc/wsmg_pg_rollout.hip): habitat-baselines'
-`RolloutStorage.compute_returns` + `PPO.get_advantages`, restated.  No autograd: none of these quantities is differentiated in PPO.
+`RolloutStorage.compute_returns` + `PPO.get_advantages`, restated; and a minibatch of its `recurrent_generator` in one launch
+(csrc/wsmg_rollout_gather.hip).  No autograd: none of these quantities is differentiated in PPO.
 """
+import ctypes
+
 import torch
 
 from .. import _abi
@@ -71,3 +74,76 @@ def gae_returns(rewards, value_preds, masks, next_value, gamma, tau, use_gae=Tru
     _abi.call("wsmg_gae_returns", _p(rewards), _p(value_preds), _p(masks), _p(next_value), float(gamma), float(gamma) * float(tau),
               int(bool(use_gae)), T, N, _p(returns), _p(adv), _p(adv_norm), _p(stats), float(eps), _stream())
     return returns, adv, adv_norm, stats
+
+
+GATHER_MAX_FIELDS = 32       # GATHER_MAX of csrc/wsmg_common.h: fields per launch (a longer list is several launches)
+
+
+def _row_bytes(t):
+    return (t.numel() // (t.shape[0] * t.shape[1]) if t.shape[0] and t.shape[1] else 0) * t.element_size()
+
+
+def gather_kernel_ok(src, dst):
+    """Does the grouped launch take this field?  GPU tensors whose rows (everything behind [R, N]) are a positive multiple of 4
+    bytes between 4-byte aligned bases.  Anything else (a uint8 observation of odd width) goes through `index_select`."""
+    rb = _row_bytes(src)
+    return src.is_cuda and rb > 0 and rb % 4 == 0 and src.data_ptr() % 4 == 0 and dst.data_ptr() % 4 == 0
+
+
+@torch.no_grad()
+def gather_columns(fields, ind, rows=None, out=None):
+    """-> [fields[f][:rows_f].index_select(1, ind) for f], on the GPU in one launch per GATHER_MAX_FIELDS fields.
+
+    fields: tensors [R_f, N, ...] with one N, of any dtype (bytes are copied); ind: int64 [n] on their device, every entry in
+    [0, N) (on the GPU an entry outside copies nothing); rows: an int or one per field, 0 <= rows_f <= R_f (default R_f).  The
+    results are [rows_f, n, ...]: the caller flattens them.  out: a list of tensors to write into; an entry that is None is
+    allocated, and nothing is allocated when all are given.  Operands are contiguous and on one device.  CPU tensors, and fields
+    the kernel does not take (`gather_kernel_ok`), go through `index_select`, field by field."""
+    fields = list(fields)
+    if not isinstance(ind, torch.Tensor) or ind.dtype != torch.int64 or ind.dim() != 1 or ind.numel() < 1:
+        raise _abi.WsmgError("gather_columns: ind must be an int64 tensor [n] with n >= 1, got "
+                             + (f"{ind.dtype} {tuple(ind.shape)}" if isinstance(ind, torch.Tensor) else type(ind).__name__))
+    if not ind.is_contiguous():
+        raise _abi.WsmgError(f"gather_columns: ind is not contiguous (strides {ind.stride()})")
+    n, dev = ind.numel(), ind.device
+    if rows is None or isinstance(rows, int):
+        rows = [rows] * len(fields)
+    out = [None] * len(fields) if out is None else list(out)
+    if len(rows) != len(fields) or len(out) != len(fields):
+        raise _abi.WsmgError(f"gather_columns: {len(fields)} fields, but {len(rows)} rows and {len(out)} out entries")
+    N = None
+    res, descs = [], []
+    for f, (src, r, dst) in enumerate(zip(fields, rows, out)):
+        if src.dim() < 2:
+            raise _abi.WsmgError(f"gather_columns: fields[{f}] must be [R, N, ...], got {tuple(src.shape)}")
+        if src.device != dev:
+            raise _abi.WsmgError(f"gather_columns: fields[{f}] is on {src.device}, ind on {dev}")
+        if not src.is_contiguous():
+            raise _abi.WsmgError(f"gather_columns: fields[{f}] is not contiguous: shape {tuple(src.shape)} strides {src.stride()}")
+        N = src.shape[1] if N is None else N
+        if src.shape[1] != N or N < 1:
+            raise _abi.WsmgError(f"gather_columns: fields[{f}] has {src.shape[1]} columns, fields[0] has {N} (at least one is needed)")
+        r = src.shape[0] if r is None else int(r)
+        if not 0 <= r <= src.shape[0]:
+            raise _abi.WsmgError(f"gather_columns: rows[{f}] = {r} is outside fields[{f}]'s {src.shape[0]} rows")
+        shape = (r, n) + tuple(src.shape[2:])
+        if dst is None:
+            dst = torch.empty(shape, dtype=src.dtype, device=dev)
+        elif tuple(dst.shape) != shape or dst.dtype != src.dtype or dst.device != dev:
+            raise _abi.WsmgError(f"gather_columns: out[{f}] must be {src.dtype} {shape} on {dev}, got {dst.dtype} {tuple(dst.shape)} "
+                                 f"on {dst.device}")
+        elif not dst.is_contiguous():
+            raise _abi.WsmgError(f"gather_columns: out[{f}] is not contiguous: shape {tuple(dst.shape)} strides {dst.stride()}")
+        res.append(dst)
+        if dst.numel() == 0:
+            continue
+        if gather_kernel_ok(src, dst):
+            descs.append((dst.data_ptr(), src.data_ptr(), r, _row_bytes(src)))
+        else:
+            torch.index_select(src[:r], 1, ind, out=dst)
+    if descs:
+        k = len(descs)
+        dsts, srcs, rs, rbs = zip(*descs)                  # the launcher's four parallel host arrays
+        _abi.call("wsmg_rollout_gather", (ctypes.c_void_p * k)(*dsts), (ctypes.c_void_p * k)(*srcs), (ctypes.c_longlong * k)(*rs),
+                  (ctypes.c_longlong * k)(*rbs), k, _p(ind), n, N, _stream())
+    return res

@@ -8,8 +8,10 @@ captured in a HIP graph on one stream.  `returns`, the raw advantages and `value
 CPU storage, other dtypes, more than ops.GAE_MAX_ENVS environments or `fused=False` run that torch loop (the stock arm of the tests),
 as `evaluate_actions` composes stock modules outside its kernels' limits.
 
-`insert`, `after_update` and `recurrent_generator` are torch indexing.  A rollout may be partial: everything works on the rows
-`[:step]` that `insert` has filled."""
+`insert` and `after_update` are torch indexing.  On GPU storage each minibatch of `recurrent_generator` is ONE launch
+(ops.gather_columns, csrc/wsmg_rollout_gather.hip) over every stored tensor, the advantages and the row-0 hidden state, where the
+stock class runs an `index_select` and an allocation per field behind a host copy of the index list; the bits are the same.
+A rollout may be partial: everything works on the rows `[:step]` that `insert` has filled."""
 import numpy as np
 import torch
 
@@ -55,6 +57,7 @@ class RolloutStorage:
         # the one launch's other outputs: raw and normalised advantages and {mean, std}; `_adv_step`: the rows they hold, and the eps
         self._adv = self._adv_norm = self._stats = None
         self._adv_step, self._adv_eps = None, None
+        self._staging = None      # recurrent_generator(reuse_buffers=True): one minibatch's tensors, kept between minibatches
 
     _TENSORS = ("recurrent_hidden_states", "rewards", "value_preds", "returns", "action_log_probs", "actions", "prev_actions", "masks")
 
@@ -64,6 +67,7 @@ class RolloutStorage:
             setattr(self, name, getattr(self, name).to(device))
         self._adv = self._adv_norm = self._stats = None
         self._adv_step = None
+        self._staging = None
         return self
 
     # -- plumbing ----------------------------------------------------------------------------------------------------------------
@@ -149,17 +153,26 @@ class RolloutStorage:
             return (advantages - advantages.mean()) / (advantages.std() + eps)
 
     # -- minibatches -------------------------------------------------------------------------------------------------------------
-    def recurrent_generator(self, advantages, num_mini_batch):
+    def recurrent_generator(self, advantages, num_mini_batch, *, reuse_buffers=False):
         """Minibatches of whole environments, habitat-baselines' order of fields: (observations, recurrent_hidden_states, actions,
         prev_actions, value_preds, returns, masks, old_action_log_probs, advantages).  A `torch.randperm` over the environments is cut
         into num_mini_batch chunks of num_envs // num_mini_batch (environments beyond the last whole chunk sit this epoch out);
         each batch is the [:step] rows of its columns flattened to [step * n, ...] (row t * n + j: step t of the chunk's j-th
-        environment) and the hidden state of row 0 as [layers, n, H]."""
+        environment) and the hidden state of row 0 as [layers, n, H].
+
+        On GPU storage with `fused` each minibatch is ONE `ops.gather_columns` call over all of these fields (one launch; a field
+        whose rows are no multiple of 4 bytes is an `index_select` beside it), and the permutation goes to the device once per call
+        of the generator: the same draw, tuple, shapes and bits as the stock route, which CPU storage and `fused=False` run.
+        reuse_buffers: yield views of staging buffers the storage keeps (valid until the next minibatch; dropped by `to()`) instead
+        of fresh tensors."""
         N, T = self.num_envs, self.step
         if N < num_mini_batch:
             raise ValueError(f"RolloutStorage.recurrent_generator: {N} environments cannot fill {num_mini_batch} minibatches")
         per = N // num_mini_batch
         perm = torch.randperm(N)
+        if self.fused and self.rewards.is_cuda and T >= 1:
+            yield from self._gathered_minibatches(advantages, perm.to(self.rewards.device), num_mini_batch, per, reuse_buffers)
+            return
         for b in range(num_mini_batch):
             ind = perm[b * per:(b + 1) * per].to(self.rewards.device)
             cols = lambda t, rows=T: t[:rows].index_select(1, ind).flatten(0, 1)      # noqa: E731
@@ -167,3 +180,25 @@ class RolloutStorage:
             hidden = self.recurrent_hidden_states[0].index_select(1, ind)
             yield (obs, hidden, cols(self.actions), cols(self.prev_actions), cols(self.value_preds), cols(self.returns),
                    cols(self.masks), cols(self.action_log_probs), cols(advantages))
+
+    def _gathered_minibatches(self, advantages, perm, num_mini_batch, per, reuse_buffers):
+        """The fused route of `recurrent_generator`; perm is on the device."""
+        T, keys = self.step, list(self.observations)
+        if not advantages.is_contiguous():
+            advantages = advantages.contiguous()
+        fields = [self.observations[k] for k in keys] + [self.recurrent_hidden_states[0], self.actions, self.prev_actions,
+                                                        self.value_preds, self.returns, self.masks, self.action_log_probs, advantages]
+        rows = [T] * len(fields)
+        rows[len(keys)] = self.recurrent_hidden_states.shape[1]
+        out = None
+        if reuse_buffers:
+            want = [(r, per) + tuple(f.shape[2:]) for f, r in zip(fields, rows)]
+            st = self._staging
+            if st is None or [(tuple(t.shape), t.dtype) for t in st] != [(w, f.dtype) for w, f in zip(want, fields)]:
+                st = self._staging = [torch.empty(w, dtype=f.dtype, device=f.device) for w, f in zip(want, fields)]
+            out = st
+        for b in range(num_mini_batch):
+            got = ops.gather_columns(fields, perm[b * per:(b + 1) * per], rows, out)
+            flat = [g.flatten(0, 1) for g in got]
+            flat[len(keys)] = got[len(keys)]                # the hidden state stays [layers, n, H]
+            yield (dict(zip(keys, flat[:len(keys)])), *flat[len(keys):])
