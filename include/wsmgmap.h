@@ -361,6 +361,20 @@ int wsmg_adam_step_multi_hyper(const WsmgAdamDesc* descs, int n, const float* hy
 int wsmg_grad_norm_multi_hyper(const WsmgAdamDesc* descs, int n, double* partials, long long partials_cap,
                                const float* hyper_guard_row, int skip_nonfinite, float* guard, float* step_dev,
                                wsmg_stream_t stream);
+/* wsmg_grad_norm_multi / wsmg_grad_norm_multi_hyper behind an EXTERNAL GATE: one float32 word in device memory that another kernel
+ * owns (word 0 of wsmg_ppo_loss_fwd_gated's record: the update has stopped).  gate[0] is read on the device, in the finalize:
+ *   gate[0] == 0: the sums, the arithmetic and every write are those of the entry point without a gate, bit for bit;
+ *   gate[0] != 0: the step is skipped whatever the norm is — guard[2] = 2 (non-zero: wsmg_adam_step_multi_guarded / _hyper write
+ *                 nothing, wsmg_copy_multi_guarded rolls back), guard[3] += 1, step_dev is not advanced — while guard[0] and guard[1]
+ *                 keep the norm and the coefficient of the last step that was judged, and wsmg_grad_report_multi does not latch (its
+ *                 latch names a non-finite gradient: guard[2] == 1 only).
+ * WSMG_EINVAL, before anything is launched, for a NULL or not 4-byte aligned gate and for everything the mirrored entry point
+ * refuses; WSMG_ENOMEM likewise. */
+int wsmg_grad_norm_multi_gated(const WsmgAdamDesc* descs, int n, double* partials, long long partials_cap, float max_norm,
+                               int skip_nonfinite, const float* gate, float* guard, float* step_dev, wsmg_stream_t stream);
+int wsmg_grad_norm_multi_hyper_gated(const WsmgAdamDesc* descs, int n, double* partials, long long partials_cap,
+                                     const float* hyper_guard_row, int skip_nonfinite, const float* gate, float* guard,
+                                     float* step_dev, wsmg_stream_t stream);
 /* The four steps above with torch.optim.Adam's remaining options and torch.optim.AdamW's weight decay, chosen by `flags`:
  *   WSMG_ADAM_AMSGRAD       a fifth array per tensor, max_exp_avg_sq: after exp_avg_sq is updated, max = (v > max || v != v) ? v : max
  *                           (a NaN propagates, as torch.maximum's does), and the step divides by sqrt(max) / sqrt(bc2) + eps
@@ -398,7 +412,8 @@ int wsmg_adam_step_multi_hyper_ext(const WsmgAdamDesc* descs, int n, float* cons
  * same list, or that list with zero-length descriptors in between) and must not be NULL — without such a call use
  * wsmg_grad_stats_multi; scan is a workspace of 4 words per 4 096-element chunk (scan_cap counts chunks, as partials_cap does).
  * guard and step_dev (both or neither) are the guard record and the step count that call wrote.  latch (or NULL; needs guard) is
- * [8 + 4 n] words and is written ONLY when guard[2] (skip) != 0 — after a step that was taken no kernel stores one byte of it:
+ * [8 + 4 n] words and is written ONLY when guard[2] (skip) == 1 — after a step that was taken, or that an external gate skipped
+ * (guard[2] == 2, wsmg_grad_norm_multi_gated), no kernel stores one byte of it:
  *   latch[0] (uint32)guard[3]: steps skipped so far, this one included (the caller zeroes the latch once: 0 = never skipped)
  *   latch[1] (uint32)*step_dev + latch[0]: the ordinal of this attempt (steps taken + steps skipped)
  *   latch[2] lowest i with NaNs + Infs > 0, or 0xffffffff: every element was finite and the float32 norm overflowed
@@ -830,7 +845,21 @@ int wsmg_dagger_loss_bwd(const float* pred, const float* waypoint, int ld_waypoi
  *       out5 = {loss, action_loss, value_loss, mean(|ratio - 1| > clip), mean(old_logp - logp)}; nsel [1] = the number of selected
  *       rows, kept for the backward, which writes dlogp [B], dvalue [B], dentropy [1] from dloss [1] with torch autograd's
  *       conventions: min / max of two equal terms give each term half (inside the clip range the two halves meet again), clamp
- *       passes the gradient on its closed interval; a row left out gets 0 * dloss / nsel (NaN when no row is selected). */
+ *       passes the gradient on its closed interval; a row left out gets 0 * dloss / nsel (NaN when no row is selected).
+ *   wsmg_ppo_loss_fwd_gated: the same forward (the same row loop and reduction: out5 and nsel are wsmg_ppo_loss_fwd's, bit for bit)
+ *       behind a KL GATE, the early stop of a PPO update decided on the device, in the same one-workgroup launch.  gate is a record
+ *       of WSMG_KL_GATE float32 words that the host zeroes at the start of an update and only this kernel writes:
+ *         gate[0] stopped   set to 1 by the first call whose approx_kl (out5[4], the float32 stored) > kl_limit, and left set by every
+ *                           later call until the host clears it; a NaN approx_kl (no row selected) does not set it
+ *         gate[1] taken     += 1 by every call that leaves the gate open: the steps an optimizer behind gate[0] takes
+ *         gate[2] seen      += 1 by every call: the ordinal of the next minibatch within the update
+ *         gate[3], gate[4]  the ordinal and the approx_kl of the call that closed the gate (0 while it is open)      gate[5..8) unused
+ *       While the gate is open after the call's own decision, sums5[i] += {value_loss, action_loss, entropy, clip_frac, approx_kl}[i]
+ *       in float32, one rounding each; the call that closes the gate and every call after it add nothing.  One thread stores all of it
+ *       behind the reduction: plain stores, no atomics.  Counters are float32 integers (exact below 2^24).  The backward is
+ *       wsmg_ppo_loss_bwd, unchanged: a stopped call's gradients are computed, and wsmg_grad_norm_multi_gated applies none of them.
+ *       WSMG_EINVAL before anything is enqueued: what wsmg_ppo_loss_fwd refuses, and a NULL or not 4-byte aligned gate or sums5. */
+enum { WSMG_KL_GATE = 8 };
 int wsmg_eval_heads_fwd(const float* x, const float* wm, const float* bm, const float* logstd, const float* wc, const float* bc,
                         const float* action, int B, int K, int A, float* value, float* logp, float* mean, float* entropy,
                         wsmg_stream_t stream);
@@ -840,6 +869,10 @@ int wsmg_eval_heads_bwd(const float* x, const float* wm, const float* wc, const 
 int wsmg_ppo_loss_fwd(const float* logp, const float* old_logp, const float* adv, const float* value, const float* old_value,
                       const float* ret, const unsigned char* mask, const float* entropy, float clip, float value_coef,
                       float entropy_coef, int clipped_value, int B, float* out5, float* nsel, wsmg_stream_t stream);
+int wsmg_ppo_loss_fwd_gated(const float* logp, const float* old_logp, const float* adv, const float* value, const float* old_value,
+                            const float* ret, const unsigned char* mask, const float* entropy, float clip, float value_coef,
+                            float entropy_coef, int clipped_value, int B, float kl_limit, float* out5, float* nsel, float* gate,
+                            float* sums5, wsmg_stream_t stream);
 int wsmg_ppo_loss_bwd(const float* logp, const float* old_logp, const float* adv, const float* value, const float* old_value,
                       const float* ret, const unsigned char* mask, const float* nsel, const float* dloss, float clip,
                       float value_coef, float entropy_coef, int clipped_value, int B, float* dlogp, float* dvalue, float* dentropy,

@@ -27,6 +27,8 @@
 //                                 AMSGRAD>): `flags` and the decay factor travel as wave-uniform kernel arguments, max_exp_avg_sq as
 //                                 a parallel host array of pointers.  The four kernels above are compiled from the same element step
 //                                 and chunk walk with the options off at compile time: not one of their instructions knows of them.
+//   wsmg_grad_norm_multi{,_hyper}_gated   the guard's finalize behind an external gate word (grad_guard_finalize_gated_kernel): a
+//                                 non-zero gate[0] forces the skip — the element kernels above do not change, they read the flag.
 // No host synchronisation anywhere.
 #include "wsmg_common.h"
 
@@ -268,13 +270,26 @@ __global__ __launch_bounds__(256) void grad_sumsq_multi_kernel(GradBatch b) {
 // One workgroup: every partial of every launch, strided per thread, then the fixed tree.  Finiteness is judged on the float32 norm
 // and the clip coefficient is clip_grad_norm_'s (max_norm / (norm + 1e-6), clamped to 1; a NaN norm gives a NaN coefficient there
 // too).  The step count advances here, by 1 - skip: a skipped step does not advance the bias corrections.
+// GATED (the _gated entry points; compiled out of the two kernels without a gate): a non-zero gate[0] forces the skip whatever the
+// norm is.  Such a step is skipped for everything that reads the record — skip is non-zero, skipped advances, the step count does
+// not — but it is no finding about the gradients: the record keeps the norm and the coefficient of the last step that was judged,
+// and skip is GUARD_SKIP_GATE (2), not 1, which grad_report_latch_kernel does not latch.
+constexpr float GUARD_SKIP_GATE = 2.f;
+
+template <bool GATED>
 __device__ __forceinline__ void guard_finalize(const double* __restrict__ partials, int total, float max_norm, int skip_nonfinite,
-                                               float* __restrict__ guard, float* __restrict__ step_dev) {
+                                               const float* __restrict__ gate, float* __restrict__ guard,
+                                               float* __restrict__ step_dev) {
   __shared__ double red[4];
   double acc = 0.0;
   for (int i = threadIdx.x; i < total; i += 256) acc += partials[i];
   const double sum = block_sum_d(acc, red);
   if (threadIdx.x == 0) {
+    if (GATED && gate[0] != 0.f) {
+      guard[GUARD_SKIP] = GUARD_SKIP_GATE;
+      guard[GUARD_SKIPPED] += 1.f;
+      return;
+    }
     const float norm = (float)sqrt(sum);
     float coef = 1.f;
     if (max_norm > 0.f) {
@@ -293,14 +308,25 @@ __device__ __forceinline__ void guard_finalize(const double* __restrict__ partia
 __global__ __launch_bounds__(256) void grad_guard_finalize_kernel(const double* __restrict__ partials, int total, float max_norm,
                                                                    int skip_nonfinite, float* __restrict__ guard,
                                                                    float* __restrict__ step_dev) {
-  guard_finalize(partials, total, max_norm, skip_nonfinite, guard, step_dev);
+  guard_finalize<false>(partials, total, max_norm, skip_nonfinite, nullptr, guard, step_dev);
 }
 
 // max_norm from the hyper record's guard row {max_grad_norm or 0 for "no clipping", 0, ...}: the same sums, arithmetic and writes.
 __global__ __launch_bounds__(256) void grad_guard_finalize_hyper_kernel(const double* __restrict__ partials, int total,
                                                                          const float* __restrict__ hyper_guard_row, int skip_nonfinite,
                                                                          float* __restrict__ guard, float* __restrict__ step_dev) {
-  guard_finalize(partials, total, hyper_guard_row[HYPER_MAX_NORM], skip_nonfinite, guard, step_dev);
+  guard_finalize<false>(partials, total, hyper_guard_row[HYPER_MAX_NORM], skip_nonfinite, nullptr, guard, step_dev);
+}
+
+// Both of the above behind an external gate (a device word that another kernel owns: ppo_loss_fwd_gated_kernel's `stopped`).
+// max_norm comes from hyper_guard_row when that is not null, else by value; with gate[0] == 0 the sums, arithmetic and writes are
+// those of the kernel without a gate.
+__global__ __launch_bounds__(256) void grad_guard_finalize_gated_kernel(const double* __restrict__ partials, int total, float max_norm,
+                                                                         const float* __restrict__ hyper_guard_row, int skip_nonfinite,
+                                                                         const float* __restrict__ gate, float* __restrict__ guard,
+                                                                         float* __restrict__ step_dev) {
+  guard_finalize<true>(partials, total, hyper_guard_row ? hyper_guard_row[HYPER_MAX_NORM] : max_norm, skip_nonfinite, gate, guard,
+                       step_dev);
 }
 
 // ---- the per-tensor gradient report (wsmg_grad_report_multi / wsmg_grad_stats_multi): which tensor made the guard skip
@@ -313,7 +339,7 @@ __global__ __launch_bounds__(256) void grad_guard_finalize_hyper_kernel(const do
 //   grad_report_fold_kernel    one workgroup per tensor (ADAM_MAX per launch, table in the kernel arguments): the tensor's float64
 //                              partials in guard_finalize's order (thread t adds chunks t, t + 256, ...; block_sum_d), its scan words
 //                              -> the report row {(float)sqrt(S), max |g|, NaNs, Infs}.  A tensor without chunks gets a zero row.
-//   grad_report_latch_kernel   one workgroup: returns before its first store unless guard[GUARD_SKIP] is set; otherwise the header
+//   grad_report_latch_kernel   one workgroup: returns before its first store unless guard[GUARD_SKIP] is 1; otherwise the header
 //                              {skipped, attempt, first non-finite tensor, largest norm, non-finite tensors, 0, 0, 0} and a copy of
 //                              the report (the rows strided over the threads, the header from thread 0).
 // Every reduction is a maximum or an integer sum (any order gives the same bits) or the float64 tree above; no atomics; thread 0 stores
@@ -425,7 +451,9 @@ __global__ __launch_bounds__(256) void grad_report_latch_kernel(const uint32_t* 
                                                                 uint32_t* __restrict__ latch) {
   __shared__ unsigned long long bred[4];
   __shared__ uint32_t ured[12];
-  if (guard[GUARD_SKIP] == 0.f) return;          // a step that was taken: not one byte of the latch is stored
+  // a step that was taken (0), or one that an external gate skipped (GUARD_SKIP_GATE: the latch names a non-finite gradient, and
+  // such a skip has none): not one byte of the latch is stored
+  if (guard[GUARD_SKIP] != 1.f) return;
   unsigned long long best = 0ull;
   uint32_t notfirst = 0, bad = 0, unused = 0;    // notfirst = ~(lowest non-finite i): a maximum, as block_scan_reduce takes it
   for (int i = threadIdx.x; i < n; i += 256) {
@@ -648,15 +676,20 @@ static int grad_sumsq_launches(const WsmgAdamDesc* descs, int n, double* partial
 // Global L2 norm of the descs' gradients (param / exp_avg / exp_avg_sq are not read) into the guard record.  The partials' capacity
 // is checked against the chunk total.  hyper_guard_row (or null): max_norm is read from it on the device and the by-value max_norm
 // is ignored.
+// gate (or null): the _gated forms' device word; a non-zero gate[0] forces the skip (guard_finalize<true>).
 static int grad_norm_launch(const WsmgAdamDesc* descs, int n, double* partials, long long partials_cap, float max_norm,
-                            const float* hyper_guard_row, int skip_nonfinite, float* guard, float* step_dev, wsmg_stream_t s) {
+                            const float* hyper_guard_row, int skip_nonfinite, float* guard, float* step_dev, wsmg_stream_t s,
+                            const float* gate = nullptr) {
   if (!guard || !partials || partials_cap < 0 || !(max_norm >= 0.f)) return WSMG_EINVAL;
-  if (((uintptr_t)partials & 7) || ((uintptr_t)guard & 3) || ((uintptr_t)step_dev & 3)) return WSMG_EINVAL;
+  if (((uintptr_t)partials & 7) || ((uintptr_t)guard & 3) || ((uintptr_t)step_dev & 3) || ((uintptr_t)gate & 3)) return WSMG_EINVAL;
   const long long total = check_descs(descs, n, DESC_GRAD, DESC_MAX_N);
   if (total < 0) return WSMG_EINVAL;
   if (total > partials_cap) return WSMG_ENOMEM;
   const int base = grad_sumsq_launches(descs, n, partials, s);
-  if (hyper_guard_row)
+  if (gate)
+    hipLaunchKernelGGL(grad_guard_finalize_gated_kernel, dim3(1), dim3(256), 0, wsmg_s(s), (const double*)partials, base, max_norm,
+                       hyper_guard_row, skip_nonfinite, gate, guard, step_dev);
+  else if (hyper_guard_row)
     hipLaunchKernelGGL(grad_guard_finalize_hyper_kernel, dim3(1), dim3(256), 0, wsmg_s(s), (const double*)partials, base,
                        hyper_guard_row, skip_nonfinite, guard, step_dev);
   else
@@ -676,6 +709,21 @@ extern "C" int wsmg_grad_norm_multi_hyper(const WsmgAdamDesc* descs, int n, doub
                                           wsmg_stream_t s) {
   if (!hyper_guard_row || ((uintptr_t)hyper_guard_row & 3)) return WSMG_EINVAL;
   return grad_norm_launch(descs, n, partials, partials_cap, 0.f, hyper_guard_row, skip_nonfinite, guard, step_dev, s);
+}
+
+// The two entry points above behind an external gate: gate[0] != 0 (read on the device, in the finalize) forces the skip.  A NULL or
+// not 4-byte aligned gate is WSMG_EINVAL, with the checks of the entry point each mirrors, before anything is launched.
+extern "C" int wsmg_grad_norm_multi_gated(const WsmgAdamDesc* descs, int n, double* partials, long long partials_cap, float max_norm,
+                                          int skip_nonfinite, const float* gate, float* guard, float* step_dev, wsmg_stream_t s) {
+  if (!gate) return WSMG_EINVAL;
+  return grad_norm_launch(descs, n, partials, partials_cap, max_norm, nullptr, skip_nonfinite, guard, step_dev, s, gate);
+}
+
+extern "C" int wsmg_grad_norm_multi_hyper_gated(const WsmgAdamDesc* descs, int n, double* partials, long long partials_cap,
+                                                const float* hyper_guard_row, int skip_nonfinite, const float* gate, float* guard,
+                                                float* step_dev, wsmg_stream_t s) {
+  if (!gate || !hyper_guard_row || ((uintptr_t)hyper_guard_row & 3)) return WSMG_EINVAL;
+  return grad_norm_launch(descs, n, partials, partials_cap, 0.f, hyper_guard_row, skip_nonfinite, guard, step_dev, s, gate);
 }
 
 // The report's argument checks (the chunk total against both capacities): 0, WSMG_EINVAL or WSMG_ENOMEM.

@@ -11,6 +11,8 @@
 //   ppo_loss_fwd_kernel     habitat-baselines' PPO.update: ratio = exp(logp - old_logp), action_loss = -mean(min(ratio adv, clamp(ratio) adv)),
 //                           value_loss = 0.5 mean(max((v - ret)^2, (v_clipped - ret)^2)) or 0.5 mean((ret - v)^2),
 //                           loss = value_coef value_loss + action_loss - entropy_coef entropy;  + clip fraction and approximate KL
+//   ppo_loss_fwd_gated_kernel   the same forward (ppo_loss_rows, written once) behind a KL gate record: closes the gate when
+//                           approx_kl > limit, and while it is open adds the five figures to a device `sums` and counts the step
 //   ppo_loss_bwd_kernel     d logp, d value, d entropy from d loss, with torch autograd's conventions at ties and clamp edges
 //
 // float32 throughout; every sum in a fixed order, no atomics (the same bits every run); the rows a mask leaves out are DROPPED from
@@ -133,10 +135,12 @@ struct PpoRows {
 
 __device__ __forceinline__ float clampf(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-// One workgroup.  Thread t adds the terms of rows t, t + 256, ... (chunks of 256 rows, in row order), then the 256 partial sums
-// are added by the wave butterfly and the four waves in order: the order never depends on anything but B.
-__global__ __launch_bounds__(256) void ppo_loss_fwd_kernel(PpoRows a, const float* __restrict__ entropy, float* __restrict__ out,
-                                                           float* __restrict__ nsel) {
+// THE forward, for both kernels below.  One workgroup.  Thread t adds the terms of rows t, t + 256, ... (chunks of 256 rows, in row
+// order), then the 256 partial sums are added by the wave butterfly and the four waves in order: the order never depends on anything
+// but B.  Thread 0 stores out[0..5) and nsel and gets the five figures back in the order the trainer sums them, {value_loss,
+// action_loss, entropy, clip_frac, approx_kl}: the very floats it stored (fig is written by thread 0 only).
+__device__ __forceinline__ void ppo_loss_rows(const PpoRows& a, const float* __restrict__ entropy, float* __restrict__ out,
+                                              float* __restrict__ nsel, float (&fig)[5]) {
   __shared__ float red[4];
   float n = 0.f, sa = 0.f, sv = 0.f, sc = 0.f, sk = 0.f;
   const float lo = 1.f - a.clip, hi = 1.f + a.clip;
@@ -165,12 +169,56 @@ __global__ __launch_bounds__(256) void ppo_loss_fwd_kernel(PpoRows a, const floa
   sk = block_sum(sk, red);
   if (threadIdx.x == 0) {
     const float action = -(sa / n), vloss = 0.5f * (sv / n);     // (an empty selection is NaN, as aux_reduce's is)
-    out[0] = a.value_coef * vloss + action - a.entropy_coef * entropy[0];
+    const float ent = entropy[0], frac = sc / n, kl = sk / n;
+    out[0] = a.value_coef * vloss + action - a.entropy_coef * ent;
     out[1] = action;
     out[2] = vloss;
-    out[3] = sc / n;
-    out[4] = sk / n;
+    out[3] = frac;
+    out[4] = kl;
     nsel[0] = n;
+    fig[0] = vloss; fig[1] = action; fig[2] = ent; fig[3] = frac; fig[4] = kl;
+  }
+}
+
+__global__ __launch_bounds__(256) void ppo_loss_fwd_kernel(PpoRows a, const float* __restrict__ entropy, float* __restrict__ out,
+                                                           float* __restrict__ nsel) {
+  float fig[5];
+  ppo_loss_rows(a, entropy, out, nsel, fig);
+}
+
+// The same forward behind a KL gate (Spinning Up's early stop, decided on the device).  gate is a record of WSMG_KL_GATE floats that
+// the host zeroes at the start of an update and nothing but this kernel writes:
+//   gate[KL_STOPPED]     0, or 1 from the first call whose approx_kl > limit until the host clears it (a NaN never sets it)
+//   gate[KL_TAKEN]       calls that found and left the gate open: the steps an optimizer behind the gate takes
+//   gate[KL_SEEN]        calls since the record was cleared: the ordinal of the next minibatch
+//   gate[KL_STOP_ORD]    the ordinal of the call that closed the gate    gate[KL_STOP_KL]  its approx_kl        (both 0 while it is open)
+//   gate[5..8)           not written
+// While the gate is open after this call's decision, sums[i] += fig[i] (float32, one rounding each: what `sums += stack(figures)` of
+// the trainer rounds).  The call that closes the gate adds nothing, and neither does any call after it.  Every word above is a plain
+// store of thread 0 behind the reduction: no atomics, nothing another workgroup reads in this launch.  Counters are float32 integers
+// (exact below 2^24).
+enum { KL_STOPPED = 0, KL_TAKEN = 1, KL_SEEN = 2, KL_STOP_ORD = 3, KL_STOP_KL = 4 };
+
+__global__ __launch_bounds__(256) void ppo_loss_fwd_gated_kernel(PpoRows a, const float* __restrict__ entropy, float limit,
+                                                                 float* __restrict__ out, float* __restrict__ nsel,
+                                                                 float* __restrict__ gate, float* __restrict__ sums) {
+  float fig[5];
+  ppo_loss_rows(a, entropy, out, nsel, fig);
+  if (threadIdx.x == 0) {
+    const float seen = gate[KL_SEEN];
+    bool stopped = gate[KL_STOPPED] != 0.f;
+    if (!stopped && fig[4] > limit) {
+      stopped = true;
+      gate[KL_STOPPED] = 1.f;
+      gate[KL_STOP_ORD] = seen;
+      gate[KL_STOP_KL] = fig[4];
+    }
+    if (!stopped) {
+#pragma unroll
+      for (int i = 0; i < 5; ++i) sums[i] = sums[i] + fig[i];
+      gate[KL_TAKEN] += 1.f;
+    }
+    gate[KL_SEEN] = seen + 1.f;
   }
 }
 
@@ -238,6 +286,18 @@ extern "C" int wsmg_ppo_loss_fwd(const float* logp, const float* old_logp, const
   if (B <= 0 || B > PPO_MAXB) return WSMG_EINVAL;
   PpoRows a{logp, old_logp, adv, value, old_value, ret, mask, clip, value_coef, entropy_coef, clipped_value, B};
   hipLaunchKernelGGL(ppo_loss_fwd_kernel, dim3(1), dim3(256), 0, wsmg_s(stream), a, entropy, out5, nsel);
+  WSMG_RETURN_LAUNCH();
+}
+
+extern "C" int wsmg_ppo_loss_fwd_gated(const float* logp, const float* old_logp, const float* adv, const float* value,
+                                       const float* old_value, const float* ret, const unsigned char* mask, const float* entropy,
+                                       float clip, float value_coef, float entropy_coef, int clipped_value, int B, float kl_limit,
+                                       float* out5, float* nsel, float* gate, float* sums5, wsmg_stream_t stream) {
+  if (!logp || !old_logp || !adv || !value || !old_value || !ret || !entropy || !out5 || !nsel || !gate || !sums5) return WSMG_EINVAL;
+  if (((uintptr_t)gate & 3) || ((uintptr_t)sums5 & 3)) return WSMG_EINVAL;
+  if (B <= 0 || B > PPO_MAXB) return WSMG_EINVAL;
+  PpoRows a{logp, old_logp, adv, value, old_value, ret, mask, clip, value_coef, entropy_coef, clipped_value, B};
+  hipLaunchKernelGGL(ppo_loss_fwd_gated_kernel, dim3(1), dim3(256), 0, wsmg_s(stream), a, entropy, kl_limit, out5, nsel, gate, sums5);
   WSMG_RETURN_LAUNCH();
 }
 

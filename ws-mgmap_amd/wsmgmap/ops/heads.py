@@ -491,10 +491,11 @@ class _PpoLoss(torch.autograd.Function):
     """The clipped-surrogate loss of habitat-baselines' PPO.update in one launch per direction (csrc/wsmg_pg_heads.hip)."""
 
     @staticmethod
-    def forward(ctx, logp, value, entropy, old_logp, adv, old_value, returns, mask, clip, value_coef, entropy_coef, clipped_value):
+    def forward(ctx, logp, value, entropy, old_logp, adv, old_value, returns, mask, clip, value_coef, entropy_coef, clipped_value,
+                gate=None, sums=None, kl_limit=None):
         rows = (logp, old_logp, adv, value, old_value, returns)
-        _req(*rows, entropy, mask)
-        _f32(*rows, entropy)
+        _req(*rows, entropy, mask, gate, sums)
+        _f32(*rows, entropy, gate, sums)
         B = logp.numel()
         if B < 1 or B > PPO_MAX_ROWS or any(r.numel() != B for r in rows) or entropy.numel() != 1:
             raise _abi.WsmgError(f"ppo_loss: six float32 row vectors of one length in [1, {PPO_MAX_ROWS}] and a one-element entropy, got "
@@ -503,8 +504,14 @@ class _PpoLoss(torch.autograd.Function):
             raise _abi.WsmgError(f"ppo_loss: mask must be bool or uint8 with one entry per row ({B})")
         out = torch.empty(5, device=logp.device, dtype=torch.float32)
         nsel = torch.empty(1, device=logp.device, dtype=torch.float32)
-        _abi.call("wsmg_ppo_loss_fwd", _p(logp), _p(old_logp), _p(adv), _p(value), _p(old_value), _p(returns), _p(mask), _p(entropy),
-                  clip, value_coef, entropy_coef, int(clipped_value), B, _p(out), _p(nsel), _stream())
+        if gate is None:
+            _abi.call("wsmg_ppo_loss_fwd", _p(logp), _p(old_logp), _p(adv), _p(value), _p(old_value), _p(returns), _p(mask), _p(entropy),
+                      clip, value_coef, entropy_coef, int(clipped_value), B, _p(out), _p(nsel), _stream())
+        else:
+            _abi.call("wsmg_ppo_loss_fwd_gated", _p(logp), _p(old_logp), _p(adv), _p(value), _p(old_value), _p(returns), _p(mask),
+                      _p(entropy), clip, value_coef, entropy_coef, int(clipped_value), B, kl_limit, _p(out), _p(nsel), _p(gate), _p(sums),
+                      _stream())
+            torch.autograd.graph.increment_version([gate, sums])       # written through raw pointers
         ctx.save_for_backward(logp, old_logp, adv, value, old_value, returns, mask, nsel)
         ctx.hyper = (clip, value_coef, entropy_coef, int(clipped_value))
         ctx.shapes = (logp.shape, value.shape, entropy.shape)
@@ -522,10 +529,23 @@ class _PpoLoss(torch.autograd.Function):
         _abi.call("wsmg_ppo_loss_bwd", _p(logp), _p(old_logp), _p(adv), _p(value), _p(old_value), _p(returns), _p(mask), _p(nsel),
                   _p(dloss), *ctx.hyper, B, _p(dlogp), _p(dvalue), _p(dent), _stream())
         s_logp, s_value, s_ent = ctx.shapes
-        return (dlogp.view(s_logp), dvalue.view(s_value), dent.view(s_ent)) + (None,) * 9
+        return (dlogp.view(s_logp), dvalue.view(s_value), dent.view(s_ent)) + (None,) * 12
 
 
-def ppo_loss(logp, old_logp, adv, value, old_value, returns, entropy, clip, value_coef, entropy_coef, clipped_value=True, mask=None):
+# The KL gate record of wsmg_ppo_loss_fwd_gated (include/wsmgmap.h): KL_GATE float32 words, zeroed by the host at the start of an
+# update, written by that kernel alone.  Word 0 is what `wsmgmap.optim.Adam.set_step_gate` reads.
+KL_GATE = 8
+KL_STOPPED, KL_TAKEN, KL_SEEN, KL_STOP_ORDINAL, KL_STOP_KL = 0, 1, 2, 3, 4
+
+
+def kl_limit_of(target_kl):
+    """Spinning Up's threshold as the gated loss compares it: float32(1.5 * target_kl), the product formed in double and rounded once
+    (returned as the Python float of that float32)."""
+    return float(torch.tensor(1.5 * float(target_kl), dtype=torch.float64).to(torch.float32))
+
+
+def ppo_loss(logp, old_logp, adv, value, old_value, returns, entropy, clip, value_coef, entropy_coef, clipped_value=True, mask=None,
+             gate=None, sums=None, kl_limit=None):
     """-> (loss, action_loss, value_loss, clip_frac, approx_kl), 0-dim tensors; only `loss` is differentiable, towards logp,
     value and entropy (old_logp, adv, old_value and returns take no gradient).
         ratio = exp(logp - old_logp);  action_loss = -mean(min(ratio adv, clamp(ratio, 1 - clip, 1 + clip) adv))
@@ -534,10 +554,32 @@ def ppo_loss(logp, old_logp, adv, value, old_value, returns, entropy, clip, valu
         loss = value_coef value_loss + action_loss - entropy_coef entropy
         clip_frac = mean(|ratio - 1| > clip);  approx_kl = mean(old_logp - logp)
     The rows are float32 GPU tensors with B elements each ([B] or [B, 1]); entropy has one element; mask [B] bool or uint8 selects
-    the rows the means run over (none selected: NaN, as `aux_reduce`)."""
+    the rows the means run over (none selected: NaN, as `aux_reduce`).
+
+    gate, sums, kl_limit (all three or none): the same launch behind a KL gate — a PPO update's early stop, decided on the device.
+    `gate` is a contiguous float32 GPU record of KL_GATE words that the caller zeroes at the start of an update:
+        gate[KL_STOPPED]       set to 1 by the first call whose approx_kl > float32(kl_limit), and left set until the caller clears it
+                               (a NaN approx_kl does not set it); word 0: what `Adam.set_step_gate(gate)` makes the step obey
+        gate[KL_TAKEN]         calls that left the gate open (the steps taken)      gate[KL_SEEN]  calls since the record was cleared
+        gate[KL_STOP_ORDINAL], gate[KL_STOP_KL]   the ordinal (from 0) and the approx_kl of the call that closed the gate
+    and while the gate is open `sums[0:5] += (value_loss, action_loss, entropy, clip_frac, approx_kl)` in float32 (`sums`: a contiguous
+    float32 GPU tensor of at least 5 elements); the call that closes the gate and the calls after it add nothing.  The five outputs
+    and the gradients are those of the call without a gate, bit for bit: a stopped call's gradients are computed, and it is the gated
+    optimizer step that applies none of them.  No host synchronisation; capturable."""
     c = lambda t: t.contiguous()    # noqa: E731
+    if (gate is None) != (sums is None) or (gate is None) != (kl_limit is None):
+        raise _abi.WsmgError("ppo_loss: gate, sums and kl_limit come together (all three, or none)")
+    if gate is not None:
+        for name, t, n in (("gate", gate, KL_GATE), ("sums", sums, 5)):
+            if not (torch.is_tensor(t) and t.is_contiguous() and t.dim() == 1 and t.numel() >= n and not t.requires_grad):
+                raise _abi.WsmgError(f"ppo_loss: {name} must be a contiguous 1-d float32 GPU tensor of at least {n} elements (it is "
+                                     "written in place)")
+        kl_limit = float(kl_limit)
+        if kl_limit != kl_limit:
+            raise _abi.WsmgError("ppo_loss: kl_limit is NaN (no approx_kl compares above it: pass inf for a gate that never closes)")
     return _PpoLoss.apply(c(logp), c(value), c(entropy), c(old_logp), c(adv), c(old_value), c(returns),
-                          None if mask is None else c(mask), float(clip), float(value_coef), float(entropy_coef), bool(clipped_value))
+                          None if mask is None else c(mask), float(clip), float(value_coef), float(entropy_coef), bool(clipped_value),
+                          gate, sums, kl_limit)
 
 
 ROWS_MAX = 16     # rollout-size dense layers: up to this many rows go through linear_rows / act_heads

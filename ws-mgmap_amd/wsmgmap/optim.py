@@ -25,6 +25,10 @@ row per parameter {norm, max |g| over the finite elements, NaN count, Inf count}
 header into a latch that keeps them until the host reads it, however many clean steps (or graph replays) follow.  `grad_report()`
 and `last_skipped()` read them back; `grad_stats(params)` is the table alone, beside `global_grad_norm`.
 
+`Adam(a guard option).set_step_gate(word)` puts the guarded step behind a device word that another kernel owns (the KL early stop of
+`wsmgmap.ppo.PPO`): while it is non-zero the finalize of the norm (wsmg_grad_norm_multi_gated) forces the skip, with everything a skip
+entails (no write, no step count, the BatchNorm roll-back) except the latch of the gradient report.
+
 `Adam(amsgrad=True)`, `Adam(maximize=True)` and `AdamW(...)` (torch.optim.AdamW's decoupled weight decay, default 1e-2) step through
 the `_ext` entry points (wsmg_adam_step_multi_ext and its three siblings): the same element step with the option's roundings added,
 behind kernels of their own.  They combine with each other and with every option above.  With none of the three set, `step()` calls
@@ -222,6 +226,7 @@ class Adam(torch.optim.Optimizer):
         self._guard = None        # device tensors of the guarded step: the record {norm, coef, skip, skipped}, the step count
         self._guard_step = None   # and the norm's float64 workspace (allocated below, never by a default construction)
         self._partials = None
+        self._step_gate = None    # set_step_gate: a device word that forces the guarded step to skip while it is non-zero
         if guard_buffers is not None and not self._skip_nonfinite:
             raise ValueError("guard_buffers needs skip_nonfinite=True: nothing else ever triggers the roll-back")
         self._guard_buffers = guard_buffers
@@ -387,6 +392,27 @@ class Adam(torch.optim.Optimizer):
             value = float(value)
             _check_max_grad_norm(value)
         self._max_grad_norm = value
+
+    def set_step_gate(self, gate):
+        """Put the guarded step behind an external gate: `gate` is a float32 CUDA tensor on the parameters' device whose element 0
+        another kernel owns (the `stopped` word of `ops.ppo_loss(..., gate=...)`), or None to take the gate away.  While gate[0] is
+        non-zero every `step()` is skipped on the device, whatever its gradients are — parameters, moments and the device step count
+        stay, `guard_buffers` rolls back, `skipped_steps` advances (so `state_dict()`'s `step` stays the steps taken, and
+        `note_replayed_steps` stays right) — and `grad_norm` keeps the last judged step's norm; such a skip is no finding about the
+        gradients, so `last_skipped()` does not report it.  With gate[0] == 0 the step is the step without a gate, bit for bit.
+        The word is read on the device at each step (wsmg_grad_norm_multi_gated): no host synchronisation, and a step captured in a
+        graph obeys it at every replay — set the gate before capturing.  Only the guarded step has a skip to force: an optimizer
+        without max_grad_norm / skip_nonfinite refuses (ValueError)."""
+        if gate is None:
+            self._step_gate = None
+            return
+        if not self._guarded:
+            raise ValueError("wsmgmap.optim.Adam.set_step_gate needs the guarded step (max_grad_norm / skip_nonfinite): only that step "
+                             "reads a skip flag on the device; construct the optimizer with skip_nonfinite=True")
+        if not (torch.is_tensor(gate) and gate.is_cuda and gate.dtype == torch.float32 and gate.numel() >= 1 and gate.is_contiguous()):
+            raise ValueError("wsmgmap.optim.Adam.set_step_gate: the gate must be a contiguous float32 CUDA tensor with at least one "
+                             f"element (element 0 is read), got {gate!r}")
+        self._step_gate = gate
 
     def add_param_group(self, param_group):
         if self._hyper_fixed:
@@ -608,7 +634,13 @@ class Adam(torch.optim.Optimizer):
             # the finalize advances the step count by 1 - skip: a skipped step does not advance the bias corrections
             norm, max_norm = (("wsmg_grad_norm_multi_hyper", self._hyper_row(len(self.param_groups))) if self._hyper_on_device
                               else ("wsmg_grad_norm_multi", self._max_grad_norm or 0.0))
-            _abi.call(norm, descs, len(every), partials, self._partials.numel(), max_norm, int(self._skip_nonfinite), guard, sd, stream)
+            if self._step_gate is None:
+                _abi.call(norm, descs, len(every), partials, self._partials.numel(), max_norm, int(self._skip_nonfinite), guard, sd, stream)
+            else:     # the same norm; the finalize also reads the gate's word and skips while it is set
+                if self._step_gate.device != dev:
+                    raise _abi.WsmgError("wsmgmap.optim.Adam.set_step_gate: the gate is not on the stepped parameters' device")
+                _abi.call(norm + "_gated", descs, len(every), partials, self._partials.numel(), max_norm, int(self._skip_nonfinite),
+                          _ptr(self._step_gate), guard, sd, stream)
             if rows is not None:
                 # descriptors of their own over ALL parameters: the stepped list with a zero-length one for every parameter without a
                 # gradient — those own no chunk, so the norm's partials line up, and no row ever shifts
@@ -635,7 +667,8 @@ class Adam(torch.optim.Optimizer):
 
     @property
     def skipped_steps(self):
-        """How many guarded steps found a non-finite norm and wrote nothing (since construction or load_state_dict): one readback."""
+        """How many guarded steps found a non-finite norm, or a step gate that was set, and wrote nothing (since construction or
+        load_state_dict): one readback."""
         return 0 if self._guard is None else int(self._guard[3].item())
 
     def _report_names(self, names):
