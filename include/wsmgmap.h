@@ -435,6 +435,35 @@ int wsmg_grad_stats_multi(const WsmgAdamDesc* descs, int n, double* partials, lo
  * env WSMG_CONV_WIN3).
  * Returns the previous choice.  No reference counterpart (the reference calls torch.nn.Conv2d, map_encoder.py:29-112). */
 int wsmg_conv_debug_win3_tile(int mt);
+/* Tests / tools: the kernel the bf16 conv engine runs for one call — the answer of the one function its launchers switch on, so what
+ * this reports is what a launch with the same arguments takes (the debug tile above and the WSMG_* tunes included).  Host only:
+ * queues nothing, touches no device beyond the cached CU count (256 where there is none).
+ * pass: WSMG_CONV_FWD (the wsmg_conv2d_fwd_bf16 family), WSMG_CONV_BWD_DATA, WSMG_CONV_BWD_WEIGHT; the geometry is the convolution's
+ * in every pass (x [B][H][W][Cin], y [B][OH][OW][Cout]).  needs: what the call asks beyond a plain bf16 output, as bits —
+ *   WSMG_NEED_F32     a float32 or accumulated output: forward flags & 5, backward-data flags & 7
+ *   WSMG_NEED_SLICE   forward: y_ld != Cout, the output is a channel slice      WSMG_NEED_STATS  BatchNorm sums (moves no route)
+ *   WSMG_NEED_RELU_Y  backward-data: the gradient is masked with relu_y         WSMG_NEED_SPLIT  ... and stored as two tensors (dx2)
+ * route [WSMG_ROUTE_WORDS] ints: [WSMG_RW_KIND] the family, one of WSMG_ROUTE_*; [WSMG_RW_MT] the 3x3 window's pixels per workgroup
+ * and [WSMG_RW_BY_SHAPE] whether the shape chose it (0: forced); weight gradient: [WSMG_RW_NSPLIT] the slabs of the plan call, and for
+ * the generic kernel its tile [WSMG_RW_TC] x 32 output channels by [WSMG_RW_TU] x 4 units, grid [WSMG_RW_GX] x [WSMG_RW_GY] x nsplit
+ * and [WSMG_RW_CHUNK] pixels per split; words that do not apply are 0.
+ * WSMG_EINVAL: a geometry the engine refuses, an unknown pass, a needs bit the pass does not have, NULL route. */
+enum { WSMG_CONV_FWD = 0, WSMG_CONV_BWD_DATA = 1, WSMG_CONV_BWD_WEIGHT = 2 };
+enum { WSMG_NEED_F32 = 1, WSMG_NEED_SLICE = 2, WSMG_NEED_RELU_Y = 4, WSMG_NEED_SPLIT = 8, WSMG_NEED_STATS = 16 };
+enum { WSMG_ROUTE_IGEMM = 0,            /* implicit GEMM (forward / backward-data) */
+       WSMG_ROUTE_STEM_WIN = 1,         /* k8 s2 stem out of an LDS window, forward */
+       WSMG_ROUTE_WIN3 = 2,             /* 3x3 LDS-window kernel */
+       WSMG_ROUTE_WIN3_K32 = 3,         /* its form for a 32-channel reduction axis */
+       WSMG_ROUTE_CONVT_K4S2 = 4,       /* ConvTranspose k4 s2 (a backward-data pass) */
+       WSMG_ROUTE_WGRAD = 5,            /* generic weight gradient */
+       WSMG_ROUTE_WGRAD_STEM_WIN = 6,   /* k8 stem window weight gradient */
+       WSMG_ROUTE_WGRAD_WIN3 = 7,       /* 3x3 window weight gradient */
+       WSMG_ROUTE_WGRAD_S2WIN = 8 };    /* k5 / k7 stride-2 window weight gradient */
+enum { WSMG_RW_KIND = 0, WSMG_RW_MT = 1, WSMG_RW_BY_SHAPE = 2, WSMG_RW_NSPLIT = 3, WSMG_RW_TC = 4, WSMG_RW_TU = 5, WSMG_RW_GX = 6,
+       WSMG_RW_GY = 7, WSMG_RW_CHUNK = 8 };
+#define WSMG_ROUTE_WORDS 9
+int wsmg_conv_route_bf16(int pass, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH, int OW,
+                         int needs, int* route);
 int wsmg_bn_act_fwd_bf16_pre(const void* x, const void* residual, const float* gamma, const float* beta, float* running_mean,
                              float* running_var, float momentum, float eps, int relu, int64_t rows, int C, void* y,
                              float* save_mean, float* save_invstd, double* stats, int nslab, wsmg_stream_t stream);

@@ -1,8 +1,9 @@
 """GPU tests per compiled kernel INSTANTIATION: the entry points of libwsmgmap.so are host-side dispatchers that pick one of several
 template instantiations from the shape, and a test proves only the instantiation its shape selects.  Every case here is chosen so
-that the dispatcher provably takes a form that profiles/kernel_coverage_before.txt lists as never launched by the rest of the suite
-(the selection is asserted where the ABI exposes it; otherwise profiles/kernel_coverage.txt, the trace of the suite with this file,
-is the proof), and is compared with a float64 CPU evaluation of the same operator on oracle.detfill inputs.  Tolerances are those of
+that the dispatcher takes a form that profiles/kernel_coverage_before.txt lists as never launched by the rest of the suite (the
+selection is asserted where the ABI exposes it — for the bf16 convolutions the kernel family and tile that wsmg_conv_route_bf16 reports,
+the function the launchers switch on; otherwise profiles/kernel_coverage.txt, the trace of the suite with this file, is the proof), and
+is compared with a float64 CPU evaluation of the same operator on oracle.detfill inputs.  Tolerances are those of
 the neighbouring test of the same kernel family; they are quoted at each assert."""
 import ctypes
 
@@ -11,6 +12,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_route_util as cr
 from oracle import detfill as df
 from util import T
 
@@ -197,8 +199,10 @@ def test_implicit_gemm_conv_tiles_match_float64(ops, cfg, dtype):
 
 def test_conv_fwd_ex_channel_slice_on_the_implicit_gemm_route(ops):
     """wsmg_conv2d_fwd_bf16_ex (y_ld: the output is a channel slice of a wider tensor) on the implicit-GEMM kernel — a 5 x 5 layer, which
-    no window kernel takes: the slice equals float64 within one bf16 rounding, the other channels of the wide tensor keep their value."""
+    no window kernel takes (asserted on the route): the slice equals float64 within one bf16 rounding, the other channels of the wide
+    tensor keep their value."""
     B, Cin, Cout, H, W, Ctot, c_off = 2, 64, 96, 11, 14, 160, 32
+    assert cr.route(cr.FWD, cr.dims(B, Cin, Cout, 5, 1, 2, H, W), cr.SLICE)["kind"] == "IGEMM"
     x = T(df.uniform("inst.ex.x", (B, Cin, H, W), 2.0)).to(torch.bfloat16)
     w = T(df.uniform("inst.ex.w", (Cout, Cin, 5, 5), float(np.sqrt(12.0 / (Cin * 25)))))
     b = T(df.uniform("inst.ex.b", (Cout,), 0.5))
@@ -214,7 +218,7 @@ def test_stem_window_conv_statistics_match_the_implicit_gemm_route():
     """The k8 s2 p3 64 -> 64 stem through wsmg_conv2d_fwd_bf16_stats: conv_win_fwd_kernel flushes its BatchNorm sums once per workgroup run
     (the half-wave exchange on float64), the one statistics path no test held against a second route.  52 x 52 -> 26 x 26 with 5 x 25 tiles: a
     partial tile column (1 of 25) and a partial tile row (1 of 5), B = 3, 8 slabs.  The second route is the implicit-GEMM kernel, which
-    wsmg_conv2d_fwd_bf16_ex takes in this process when the output is a channel slice (y_ld != Cout).  Outputs bit for bit; both routes'
+    wsmg_conv2d_fwd_bf16_ex takes when the output is a channel slice (y_ld != Cout; both routes asserted).  Outputs bit for bit; both routes'
     sums against float64 sums of the returned bf16 output to 1e-6 relative (the bar of tests/test_gpu_round6.py for this quantity)."""
     from wsmgmap import _abi, ops
     B, H, C, OH, nslab = 3, 52, 64, 26, 8
@@ -222,6 +226,7 @@ def test_stem_window_conv_statistics_match_the_implicit_gemm_route():
     w = T(df.uniform("inst.stem.w", (C, 8, 8, C), float(np.sqrt(12.0 / (C * 64))))).to(torch.bfloat16).cuda()      # OHWI
     bias = T(df.uniform("inst.stem.b", (C,), 0.5)).cuda()
     args = (B, H, H, C, C, 8, 8, 2, 3, OH, OH)
+    assert cr.route(cr.FWD, args, cr.STATS)["kind"] == "STEM_WIN" and cr.route(cr.FWD, args, cr.STATS | cr.SLICE)["kind"] == "IGEMM"
     P, st = ops._p, ops._stream
     y_win = torch.empty(B, OH, OH, C, device="cuda", dtype=torch.bfloat16)
     wide = torch.full((B, OH, OH, C + 64), 7.0, device="cuda", dtype=torch.bfloat16)
@@ -240,11 +245,14 @@ def test_stem_window_conv_statistics_match_the_implicit_gemm_route():
         assert rel < 1e-6, (name, rel)
 
 
-def _bwd_data_ex_case(name, B, Cin, Cout, k, s, p, H, W, ca):
+def _bwd_data_ex_case(name, B, Cin, Cout, k, s, p, H, W, ca, family, mt=0, by_shape=0):
     """wsmg_conv2d_bwd_data_bf16_ex with relu_y (the gradient is masked with the consumed tensor's ReLU) and dx2 / split_c (it is stored
-    as two contiguous channel parts) against the masked float64 input gradient of the same bf16 operands; bar of the bf16 engine."""
+    as two contiguous channel parts) against the masked float64 input gradient of the same bf16 operands; bar of the bf16 engine.
+    family, mt, by_shape: the route the call must report before it is launched."""
     from wsmgmap import _abi, ops
     OH, OW = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+    r = cr.route(cr.BWD_DATA, (B, H, W, Cin, Cout, k, k, s, p, OH, OW), cr.RELU_Y | cr.SPLIT)
+    assert (r["kind"], r["mt"], r["by_shape"]) == (family, mt, by_shape), (name, r)
     w = T(df.uniform(f"inst.{name}.w", (Cout, Cin, k, k), float(np.sqrt(12.0 / (Cout * k * k))))).to(torch.bfloat16)
     gy = T(df.uniform(f"inst.{name}.gy", (B, Cout, OH, OW), 2.0)).to(torch.bfloat16)
     z = T(df.uniform(f"inst.{name}.z", (B, Cin, H, W), 2.0)).to(torch.bfloat16)         # the tensor whose ReLU masks the gradient
@@ -263,8 +271,8 @@ def _bwd_data_ex_case(name, B, Cin, Cout, k, s, p, H, W, ca):
 
 def test_conv_bwd_data_ex_mask_and_split_on_the_implicit_gemm_route():
     """The mask / split arguments on the implicit-GEMM kernel, stride 2 with odd unequal sizes (four parity classes of different
-    size) — a geometry no window kernel takes."""
-    _bwd_data_ex_case("bex.igemm", 2, 96, 64, 3, 2, 1, 11, 15, 32)
+    size) — a geometry no window kernel takes (asserted on the route)."""
+    _bwd_data_ex_case("bex.igemm", 2, 96, 64, 3, 2, 1, 11, 15, 32, "IGEMM")
 
 
 # (name, forced tile (1 = by shape), B, H = W, Cin = produced channels N, Cout = reduction channels Kc).  The window kernel takes a tile
@@ -275,6 +283,8 @@ def test_conv_bwd_data_ex_mask_and_split_on_the_implicit_gemm_route():
 #   mixed256_n128: the 128-pixel remainder tiles need window_bound(128) <= 256, which 48 x 48 misses (337) and 24 x 24 meets
 #     (128 + 12 + 52 + 54 + 1 = 247; window_bound(256) = 385 <= 512); B = 232: the same 133 632 pixels, 522 tiles of 256 = two whole
 #     rounds + 10: conv_win3_mixed_kernel<256, 4, 2, 128, 1>.
+# The test asserts the family, the tile (the forced one, or 256 / 512 by shape as the case's name says) and by_shape on the queried route;
+# the choice between the mixed and the plain launch of a tile stays inside the kernel's file (the arithmetic above).
 WIN3_AUX = [
     ("t256_n128", 256, 29, 48, 128, 64), ("t256_n64", 256, 29, 48, 64, 64), ("t256_n32", 256, 29, 48, 32, 32),
     ("t512_n128", 512, 29, 48, 128, 64), ("t512_n64", 512, 29, 48, 64, 64), ("t512_n32", 512, 29, 48, 32, 32),
@@ -292,16 +302,18 @@ def test_window_conv_mask_and_split_store_forms(cfg):
     L = _abi.lib()
     prev = L.wsmg_conv_debug_win3_tile(tile)
     try:
-        _bwd_data_ex_case("w3aux." + name, B, Cin, Cout, 3, 1, 1, HW, HW, Cin // 4 if Cin > 32 else 8)
+        mt = tile if tile != 1 else int(name[len("mixed"):name.index("_")])
+        _bwd_data_ex_case("w3aux." + name, B, Cin, Cout, 3, 1, 1, HW, HW, Cin // 4 if Cin > 32 else 8, "WIN3", mt, int(tile == 1))
     finally:
         L.wsmg_conv_debug_win3_tile(prev)
 
 
 # ----------------------------------------------------------------------------- generic bf16 weight gradient: every (TC, TU, UPT) form
-# conv_wgrad_bf16_kernel<TC, TU, 1, UPT> (csrc/wsmg_conv_bf16.hip, wgrad_plan_bf16 / launch_wgrad_bf16), units = k k Cin / 32:
+# conv_wgrad_bf16_kernel<TC, TU, 1, UPT> (csrc/wsmg_conv_bf16.hip, wsmg_conv_wgrad_plan / launch_wgrad_bf16), units = k k Cin / 32:
 #   TC = 4 (128 output channels per tile) when Cout % 128 == 0 and units >= 48, then TU = 2;  else TC = 2, and TU = 2 only for
 #   Cin == 64 with units >= 128 (an 8 x 8 kernel);  UPT = the largest power of two <= 4 TU that divides Cin / 32.
-# None of these geometries is one a window kernel takes (1 x 1, 3 x 3 stride 2, 4 x 4, 5 x 5 stride 1, 7 x 7 stride 1, 8 x 8 stride 1).
+# None of these geometries is one a window kernel takes (1 x 1, 3 x 3 stride 2, 4 x 4, 5 x 5 stride 1, 7 x 7 stride 1, 8 x 8 stride 1): the
+# test asserts that the queried route is the generic kernel with the (TC, TU) of _wgrad_form and the plan call's nsplit.
 # (name, (TC, TU, UPT), B, Cin, Cout, k, stride, pad, H, W)
 WGRAD = [
     ("t42u8_k3s2_c256", (4, 2, 8), 11, 256, 128, 3, 2, 1, 13, 17),
@@ -348,6 +360,9 @@ def test_generic_bf16_weight_gradient_forms(cfg):
     chunk = -(-(-(-npix // ns.value)) // WKP) * WKP
     assert ns.value >= 1 and -(-npix // chunk) == ns.value and fl.value == ns.value * Cout * k * k * Cin, (ns.value, npix)
     assert npix % chunk != 0, "choose a pixel count that leaves the last split short"
+    r = cr.route(cr.BWD_WEIGHT, dims)
+    assert (r["kind"], r["tc"], r["tu"]) == ("WGRAD",) + form[:2] and r["nsplit"] == ns.value, r
+    assert r["chunk"] % WKP == 0 and -(-npix // r["chunk"]) == ns.value and npix % r["chunk"] != 0, r      # (the kernel's own chunk)
     want = torch.nn.grad.conv2d_weight(x.double().permute(0, 3, 1, 2), (Cout, Cin, k, k), dy.double().permute(0, 3, 1, 2), stride=s, padding=p)
     scale = float(want.abs().max())
     xg, dyg = x.cuda(), dy.cuda()

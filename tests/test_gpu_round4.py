@@ -447,10 +447,14 @@ def test_small_channel_window_weight_gradients_3x3(shape):
     dims = (B, H, W, Cin, Cout, 3, 3, 1, 1, H, W)
     _abi.call("wsmg_conv2d_bwd_weight_bf16_plan", *dims, ctypes.cast(ctypes.byref(ns), ctypes.c_void_p), ctypes.cast(ctypes.byref(fl), ctypes.c_void_p))
     assert 1 <= ns.value <= 256, f"{ns.value} slabs: the layer did not take the window kernel's plan"
+    import conv_route_util as cr
+    r = cr.route(cr.BWD_WEIGHT, dims)
+    assert (r["kind"], r["nsplit"]) == ("WGRAD_WIN3", ns.value), r
 
     def atomic(tile):
         prev = _abi.lib().wsmg_conv_debug_win3_tile(tile)
         try:
+            assert cr.route(cr.BWD_WEIGHT, dims)["kind"] == ("WGRAD_WIN3" if tile else "WGRAD")      # tile 0: window kernels off
             dw = torch.zeros(Cout, 3, 3, Cin, device="cuda")
             _abi.call("wsmg_conv2d_bwd_weight_bf16", P(x), P(gy), P(dw), *dims, st)
             torch.cuda.synchronize()
@@ -493,6 +497,9 @@ def test_stride2_window_weight_gradients(geom):
     ns, fl = ctypes.c_int(0), ctypes.c_longlong(0)
     _abi.call("wsmg_conv2d_bwd_weight_bf16_plan", *dims, ctypes.cast(ctypes.byref(ns), ctypes.c_void_p), ctypes.cast(ctypes.byref(fl), ctypes.c_void_p))
     assert ns.value % 8 == 0 and ns.value <= 48, f"{ns.value} slabs: not the stride-2 window kernel's plan"
+    import conv_route_util as cr
+    r = cr.route(cr.BWD_WEIGHT, dims)
+    assert (r["kind"], r["nsplit"]) == ("WGRAD_S2WIN", ns.value), r
     want = torch.nn.grad.conv2d_weight(x.double().permute(0, 3, 1, 2), (Cout, Cin, K, K), dy.double().permute(0, 3, 1, 2), stride=2, padding=pad)
     scale = float(want.abs().max())
     dw = torch.zeros(Cout, K, K, Cin, device="cuda")

@@ -292,9 +292,17 @@ def test_k32_window_convolution_is_bit_identical_to_the_general_window_kernel(B,
     P, st = ops._p, ops._stream
     nslab = 8
     outs = {}
-    for mt in (256, 1):       # 256: the general window kernel's 256-pixel tile, forced; 1: by shape = the k32 kernel
+    import conv_route_util as cr
+    for mt in (256, 1):       # 256: a forced tile keeps the k32 kernel off; 1: by shape = the k32 kernel
         old = _abi.lib().wsmg_conv_debug_win3_tile(mt)
         try:
+            # the kernels the four calls below take, as the route reports them: by shape the k32 kernel every time; forced, the general
+            # window kernel's 256-pixel tile — or, forward with 64 / 128 output channels (64-channel tiles want Kc >= 64), implicit GEMM
+            other = "WIN3" if Cout % 64 else "IGEMM"
+            for needs in (0, cr.STATS, cr.SLICE):
+                assert cr.route(cr.FWD, args, needs)["kind"] == ("WIN3_K32" if mt == 1 else other), (mt, needs)
+            r = cr.route(cr.BWD_DATA, args)     # (its reduction axis is Cout: the k32 kernel for the 32 -> 32 layers only)
+            assert (r["kind"], r["mt"]) == (("WIN3_K32", 0) if mt == 1 and Cout == 32 else ("WIN3", 256)), (mt, r)
             y0 = torch.empty(B, H, H, Cout, device="cuda", dtype=torch.bfloat16)
             y1 = torch.empty_like(y0)
             wide = torch.full((B, H, H, Cout + 64), 7.0, device="cuda", dtype=torch.bfloat16)
@@ -366,9 +374,12 @@ def test_convtranspose_k4s2_kernel_is_bit_identical_to_the_implicit_gemm_route(B
     P, st = ops._p, ops._stream
     nslab = 8
     outs = {}
+    import conv_route_util as cr
     for mt in (256, 1):       # 256: a forced window tile turns the by-shape choice off -> implicit-GEMM kernel; 1: by shape
         old = _abi.lib().wsmg_conv_debug_win3_tile(mt)
         try:
+            for needs in (0, cr.STATS):
+                assert cr.route(cr.BWD_DATA, dims, needs)["kind"] == ("CONVT_K4S2" if mt == 1 else "IGEMM"), (mt, needs)
             y0 = torch.empty(B, 2 * H, 2 * H, 32, device="cuda", dtype=torch.bfloat16)
             y1 = torch.empty_like(y0)
             stats = torch.zeros(nslab, 2, 32, device="cuda", dtype=torch.float64)

@@ -105,38 +105,61 @@ __device__ __forceinline__ double block_sum_d(double v, double* red) {
   return red[0] + red[1] + red[2] + red[3];
 }
 
-// wsmg_conv_win.hip: direct convolution with an LDS-resident input window (64 -> 64 channels, k8 s2 p3); WSMG_EINVAL for
-// any other shape
+// The bf16 conv engine.  Which kernel family takes a layer is decided in ONE place, wsmg_conv_route (wsmg_conv_route.hip, where the
+// tunes are listed); the launchers of wsmg_conv_bf16.hip switch on its answer.  Each kernel file owns the acceptance test of its
+// kernel — the function the route asks and the entry point's own argument check (a `_fits` answers yes / no, a `_splits` / `_grid`
+// the slab / workgroup count, 0 = the layer is not this kernel's) — so an entry point that answers WSMG_EINVAL to a routed layer is a
+// bug, which the launchers hand back, not a reason to try another kernel.
+struct WsmgConvRoute {
+  int kind;                     // WSMG_ROUTE_*: the kernel family
+  int mt, by_shape, mixed;      // 3 x 3 window: pixels per workgroup; chosen by shape (not forced); half-size tiles allowed in the last round
+  int wgs;                      // k32 / ConvTranspose: workgroups per CU
+  int nsplit;                   // weight gradient: partial sums (pixel chunks / image ranges / tile groups) = slabs of the deterministic form
+  int tc, tu, gx, gy;           // generic weight gradient: tile shape and grid
+  int64_t chunk;                //   ... and pixels per split
+};
+// pass: WSMG_CONV_FWD / _BWD_DATA / _BWD_WEIGHT; the geometry is the convolution's (x [B][H][W][Cin], y [B][OH][OW][Cout]) in every pass
+// and has passed wsmg_check_conv_bf16; needs: the WSMG_NEED_* bits of the call, everything about it that is no pointer
+WsmgConvRoute wsmg_conv_route(int pass, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH, int OW, int needs);
+// wsmg_conv_bf16.hip: the generic weight-gradient kernel's plan (tc .. chunk, nsplit), written into r
+void wsmg_conv_wgrad_plan(int B, int Cin, int Cout, int KH, int KW, int OH, int OW, WsmgConvRoute& r);
+// wsmg_conv_win.hip: direct convolution with an LDS-resident input window (64 -> 64 channels, k8 s2 p3)
+bool wsmg_conv_win_fits(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad);
 int wsmg_conv_win_fwd_bf16(const void* x, const void* w_ohwi, const float* bias, void* y, int relu, double* stats, int nslab, int B,
                            int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH, int OW, hipStream_t s);
-// wsmg_conv_win_wgrad.hip: weight gradient of the same layer out of an LDS-resident input window; WSMG_EINVAL for any other shape
+// wsmg_conv_win_wgrad.hip: weight gradient of the same layer out of an LDS-resident input window (its test: winw_fits)
+int wsmg_conv_win_wgrad_splits(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH, int OW);
 int wsmg_conv_win_wgrad_bf16(const void* x, const void* dy, float* dw_ohwi, long long slab_floats, int B, int H, int W, int Cin, int Cout,
                              int KH, int KW, int stride, int pad, int OH, int OW, hipStream_t s);
-int wsmg_conv_win_wgrad_splits(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH, int OW);
 // wsmg_conv_s2_wgrad.hip: weight gradient of the k5 s2 (64 -> 128 at 50 x 50) and k7 s2 (256 -> 64 at 24 x 24) layers out of an
-// LDS-resident input window; WSMG_EINVAL / 0 splits for any other shape
+// LDS-resident input window (its test: s2w_shape)
+int wsmg_conv_s2_wgrad_splits(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH, int OW);
 int wsmg_conv_s2_wgrad_bf16(const void* x, const void* dy, float* dw_ohwi, long long slab_floats, int B, int H, int W, int Cin, int Cout,
                             int KH, int KW, int stride, int pad, int OH, int OW, hipStream_t s);
-int wsmg_conv_s2_wgrad_splits(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH, int OW);
-// wsmg_conv_win3.hip: 3 x 3 / stride 1 / pad 1 out of a zero-padded LDS pixel window (forward / backward-data), N % 128 == 0,
-// Kc % 32 == 0, mt = 512 or 256 pixels per workgroup, mixed != 0: the last partial round as half-size tiles; WSMG_EINVAL otherwise
+// wsmg_conv_win3.hip: 3 x 3 / stride 1 / pad 1 out of a zero-padded LDS pixel window (forward / backward-data), N % 32 == 0,
+// Kc % 32 == 0, mt = 512 or 256 pixels per workgroup, mixed != 0: the last partial round as half-size tiles where that pays
 // (round 6) relu_z [pixels][N] or null: ReLU outputs the output tile is masked with (wsmg_relu_mask.h); dst_ld: pixel pitch of dst in
 // elements (0 = N); dst2 / split_c: output channels >= split_c go to the second tensor (null: none)
+bool wsmg_conv_win3_fits(int mt, int B, int H, int W, int Kc, int N);
 int wsmg_conv_win3_bf16(int bwd, const void* src, const void* wt, const float* bias, void* dst, int relu, double* stats, int nslab,
                         int B, int H, int W, int Kc, int N, int mt, int mixed, const void* relu_z, int dst_ld, void* dst2, int split_c,
                         hipStream_t s);
 // wsmg_conv_win3_k32.hip (round 6): the same convolution over a 32-channel reduction axis (Kc == 32, N % 32 == 0, plain output): weights
-// resident in LDS, one barrier per 256-pixel tile, three workgroups per CU; WSMG_EINVAL otherwise
+// resident in LDS, one barrier per 256-pixel tile, three workgroups per CU; wgs: workgroups per CU of the grid
+int64_t wsmg_conv_win3_k32_grid(int B, int H, int W, int N, int wgs);
 int wsmg_conv_win3_k32_bf16(int bwd, const void* src, const void* wt, const float* bias, void* dst, int relu, double* stats, int nslab,
-                            int B, int H, int W, int N, int dst_ld, hipStream_t s);
+                            int B, int H, int W, int N, int dst_ld, int wgs, hipStream_t s);
 // wsmg_convt_k4s2.hip (round 6): ConvTranspose2d(64 -> 32, k4, s2, p1) forward — both column parities of a row parity per workgroup,
-// weights resident in LDS, full-line stores; WSMG_EINVAL when the window does not fit
-int wsmg_convt_k4s2_bf16(const void* src, const void* w_ihwo, void* dst, double* stats, int nslab, int B, int H, int W, hipStream_t s);
+// weights resident in LDS, full-line stores.  The test takes the adjoint convolution's geometry (its backward-data pass), the entry
+// point the ConvTranspose's input grid H x W
+int64_t wsmg_convt_k4s2_grid(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH, int OW, int wgs);
+int wsmg_convt_k4s2_bf16(const void* src, const void* w_ihwo, void* dst, double* stats, int nslab, int B, int H, int W, int wgs,
+                         hipStream_t s);
 // wsmg_conv_win3_wgrad.hip: weight gradient of a 3 x 3 / stride 1 / pad 1 layer out of a zero-padded LDS window (W <= 24, channel
-// multiples of 64 / 128); WSMG_EINVAL otherwise
+// multiples of 64 / 128; its test: w3w_variant)
+int wsmg_conv_win3_wgrad_splits(int B, int H, int W, int Cin, int Cout);
 int wsmg_conv_win3_wgrad_bf16(const void* x, const void* dy, float* dw_ohwi, long long slab_floats, int B, int H, int W, int Cin, int Cout,
                               hipStream_t s);
-int wsmg_conv_win3_wgrad_splits(int B, int H, int W, int Cin, int Cout);
 // wsmg_rnn.hip: device pointer of the process-wide persistent-kernel status word (host-mapped; bits 1 gru_fwd, 2 gru_bwd, 4 lstm_fwd,
 // 8 lstm_bwd), for kernels of other files that wait on a chain counter (wsmg_rows_gemm.hip)
 unsigned* wsmgi_rnn_status_dev();

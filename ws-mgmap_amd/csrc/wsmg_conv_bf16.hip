@@ -558,58 +558,9 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_kernel(WgradArgsB a) {
   }
 }
 
-int check_conv_bf16(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH, int OW) {
-  if (int e = wsmg_check_conv(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
-  // 32-bit byte offsets into the buffer resources
-  if ((int64_t)B * H * W * Cin * 2 >= (1ll << 31) || (int64_t)B * OH * OW * Cout * 2 >= (1ll << 31)) return WSMG_EINVAL;
-  return 0;
-}
-
 // register prefetch depth (k-steps in flight) is PF = 1 everywhere.  Measured on MI355X (tools/bench_conv.py): the igemm
 // kernels are fastest at 1 (deeper costs occupancy, which hides more latency than the prefetch does); the PF = 2 / 3
 // instantiations no dispatcher could select are gone.
-
-int g_win3_tile = -1;
-int win3_tile() {   // WSMG_CONV_WIN3: 0 = off, 1 = by shape (default), 512 / 256 = that many pixels per workgroup
-  if (g_win3_tile < 0) g_win3_tile = WSMG_TUNE("WSMG_CONV_WIN3", 1);
-  return g_win3_tile;
-}
-// The LDS-window kernel (wsmg_conv_win3.hip) for a 3 x 3 / stride 1 / pad 1 layer of M pixels, Kc reduction channels and N output
-// channels: 0 = no (implicit-GEMM kernel), else pixels per workgroup.  Measured at B = 512 (tools/ab_win3.sh): at Kc = 32 (9
-// k-steps) its prologue costs more than the window saves; 512-pixel tiles move half the weight bytes per MFMA of 256-pixel
-// ones but need >= 4 rounds of workgroups over the 256 CUs to keep the last round's idle CUs cheap (N = 128 layers: 256).
-// round 6: a 32-channel reduction axis takes wsmg_conv_win3_k32.hip (by-shape choice only: a forced tile keeps the general window kernel,
-// which is how the tests hold the two against each other; WSMG_CONV_K32=0: A/B)
-bool k32_choice(int64_t M, int Kc, int N) {
-  // (N = 128, the classifier's 32 -> 128 projection: 41 us on either kernel alone, 48.7 against 55.6 us in the update — rocprofv3 --stats)
-  return win3_tile() == 1 && Kc == 32 && (N == 32 || N == 64 || N == 128) && M >= 2 * 256 * 256 && WSMG_TUNE("WSMG_CONV_K32", 1) != 0;
-}
-int win3_choice(int64_t M, int Kc, int N) {
-  const int t = win3_tile();
-  if (t == 0 || M < 256 * 256 || Kc % 32 || N % 32) return 0;
-  if (N % 64) {                      // 32-channel tiles (round 3; WSMG_CONV_WIN3_N32=0: implicit-GEMM kernel, 512 / 256: the tile).
-    // The classifier's 32 -> 32 layer at 48 x 48 (B = 512), alone: forward 0.071 -> 0.063 (512-pixel tiles) -> 0.055 ms (256),
-    // backward-data 0.075 -> 0.063 -> 0.056: the implicit-GEMM kernel pads the 32 channels to a 64-wide tile and re-fetches the
-    // pixels per tap; nine k-steps are too few to hide the window's load, so this is 390 TFLOP/s, not 800
-    const int n32 = WSMG_TUNE("WSMG_CONV_WIN3_N32", 256);
-    if (t != 1) return t;
-    if (n32 == 0 || M < 2 * 256 * 256) return 0;
-    return n32;
-  }
-  if (Kc < 64) return 0;
-  if (N % 128) {                     // 64-channel tiles (round 3; WSMG_CONV_WIN3_N64=0: the implicit-GEMM kernel, 512 / 256: the tile)
-    const int n64 = WSMG_TUNE("WSMG_CONV_WIN3_N64", 1);
-    if (t != 1) return t;           // (forced by wsmg_conv_debug_win3_tile / WSMG_CONV_WIN3)
-    // measured alone at B = 512, 24 x 24 (tools/bench_conv.py): orig0 (256 -> 64) forward 0.118 -> 0.103 ms, orig2 (192 -> 64)
-    // forward 0.091 -> 0.083 and backward-data (64 -> 192) 0.106 -> 0.090; orig1 (64 -> 64: 18 k-steps, one 64-channel tile)
-    // 0.037 -> 0.043: that one stays on the implicit-GEMM kernel
-    if (n64 == 0 || M < 2 * 256 * 256 || (Kc < 128 && N < 192)) return 0;
-    return n64 == 1 ? 512 : n64;
-  }
-  if (t != 1) return t;
-  if (M < 2 * 256 * 256) return 0;   // 12 x 12 maps at B = 512 (73 728 pixels, 128 -> 128): 0.035 vs 0.033 ms
-  return ((M + 511) / 512) * (N / 128) >= 1024 ? 512 : 256;
-}
 
 template <bool BWD>
 int launch_igemm(ConvArgsB& a, int64_t mrows, int classes, hipStream_t s) {
@@ -627,7 +578,7 @@ int launch_igemm(ConvArgsB& a, int64_t mrows, int classes, hipStream_t s) {
     hipLaunchKernelGGL((conv_igemm_bf16_kernel<BWD, 128, 32, 1>), grid, dim3(256), 0, s, a);
   else
     hipLaunchKernelGGL((conv_igemm_bf16_kernel<BWD, 64, 32, 1>), grid, dim3(256), 0, s, a);
-  return 0;
+  WSMG_RETURN_LAUNCH();
 }
 
 // split-K plan of a forward layer: 1 = none.  Only layers that leave most of the chip idle (fewer than 128 tiles of 128 pixels
@@ -717,7 +668,7 @@ extern "C" int wsmg_conv2d_splitk_plan(int B, int OH, int OW, int Cin, int Cout,
 extern "C" int wsmg_conv2d_fwd_bf16_splitk(const void* x, const void* w_ohwi, const float* bias, void* y, int flags, int ksplit,
                                            float* part, int B, int H, int W, int Cin, int Cout, int KH, int KW,
                                            int stride, int pad, int OH, int OW, wsmg_stream_t stream) {
-  if (int e = check_conv_bf16(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
+  if (int e = wsmg_check_conv_bf16(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
   const int64_t M = (int64_t)B * OH * OW;
   if (ksplit < 2 || ksplit != splitk_plan(M, Cin, Cout, KH, KW) || !part || (flags & ~7)) return WSMG_EINVAL;
   ConvArgsB a{(const bf16_t*)x, (const bf16_t*)w_ohwi, nullptr, y, B, H, W, Cin, OH, OW, Cout, KH, KW, stride, pad, 0, 0, flags,
@@ -739,7 +690,7 @@ namespace {
 // y_ld (0 = Cout): pixel pitch of y in elements — y may be a channel slice of a wider tensor
 int conv_fwd_bf16_impl(const void* x, const void* w_ohwi, const float* bias, void* y, int out_f32, double* stats, int nslab, int y_ld, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
                        int OH, int OW, wsmg_stream_t stream) {
-  if (int e = check_conv_bf16(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
+  if (int e = wsmg_check_conv_bf16(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
   if (stats && (nslab <= 0 || (out_f32 & 5) != 0 || (Cout & 7) != 0)) return WSMG_EINVAL;   // statistics: bf16 output, no accumulate
   const bool ex = y_ld && y_ld != Cout;
   if (ex) {
@@ -747,29 +698,24 @@ int conv_fwd_bf16_impl(const void* x, const void* w_ohwi, const float* bias, voi
     if (y_ld && (y_ld < Cout || (y_ld & 7) || ((uintptr_t)y & 15))) return WSMG_EINVAL;
     if ((int64_t)B * OH * OW * (y_ld ? y_ld : Cout) * 2 >= (1ll << 31)) return WSMG_EINVAL;
   }
-  if (!ex && Cin == 64 && Cout == 64 && KH == 8 && KW == 8 && stride == 2 && pad == 3 && (out_f32 & 5) == 0) {
-    // the map encoder's stem: direct convolution out of an LDS-resident input window (wsmg_conv_win.hip); WSMG_CONV_WIN=0
-    // keeps the implicit-GEMM kernel (A/B)
-    if (WSMG_TUNE("WSMG_CONV_WIN", 1)) {
-      int rc = wsmg_conv_win_fwd_bf16(x, w_ohwi, bias, y, (out_f32 & 2) != 0, stats, nslab, B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW, wsmg_s(stream));
-      if (rc != WSMG_EINVAL) return rc;
+  const int needs = ((out_f32 & 5) ? WSMG_NEED_F32 : 0) | (ex ? WSMG_NEED_SLICE : 0) | (stats ? WSMG_NEED_STATS : 0);
+  const WsmgConvRoute r = wsmg_conv_route(WSMG_CONV_FWD, B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW, needs);
+  const int relu = (out_f32 & 2) != 0;
+  switch (r.kind) {
+    case WSMG_ROUTE_STEM_WIN:
+      return wsmg_conv_win_fwd_bf16(x, w_ohwi, bias, y, relu, stats, nslab, B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW, wsmg_s(stream));
+    case WSMG_ROUTE_WIN3_K32:
+      return wsmg_conv_win3_k32_bf16(0, x, w_ohwi, bias, y, relu, stats, nslab, B, H, W, Cout, y_ld, r.wgs, wsmg_s(stream));
+    case WSMG_ROUTE_WIN3:
+      return wsmg_conv_win3_bf16(0, x, w_ohwi, bias, y, relu, stats, nslab, B, H, W, Cin, Cout, r.mt, r.mixed, nullptr, y_ld, nullptr, 0, wsmg_s(stream));
+    case WSMG_ROUTE_IGEMM: {
+      ConvArgsB a{(const bf16_t*)x, (const bf16_t*)w_ohwi, bias, y, B, H, W, Cin, OH, OW, Cout, KH, KW, stride, pad, 0, 0, out_f32,
+                  (unsigned)((size_t)B * H * W * Cin * 2), (unsigned)((size_t)Cout * KH * KW * Cin * 2), stats, nslab};
+      a.dst_ld = y_ld;
+      return launch_igemm<false>(a, (int64_t)B * OH * OW, 1, wsmg_s(stream));
     }
   }
-  if (KH == 3 && KW == 3 && stride == 1 && pad == 1 && OH == H && OW == W && (out_f32 & 5) == 0) {
-    if (k32_choice((int64_t)B * OH * OW, Cin, Cout)) {
-      int rc = wsmg_conv_win3_k32_bf16(0, x, w_ohwi, bias, y, (out_f32 & 2) != 0, stats, nslab, B, H, W, Cout, y_ld, wsmg_s(stream));
-      if (rc != WSMG_EINVAL) return rc;
-    }
-    if (const int mt = win3_choice((int64_t)B * OH * OW, Cin, Cout)) {
-      int rc = wsmg_conv_win3_bf16(0, x, w_ohwi, bias, y, (out_f32 & 2) != 0, stats, nslab, B, H, W, Cin, Cout, mt, win3_tile() == 1, nullptr, y_ld, nullptr, 0, wsmg_s(stream));
-      if (rc != WSMG_EINVAL) return rc;
-    }
-  }
-  ConvArgsB a{(const bf16_t*)x, (const bf16_t*)w_ohwi, bias, y, B, H, W, Cin, OH, OW, Cout, KH, KW, stride, pad, 0, 0, out_f32,
-              (unsigned)((size_t)B * H * W * Cin * 2), (unsigned)((size_t)Cout * KH * KW * Cin * 2), stats, nslab};
-  a.dst_ld = y_ld;
-  if (int e = launch_igemm<false>(a, (int64_t)B * OH * OW, 1, wsmg_s(stream))) return e;
-  WSMG_RETURN_LAUNCH();
+  return WSMG_EINVAL;   // (a forward route names no other family)
 }
 }  // namespace
 
@@ -785,13 +731,6 @@ extern "C" int wsmg_conv2d_fwd_bf16_ex(const void* x, const void* w_ohwi, const 
   return conv_fwd_bf16_impl(x, w_ohwi, bias, y, flags, stats, nslab, y_ld, B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW, stream);
 }
 
-// tests / tools: choose the window kernel's tile (0 = off, 1 = by shape, 256, 512) for the calls that follow; returns the previous choice
-extern "C" int wsmg_conv_debug_win3_tile(int mt) {
-  const int old = win3_tile();
-  if (mt == 0 || mt == 1 || mt == 256 || mt == 512) g_win3_tile = mt;
-  return old;
-}
-
 extern "C" int wsmg_conv2d_fwd_bf16(const void* x, const void* w_ohwi, const float* bias, void* y, int out_f32, int B,
                                     int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH,
                                     int OW, wsmg_stream_t stream) {
@@ -799,43 +738,38 @@ extern "C" int wsmg_conv2d_fwd_bf16(const void* x, const void* w_ohwi, const flo
 }
 
 namespace {
+// backward-data over dx [B][H][W]: stride 2 runs the four parity classes of dx as blockIdx.y, each over the rows of the largest
+int launch_igemm_bwd(ConvArgsB& a, int B, int H, int W, int stride, hipStream_t s) {
+  if (stride == 2) return launch_igemm<true>(a, (int64_t)B * ((H + 1) / 2) * ((W + 1) / 2), 4, s);
+  return launch_igemm<true>(a, (int64_t)B * H * W, 1, s);
+}
+
 int conv_bwd_data_bf16_impl(const void* dy, const void* w_ihwo, void* dx, int out_f32, double* stats, int nslab, const void* relu_y,
                             void* dx2, int split_c, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH,
                             int OW, wsmg_stream_t stream) {
-  if (int e = check_conv_bf16(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
+  if (int e = wsmg_check_conv_bf16(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
   if (stats && (nslab <= 0 || (out_f32 & 5) != 0 || (Cin & 7) != 0)) return WSMG_EINVAL;
   if (relu_y && ((out_f32 & 5) != 0 || (Cin & 7) != 0 || ((uintptr_t)relu_y & 15))) return WSMG_EINVAL;
   if (dx2 && ((out_f32 & 5) != 0 || (Cin & 7) != 0 || split_c <= 0 || split_c >= Cin || (split_c & 7) || ((uintptr_t)dx2 & 15))) return WSMG_EINVAL;
-  if (KH == 3 && KW == 3 && stride == 1 && pad == 1 && OH == H && OW == W && (out_f32 & 7) == 0) {
-    if (!relu_y && !dx2 && k32_choice((int64_t)B * H * W, Cout, Cin)) {
-      int rc = wsmg_conv_win3_k32_bf16(1, dy, w_ihwo, nullptr, dx, 0, stats, nslab, B, H, W, Cin, 0, wsmg_s(stream));
-      if (rc != WSMG_EINVAL) return rc;
+  const int needs = ((out_f32 & 7) ? WSMG_NEED_F32 : 0) | (relu_y ? WSMG_NEED_RELU_Y : 0) | (dx2 ? WSMG_NEED_SPLIT : 0) | (stats ? WSMG_NEED_STATS : 0);
+  const WsmgConvRoute r = wsmg_conv_route(WSMG_CONV_BWD_DATA, B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW, needs);
+  switch (r.kind) {
+    case WSMG_ROUTE_WIN3_K32:
+      return wsmg_conv_win3_k32_bf16(1, dy, w_ihwo, nullptr, dx, 0, stats, nslab, B, H, W, Cin, 0, r.wgs, wsmg_s(stream));
+    case WSMG_ROUTE_WIN3:
+      return wsmg_conv_win3_bf16(1, dy, w_ihwo, nullptr, dx, 0, stats, nslab, B, H, W, Cout, Cin, r.mt, r.mixed, relu_y, 0, dx2, split_c, wsmg_s(stream));
+    case WSMG_ROUTE_CONVT_K4S2:
+      return wsmg_convt_k4s2_bf16(dy, w_ihwo, dx, stats, nslab, B, OH, OW, r.wgs, wsmg_s(stream));
+    case WSMG_ROUTE_IGEMM: {
+      ConvArgsB a{(const bf16_t*)dy, (const bf16_t*)w_ihwo, nullptr, dx, B, OH, OW, Cout, H, W, Cin, KH, KW, stride, pad, 0, 0, out_f32,
+                  (unsigned)((size_t)B * OH * OW * Cout * 2), (unsigned)((size_t)Cout * KH * KW * Cin * 2), stats, nslab};
+      a.relu_z = (const bf16_t*)relu_y;
+      a.dst2 = dx2;
+      a.split_c = split_c;
+      return launch_igemm_bwd(a, B, H, W, stride, wsmg_s(stream));
     }
-    if (const int mt = win3_choice((int64_t)B * H * W, Cout, Cin)) {
-      int rc = wsmg_conv_win3_bf16(1, dy, w_ihwo, nullptr, dx, 0, stats, nslab, B, H, W, Cout, Cin, mt, win3_tile() == 1, relu_y, 0, dx2, split_c, wsmg_s(stream));
-      if (rc != WSMG_EINVAL) return rc;
-    }
   }
-  // the classifier's ConvTranspose2d(64 -> 32, k4, s2, p1) forward: wsmg_convt_k4s2.hip (by-shape choice only, like the k32 kernel;
-  // WSMG_CONVT_K4S2=0: A/B)
-  if (KH == 4 && KW == 4 && stride == 2 && pad == 1 && Cin == 32 && Cout == 64 && H == 2 * OH && W == 2 * OW && (out_f32 & 7) == 0 &&
-      !relu_y && !dx2 && win3_tile() == 1 && (int64_t)B * OH * OW >= 2 * 256 * 256 && WSMG_TUNE("WSMG_CONVT_K4S2", 1) != 0) {
-    int rc = wsmg_convt_k4s2_bf16(dy, w_ihwo, dx, stats, nslab, B, OH, OW, wsmg_s(stream));
-    if (rc != WSMG_EINVAL) return rc;
-  }
-  ConvArgsB a{(const bf16_t*)dy, (const bf16_t*)w_ihwo, nullptr, dx, B, OH, OW, Cout, H, W, Cin, KH, KW, stride, pad, 0, 0, out_f32,
-              (unsigned)((size_t)B * OH * OW * Cout * 2), (unsigned)((size_t)Cout * KH * KW * Cin * 2), stats, nslab};
-  a.relu_z = (const bf16_t*)relu_y;
-  a.dst2 = dx2;
-  a.split_c = split_c;
-  int classes = 1;
-  int64_t mmax = (int64_t)B * H * W;
-  if (stride == 2) {
-    classes = 4;
-    mmax = (int64_t)B * ((H + 1) / 2) * ((W + 1) / 2);
-  }
-  if (int e = launch_igemm<true>(a, mmax, classes, wsmg_s(stream))) return e;
-  WSMG_RETURN_LAUNCH();
+  return WSMG_EINVAL;   // (a backward-data route names no other family)
 }
 }  // namespace
 
@@ -857,18 +791,11 @@ extern "C" int wsmg_conv2d_bwd_data_bf16_ex(const void* dy, const void* w_ihwo, 
 extern "C" int wsmg_conv_transpose2d_infer_bf16(const void* x, const void* w_ihwo, const float* bias, void* y, int flags, int B,
                                                 int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH,
                                                 int OW, wsmg_stream_t stream) {
-  if (int e = check_conv_bf16(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
+  if (int e = wsmg_check_conv_bf16(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
   if (flags & ~3) return WSMG_EINVAL;
   ConvArgsB a{(const bf16_t*)x, (const bf16_t*)w_ihwo, bias, y, B, OH, OW, Cout, H, W, Cin, KH, KW, stride, pad, 0, 0, flags,
               (unsigned)((size_t)B * OH * OW * Cout * 2), (unsigned)((size_t)Cout * KH * KW * Cin * 2), nullptr, 0};
-  int classes = 1;
-  int64_t mmax = (int64_t)B * H * W;
-  if (stride == 2) {
-    classes = 4;
-    mmax = (int64_t)B * ((H + 1) / 2) * ((W + 1) / 2);
-  }
-  launch_igemm<true>(a, mmax, classes, wsmg_s(stream));
-  WSMG_RETURN_LAUNCH();
+  return launch_igemm_bwd(a, B, H, W, stride, wsmg_s(stream));
 }
 
 extern "C" int wsmg_conv2d_bwd_data_bf16(const void* dy, const void* w_ihwo, void* dx, int out_f32, int B, int H, int W,
@@ -877,62 +804,49 @@ extern "C" int wsmg_conv2d_bwd_data_bf16(const void* dy, const void* w_ihwo, voi
   return wsmg_conv2d_bwd_data_bf16_stats(dy, w_ihwo, dx, out_f32, nullptr, 0, B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW, stream);
 }
 
-namespace {
-// Which kernel takes the weight gradient of a layer, and over how many partial sums (pixel chunks / image ranges / tile groups) its
-// reduction is split — the number of slabs of the deterministic form.
-struct WgradPlan {
-  int kind;      // 0 generic (conv_wgrad_bf16_kernel), 1 k8 stem window kernel, 2 3 x 3 window kernel, 3 k5 / k7 stride-2 window kernel
-  int nsplit;
-  int tc, tu, gx, gy;
-  int64_t chunk;
-};
-
-WgradPlan wgrad_plan_bf16(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH, int OW) {
-  WgradPlan p{0, 0, 0, 0, 0, 0, 0};
-  // the map encoder's stem: LDS-window variant (wsmg_conv_win_wgrad.hip); WSMG_WGRAD_WIN=0 keeps the generic kernel (A/B)
-  if (WSMG_TUNE("WSMG_WGRAD_WIN", 1)) {
-    if (const int n = wsmg_conv_win_wgrad_splits(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) { p.kind = 1; p.nsplit = n; return p; }
-  }
-  // the other two stride-2 layers (k5 64 -> 128, k7 256 -> 64): wsmg_conv_s2_wgrad.hip; WSMG_WGRAD_S2WIN=0 keeps the generic kernel (A/B)
-  if (const int n = wsmg_conv_s2_wgrad_splits(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) { p.kind = 3; p.nsplit = n; return p; }
-  // 3 x 3 stride-1 layers: zero-padded LDS window (wsmg_conv_win3_wgrad.hip); WSMG_WGRAD_WIN3=0 (or the tests' tile switch = 0)
-  // keeps the generic kernel (A/B)
-  const int use_w3w = WSMG_TUNE("WSMG_WGRAD_WIN3", 1);
-  if (KH == 3 && KW == 3 && stride == 1 && pad == 1 && OH == H && OW == W && use_w3w && win3_tile() && (int64_t)B * H * W >= 256 * 256) {
-    if (const int n = wsmg_conv_win3_wgrad_splits(B, H, W, Cin, Cout)) { p.kind = 2; p.nsplit = n; return p; }
-  }
+// The generic weight-gradient kernel (conv_wgrad_bf16_kernel) takes every layer: its tile shape, grid and split of the pixel reduction,
+// written into the route (wsmg_conv_route.hip asks when no window kernel takes the layer)
+void wsmg_conv_wgrad_plan(int B, int Cin, int Cout, int KH, int KW, int OH, int OW, WsmgConvRoute& r) {
   const int units = KH * KW * (Cin / 32);
   const int64_t npix = (int64_t)B * OH * OW;
   // tile shape (measured per layer, tools/bench_conv.py): 128 co x 8 units where both dimensions are
   // large (cated 765 vs 660 TFLOP/s), else 64 co x 4 units, which keeps 5 workgroups per CU resident
   // (the 64-channel k8 stem, 128 units of 64 input channels: 64 co x 8 units measured 0.94 vs 0.99 ms; every other
   // 64-wide layer is faster with 4 units)
-  int tc = (Cout % 128 == 0 && units >= 48) ? 4 : 2, tu = (tc == 4 || (Cin == 64 && units >= 128)) ? 2 : 1;
-  const int gx = (int)wsmg_cdiv(units, 4 * tu), gy = (int)wsmg_cdiv(Cout, 32 * tc);
+  r.tc = (Cout % 128 == 0 && units >= 48) ? 4 : 2;
+  r.tu = (r.tc == 4 || (Cin == 64 && units >= 128)) ? 2 : 1;
+  r.gx = (int)wsmg_cdiv(units, 4 * r.tu);
+  r.gy = (int)wsmg_cdiv(Cout, 32 * r.tc);
   // workgroups over the pixel reduction (the k8 stem's 64 x 8 tile: 0.90 ms at 2048, 0.96 at 1024).  Every workgroup ends
   // with its tile going to memory — float atomics, 40-50 % of the launch for the small layers, or (slab form) plain stores
   // that the reduce launch reads back: below 40 GFLOP fewer, longer workgroups win (768: -0.08 ms over the six small
   // layers of the update; tools sweep, WSMG_WGRAD_WANT)
   const double gflop = 2.0 * (double)npix * Cout * Cin * KH * KW * 1e-9;
-  int64_t target = tc == 4 ? 1024 : (gflop < 40.0 ? 768 : 2048);
-  int64_t want = wsmg_cdiv(target, (int64_t)gx * gy);
+  int64_t target = r.tc == 4 ? 1024 : (gflop < 40.0 ? 768 : 2048);
+  int64_t want = wsmg_cdiv(target, (int64_t)r.gx * r.gy);
   int64_t maxz = wsmg_cdiv(npix, WKP * 8);
   int64_t gz = want < 1 ? 1 : (want > maxz ? maxz : want);
   if (gz < 1) gz = 1;
   if (gz > 65535) gz = 65535;
-  p.chunk = wsmg_cdiv(wsmg_cdiv(npix, gz), WKP) * WKP;
-  p.nsplit = (int)wsmg_cdiv(npix, p.chunk);
-  p.tc = tc; p.tu = tu; p.gx = gx; p.gy = gy;
-  return p;
+  r.chunk = wsmg_cdiv(wsmg_cdiv(npix, gz), WKP) * WKP;
+  r.nsplit = (int)wsmg_cdiv(npix, r.chunk);
 }
 
-// slab_floats == 0: atomics into the zeroed OHWI dW; > 0: `dw` is the slab workspace (WgradArgsB::slab)
-int launch_wgrad_bf16(const void* x, const void* dy, float* dw, long long slab_floats, int B, int H, int W, int Cin, int Cout, int KH,
-                      int KW, int stride, int pad, int OH, int OW, hipStream_t stream) {
-  const WgradPlan p = wgrad_plan_bf16(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW);
-  if (p.kind == 1) return wsmg_conv_win_wgrad_bf16(x, dy, dw, slab_floats, B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW, stream);
-  if (p.kind == 2) return wsmg_conv_win3_wgrad_bf16(x, dy, dw, slab_floats, B, H, W, Cin, Cout, stream);
-  if (p.kind == 3) return wsmg_conv_s2_wgrad_bf16(x, dy, dw, slab_floats, B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW, stream);
+namespace {
+// slab_floats == 0: atomics into the zeroed OHWI dW; > 0: `dw` is the slab workspace (WgradArgsB::slab), ws_floats floats that the caller
+// holds to be nsplit slabs — checked against the route
+int launch_wgrad_bf16(const void* x, const void* dy, float* dw, long long slab_floats, int nsplit, long long ws_floats, int B, int H, int W,
+                      int Cin, int Cout, int KH, int KW, int stride, int pad, int OH, int OW, hipStream_t stream) {
+  if (int e = wsmg_check_conv_bf16(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
+  const WsmgConvRoute p = wsmg_conv_route(WSMG_CONV_BWD_WEIGHT, B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW, 0);
+  if (slab_floats && (!dw || nsplit != p.nsplit || ws_floats < slab_floats * p.nsplit)) return WSMG_EINVAL;
+  switch (p.kind) {
+    case WSMG_ROUTE_WGRAD_STEM_WIN: return wsmg_conv_win_wgrad_bf16(x, dy, dw, slab_floats, B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW, stream);
+    case WSMG_ROUTE_WGRAD_WIN3: return wsmg_conv_win3_wgrad_bf16(x, dy, dw, slab_floats, B, H, W, Cin, Cout, stream);
+    case WSMG_ROUTE_WGRAD_S2WIN: return wsmg_conv_s2_wgrad_bf16(x, dy, dw, slab_floats, B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW, stream);
+    case WSMG_ROUTE_WGRAD: break;         // the generic kernel, below
+    default: return WSMG_EINVAL;          // (a weight-gradient route names no other family)
+  }
   WgradArgsB a{(const bf16_t*)x, (const bf16_t*)dy, dw, B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW, 0, 0, 0,
                (unsigned)((size_t)B * H * W * Cin * 2), (unsigned)((size_t)B * OH * OW * Cout * 2), 0, 0, (int64_t)slab_floats};
   a.units = KH * KW * (Cin / 32);
@@ -967,8 +881,7 @@ int launch_wgrad_bf16(const void* x, const void* dy, float* dw, long long slab_f
 extern "C" int wsmg_conv2d_bwd_weight_bf16(const void* x, const void* dy, float* dw_ohwi, int B, int H, int W, int Cin,
                                            int Cout, int KH, int KW, int stride, int pad, int OH, int OW,
                                            wsmg_stream_t stream) {
-  if (int e = check_conv_bf16(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
-  return launch_wgrad_bf16(x, dy, dw_ohwi, 0, B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW, wsmg_s(stream));
+  return launch_wgrad_bf16(x, dy, dw_ohwi, 0, 0, 0, B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW, wsmg_s(stream));
 }
 
 // Deterministic weight gradient, step 1 of 2 (the plan): how many partial sums (`nsplit`) the layer's reduction is split into and
@@ -976,10 +889,9 @@ extern "C" int wsmg_conv2d_bwd_weight_bf16(const void* x, const void* dy, float*
 extern "C" int wsmg_conv2d_bwd_weight_bf16_plan(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH,
                                                 int OW, int* nsplit, long long* ws_floats) {
   if (!nsplit || !ws_floats) return WSMG_EINVAL;
-  if (int e = check_conv_bf16(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
-  const WgradPlan p = wgrad_plan_bf16(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW);
-  *nsplit = p.nsplit;
-  *ws_floats = (long long)p.nsplit * Cout * KH * KW * Cin;
+  if (int e = wsmg_check_conv_bf16(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
+  *nsplit = wsmg_conv_route(WSMG_CONV_BWD_WEIGHT, B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW, 0).nsplit;
+  *ws_floats = (long long)*nsplit * Cout * KH * KW * Cin;
   return 0;
 }
 
@@ -990,9 +902,6 @@ extern "C" int wsmg_conv2d_bwd_weight_bf16_plan(int B, int H, int W, int Cin, in
 extern "C" int wsmg_conv2d_bwd_weight_bf16_slabs(const void* x, const void* dy, float* ws, int nsplit, long long ws_floats, int B, int H,
                                                  int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH, int OW,
                                                  wsmg_stream_t stream) {
-  if (int e = check_conv_bf16(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
-  const WgradPlan p = wgrad_plan_bf16(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW);
-  const long long slab = (long long)Cout * KH * KW * Cin;
-  if (!ws || nsplit != p.nsplit || ws_floats < slab * p.nsplit) return WSMG_EINVAL;
-  return launch_wgrad_bf16(x, dy, ws, slab, B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW, wsmg_s(stream));
+  return launch_wgrad_bf16(x, dy, ws, (long long)Cout * KH * KW * Cin, nsplit, ws_floats, B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW,
+                           wsmg_s(stream));
 }

@@ -204,7 +204,6 @@ constexpr S2wShape kEnc3{5, 1, 50, 64, 128, 8, 48}, kStem{7, 3, 24, 256, 64, 12,
 const S2wShape* s2w_shape(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH, int OW) {
   if (stride != 2 || KH != KW || H != W || OH != OW) return nullptr;
   if ((size_t)B * H * W * Cin * 2 >= (1ull << 31) || (size_t)B * OH * OW * Cout * 2 >= (1ull << 31)) return nullptr;
-  if (!WSMG_TUNE("WSMG_WGRAD_S2WIN", 1)) return nullptr;
   for (const S2wShape* s : {&kEnc3, &kStem})
     if (KH == s->K && pad == s->P && H == s->H && Cin == s->Cin && Cout == s->Cout && OH == (H + 2 * pad - KH) / 2 + 1) return s;
   return nullptr;
@@ -243,7 +242,7 @@ int wsmg_conv_s2_wgrad_splits(int B, int H, int W, int Cin, int Cout, int KH, in
 }
 
 // dW (OHWI float32) of the two layers named at the top on bf16 NHWC — slab_floats == 0: accumulated into with float atomics (the
-// caller zeroes it); > 0: one slab per tile group, stored; WSMG_EINVAL for any other shape (the caller then uses the generic kernel).
+// caller zeroes it); > 0: one slab per tile group, stored; WSMG_EINVAL for any other shape (the route of wsmg_conv_bf16.hip sends none here).
 int wsmg_conv_s2_wgrad_bf16(const void* x, const void* dy, float* dw_ohwi, long long slab_floats, int B, int H, int W, int Cin, int Cout,
                             int KH, int KW, int stride, int pad, int OH, int OW, hipStream_t s) {
   const S2wShape* sh = s2w_shape(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW);

@@ -75,12 +75,18 @@ inline int wsmg_cu_count() {
   return cus;
 }
 
-// geometry every convolution entry point checks (the bf16 engine adds its 32-bit byte-offset limits: check_conv_bf16)
+// geometry every convolution entry point checks (the bf16 engine adds its 32-bit byte-offset limits: wsmg_check_conv_bf16)
 inline int wsmg_check_conv(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH, int OW) {
   if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || KH <= 0 || KW <= 0) return WSMG_EINVAL;
   if (Cin % 32 || Cout % 32) return WSMG_EINVAL;
   if (stride != 1 && stride != 2) return WSMG_EINVAL;
   if (OH != (H + 2 * pad - KH) / stride + 1 || OW != (W + 2 * pad - KW) / stride + 1) return WSMG_EINVAL;
   if ((int64_t)B * H * W >= (1ll << 31) || (int64_t)B * OH * OW >= (1ll << 31)) return WSMG_EINVAL;
+  return 0;
+}
+inline int wsmg_check_conv_bf16(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH, int OW) {
+  if (int e = wsmg_check_conv(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return e;
+  // 32-bit byte offsets into the buffer resources
+  if ((int64_t)B * H * W * Cin * 2 >= (1ll << 31) || (int64_t)B * OH * OW * Cout * 2 >= (1ll << 31)) return WSMG_EINVAL;
   return 0;
 }

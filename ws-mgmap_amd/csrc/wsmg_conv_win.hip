@@ -231,12 +231,17 @@ __global__ __launch_bounds__(256) void conv_win_fwd_kernel(WinArgs a) {
 
 }  // namespace
 
-// Forward of a 64 -> 64 channel k8 s2 p3 convolution on bf16 NHWC; returns WSMG_EINVAL for any other shape (the
-// caller then uses the implicit-GEMM kernel).  relu: fused ReLU after the bias.
+// the layers this kernel takes: 64 -> 64 channels, k8 s2 p3, 32-bit byte offsets into x
+bool wsmg_conv_win_fits(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
+  if (Cin != 64 || Cout != 64 || KH != 8 || KW != 8 || stride != 2 || pad != 3) return false;
+  return (size_t)B * H * W * 128 < (1ull << 31);
+}
+
+// Forward of a 64 -> 64 channel k8 s2 p3 convolution on bf16 NHWC; returns WSMG_EINVAL for any other shape (the route of
+// wsmg_conv_bf16.hip sends no other here).  relu: fused ReLU after the bias.
 int wsmg_conv_win_fwd_bf16(const void* x, const void* w_ohwi, const float* bias, void* y, int relu, double* stats, int nslab, int B,
                            int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH, int OW, hipStream_t s) {
-  if (Cin != 64 || Cout != 64 || KH != 8 || KW != 8 || stride != 2 || pad != 3) return WSMG_EINVAL;
-  if ((size_t)B * H * W * 128 >= (1ull << 31)) return WSMG_EINVAL;
+  if (!wsmg_conv_win_fits(B, H, W, Cin, Cout, KH, KW, stride, pad)) return WSMG_EINVAL;
   constexpr int TH = 5, TW = 25;
   WinArgs a{(const bf16_t*)x, (const bf16_t*)w_ohwi, bias, (bf16_t*)y, B, H, W, OH, OW, (OH + TH - 1) / TH, (OW + TW - 1) / TW, relu,
             (unsigned)((size_t)B * H * W * 128), (unsigned)(64u * 8 * 8 * 64 * 2), stats, nslab};

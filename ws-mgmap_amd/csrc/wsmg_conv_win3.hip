@@ -410,41 +410,42 @@ int launch_win3_mixed(Win3Args& a, hipStream_t s) {
 
 }  // namespace
 
-// 3 x 3 / stride 1 / pad 1, bf16 in / bf16 out, N % 64 == 0 (128-channel tiles when N % 128 == 0), Kc % 32 == 0; WSMG_EINVAL otherwise (the caller then uses the
-// implicit-GEMM kernel).  bwd = 0: forward (src = x, wt = OHWI); 1: backward-data (src = dy, wt = IHWO).
+// The layers a tile of mt pixels takes: N and Kc multiples of 32, mt = 512 (6 window pieces per wave) or 256 (4) with the tile's window
+// inside those 128 NPW entries, 32-bit window positions and byte offsets
+bool wsmg_conv_win3_fits(int mt, int B, int H, int W, int Kc, int N) {
+  if (N <= 0 || N % 32 || Kc % DK || B <= 0) return false;
+  if ((int64_t)B * (H + 2) * (W + 2) * 1 > (1 << 30) || (int64_t)B * H * W * (Kc > N ? Kc : N) * 2 >= (1ll << 31)) return false;
+  return (mt == 512 && wsmg_win3_window_bound(512, H, W) <= 128 * 6) || (mt == 256 && wsmg_win3_window_bound(256, H, W) <= 128 * 4);
+}
+
+// 3 x 3 / stride 1 / pad 1, bf16 in / bf16 out, 128-channel tiles when N % 128 == 0, 64-channel tiles when N % 64 == 0, else 32; WSMG_EINVAL
+// for what wsmg_conv_win3_fits refuses.  bwd = 0: forward (src = x, wt = OHWI); 1: backward-data (src = dy, wt = IHWO).
 int wsmg_conv_win3_bf16(int bwd, const void* src, const void* wt, const float* bias, void* dst, int relu, double* stats, int nslab,
                         int B, int H, int W, int Kc, int N, int mt, int mixed, const void* relu_z, int dst_ld, void* dst2, int split_c,
                         hipStream_t s) {
-  if (N <= 0 || N % 32 || Kc % DK || B <= 0) return WSMG_EINVAL;
+  if (!wsmg_conv_win3_fits(mt, B, H, W, Kc, N)) return WSMG_EINVAL;
   if (dst2 && (dst_ld || split_c <= 0 || split_c >= N || (split_c & 7) || ((uintptr_t)dst2 & 15))) return WSMG_EINVAL;
-  if ((int64_t)B * (H + 2) * (W + 2) * 1 > (1 << 30) || (int64_t)B * H * W * (Kc > N ? Kc : N) * 2 >= (1ll << 31)) return WSMG_EINVAL;
   if ((dst_ld && (dst_ld < N || (dst_ld & 7))) || ((uintptr_t)relu_z & 15)) return WSMG_EINVAL;
   Win3Args a{(const bf16_t*)src, (const bf16_t*)wt, bias, (bf16_t*)dst, B, H, W, Kc, N, 0, 0, relu, bwd,
              (unsigned)((size_t)B * H * W * Kc * 2), (unsigned)((size_t)N * 9 * Kc * 2), stats, nslab, 0, 0, 0, dst_ld, (const bf16_t*)relu_z, (bf16_t*)dst2, split_c};
   const int64_t M = (int64_t)B * H * W;
-  // mixed == 0 (a tile size forced through wsmg_conv_debug_win3_tile) or WSMG_CONV_WIN3_MIXED=0: one tile size per launch (rounds 2-4; A/B)
-  const bool mix = mixed && WSMG_TUNE("WSMG_CONV_WIN3_MIXED", 1) != 0;
+  // mixed == 0 (the route: a tile size forced through wsmg_conv_debug_win3_tile, or WSMG_CONV_WIN3_MIXED=0): one tile size per launch
+  // (rounds 2-4; A/B).  mt is 512 or 256 and its window fits from here on; the half-size remainder tiles need theirs to fit too.
   if (N % 128 == 0) {
-    if (mt == 512 && wsmg_win3_window_bound(512, H, W) <= 128 * 6) {
-      if (mix && wsmg_win3_window_bound(256, H, W) <= 128 * 4 && mixed_plan(a, M, 512, 128)) return launch_win3_mixed<512, 6, 4, 128>(a, s);
+    if (mt == 512) {
+      if (mixed && wsmg_win3_window_bound(256, H, W) <= 128 * 4 && mixed_plan(a, M, 512, 128)) return launch_win3_mixed<512, 6, 4, 128>(a, s);
       return launch_win3<512, 6, 128>(a, s);
     }
-    if (mt == 256 && wsmg_win3_window_bound(256, H, W) <= 128 * 4) {
-      if (mix && wsmg_win3_window_bound(128, H, W) <= 128 * 2 && mixed_plan(a, M, 256, 128)) return launch_win3_mixed<256, 4, 2, 128>(a, s);
-      return launch_win3<256, 4, 128>(a, s);
-    }
-    return WSMG_EINVAL;
+    if (mixed && wsmg_win3_window_bound(128, H, W) <= 128 * 2 && mixed_plan(a, M, 256, 128)) return launch_win3_mixed<256, 4, 2, 128>(a, s);
+    return launch_win3<256, 4, 128>(a, s);
   }
   if (N % 64 == 0) {   // 64-channel tiles (N = 64, 192, ...)
-    if (mt == 512 && wsmg_win3_window_bound(512, H, W) <= 128 * 6) {
-      if (mix && wsmg_win3_window_bound(256, H, W) <= 128 * 4 && mixed_plan(a, M, 512, 64)) return launch_win3_mixed<512, 6, 4, 64>(a, s);
+    if (mt == 512) {
+      if (mixed && wsmg_win3_window_bound(256, H, W) <= 128 * 4 && mixed_plan(a, M, 512, 64)) return launch_win3_mixed<512, 6, 4, 64>(a, s);
       return launch_win3<512, 6, 64>(a, s);
     }
-    if (mt == 256 && wsmg_win3_window_bound(256, H, W) <= 128 * 4) return launch_win3<256, 4, 64>(a, s);
-    return WSMG_EINVAL;
+    return launch_win3<256, 4, 64>(a, s);
   }
   // 32-channel tiles (N = 32, 96, ...)
-  if (mt == 512 && wsmg_win3_window_bound(512, H, W) <= 128 * 6) return launch_win3<512, 6, 32>(a, s);
-  if (mt == 256 && wsmg_win3_window_bound(256, H, W) <= 128 * 4) return launch_win3<256, 4, 32>(a, s);
-  return WSMG_EINVAL;
+  return mt == 512 ? launch_win3<512, 6, 32>(a, s) : launch_win3<256, 4, 32>(a, s);
 }

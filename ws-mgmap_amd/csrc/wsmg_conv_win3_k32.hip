@@ -176,26 +176,32 @@ __global__ __launch_bounds__(256) void conv_win3_k32_kernel(K32Args a) {
 
 }  // namespace
 
-// Kc == 32, N % 32 == 0, plain output (no mask, no split); WSMG_EINVAL otherwise (the caller then uses the general window kernel)
+// Workgroups of the launch for a layer of N output channels with wgs workgroups per CU (WSMG_CONV_K32_WGS); 0: the layer is not
+// this kernel's (N no multiple of 32, a 256-pixel tile's window beyond the 512 entries, no whole set of channel tiles in the grid)
+int64_t wsmg_conv_win3_k32_grid(int B, int H, int W, int N, int wgs) {
+  if (N <= 0 || N % 32 || B <= 0 || wsmg_win3_window_bound(MT, H, W) > WCAP) return 0;
+  const int ntiles = N / 32;
+  const int64_t tiles = wsmg_cdiv((int64_t)B * H * W, MT) * ntiles;
+  int64_t grid = (int64_t)wgs * wsmg_cu_count();
+  if (grid > tiles) grid = tiles;
+  grid = grid / ntiles * ntiles;            // a workgroup's channel tile is blockIdx % ntiles for every tile it walks
+  return grid > 0 ? grid : 0;
+}
+
+// Kc == 32, N % 32 == 0, plain output (no mask, no split); WSMG_EINVAL where wsmg_conv_win3_k32_grid answers 0
 int wsmg_conv_win3_k32_bf16(int bwd, const void* src, const void* wt, const float* bias, void* dst, int relu, double* stats, int nslab,
-                            int B, int H, int W, int N, int dst_ld, hipStream_t s) {
-  if (N <= 0 || N % 32 || B <= 0 || wsmg_win3_window_bound(MT, H, W) > WCAP) return WSMG_EINVAL;
-  if (stats && nslab <= 0) return WSMG_EINVAL;
+                            int B, int H, int W, int N, int dst_ld, int wgs, hipStream_t s) {
+  const int64_t grid = wsmg_conv_win3_k32_grid(B, H, W, N, wgs);
+  if (grid == 0 || (stats && nslab <= 0)) return WSMG_EINVAL;
   K32Args a{(const bf16_t*)src, (const bf16_t*)wt, bias, (bf16_t*)dst, B, H, W, N, N / 32, 0, relu, bwd, dst_ld,
             (unsigned)((size_t)B * H * W * 32 * 2), (unsigned)((size_t)N * 9 * 32 * 2), stats, nslab};
-  const int64_t M = (int64_t)B * H * W;
-  a.mtiles = (int)wsmg_cdiv(M, MT);
+  a.mtiles = (int)wsmg_cdiv((int64_t)B * H * W, MT);
   static bool attr = false;
   if (!attr) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_win3_k32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, K32_LDS);
     if (e != hipSuccess) return (int)e;
     attr = true;
   }
-  const int64_t tiles = (int64_t)a.mtiles * a.ntiles;
-  int64_t grid = (int64_t)WSMG_TUNE("WSMG_CONV_K32_WGS", 6) * wsmg_cu_count();
-  if (grid > tiles) grid = tiles;
-  grid = grid / a.ntiles * a.ntiles;            // a workgroup's channel tile is blockIdx % ntiles for every tile it walks
-  if (grid <= 0) return WSMG_EINVAL;
   hipLaunchKernelGGL(conv_win3_k32_kernel, dim3((unsigned)grid), dim3(256), K32_LDS, s, a);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;

@@ -219,7 +219,7 @@ __global__ __launch_bounds__(256, 2) void conv_win_wgrad_kernel(WinWgradArgs a) 
 
 // dW (OHWI float32) of a 64 -> 64 channel k8 s2 p3 convolution on bf16 NHWC — slab_floats == 0: accumulated into with float atomics
 // (the caller zeroes it); > 0: one slab per tile group, stored (WinWgradArgs::slab); returns WSMG_EINVAL for any other shape (the
-// caller then uses the generic kernel).
+// route of wsmg_conv_bf16.hip sends none here).
 static bool winw_fits(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH, int OW) {
   if (Cin != 64 || Cout != 64 || KH != 8 || KW != 8 || stride != 2 || pad != 3) return false;
   return !((size_t)B * H * W * 128 >= (1ull << 31) || (size_t)B * OH * OW * 128 >= (1ull << 31));

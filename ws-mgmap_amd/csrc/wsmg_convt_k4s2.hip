@@ -175,11 +175,26 @@ __global__ __launch_bounds__(256) void convt_k4s2_kernel(CtArgs a) {
 
 }  // namespace
 
+// Workgroups of the launch, with wgs workgroups per CU (WSMG_CONVT_WGS), for the backward-data pass of the adjoint convolution
+// (32 -> 64 channels, k4 s2 p1, H x W = 2 OH x 2 OW: the ConvTranspose's output); 0: the layer is not this kernel's (another geometry, a
+// 128-pixel tile's window beyond the 256 entries, offsets beyond 32 bits, no pair of row parities in the grid)
+int64_t wsmg_convt_k4s2_grid(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH, int OW, int wgs) {
+  if (KH != 4 || KW != 4 || stride != 2 || pad != 1 || Cin != 32 || Cout != 64 || H != 2 * OH || W != 2 * OW) return 0;
+  if (B <= 0 || OH <= 0 || OW <= 0 || wsmg_win3_window_bound(CT_MT, OH, OW) > CT_ENT) return 0;
+  if ((int64_t)B * 4 * OH * OW * 32 * 2 >= (1ll << 31) || (int64_t)B * (OH + 2) * (OW + 2) >= (1 << 30)) return 0;
+  const int64_t units = wsmg_cdiv((int64_t)B * OH * OW, CT_MT) * 2;
+  int64_t grid = (int64_t)wgs * wsmg_cu_count();
+  if (grid > units) grid = units;
+  grid &= ~(int64_t)1;                          // a workgroup's row parity is blockIdx & 1 for every unit it walks
+  return grid > 0 ? grid : 0;
+}
+
 // dst [B][2H][2W][32] = ConvTranspose2d(k4, s2, p1) of src [B][H][W][64] with the adjoint convolution's IHWO weights [32][4][4][64];
-// WSMG_EINVAL for geometries whose window does not fit (the caller then uses the implicit-GEMM kernel)
-int wsmg_convt_k4s2_bf16(const void* src, const void* w_ihwo, void* dst, double* stats, int nslab, int B, int H, int W, hipStream_t s) {
-  if (B <= 0 || H <= 0 || W <= 0 || wsmg_win3_window_bound(CT_MT, H, W) > CT_ENT || (stats && nslab <= 0)) return WSMG_EINVAL;
-  if ((int64_t)B * 4 * H * W * 32 * 2 >= (1ll << 31) || (int64_t)B * (H + 2) * (W + 2) >= (1 << 30)) return WSMG_EINVAL;
+// WSMG_EINVAL where wsmg_convt_k4s2_grid answers 0
+int wsmg_convt_k4s2_bf16(const void* src, const void* w_ihwo, void* dst, double* stats, int nslab, int B, int H, int W, int wgs,
+                         hipStream_t s) {
+  const int64_t grid = wsmg_convt_k4s2_grid(B, 2 * H, 2 * W, 32, 64, 4, 4, 2, 1, H, W, wgs);
+  if (grid == 0 || (stats && nslab <= 0)) return WSMG_EINVAL;
   CtArgs a{(const bf16_t*)src, (const bf16_t*)w_ihwo, (bf16_t*)dst, B, H, W, (int)wsmg_cdiv((int64_t)B * H * W, CT_MT),
            (unsigned)((size_t)B * H * W * 64 * 2), (unsigned)(32u * 16 * 64 * 2), stats, nslab};
   static bool attr = false;
@@ -188,11 +203,6 @@ int wsmg_convt_k4s2_bf16(const void* src, const void* w_ihwo, void* dst, double*
     if (e != hipSuccess) return (int)e;
     attr = true;
   }
-  const int64_t units = (int64_t)a.mtiles * 2;
-  int64_t grid = (int64_t)WSMG_TUNE("WSMG_CONVT_WGS", 6) * wsmg_cu_count();
-  if (grid > units) grid = units;
-  grid &= ~(int64_t)1;                          // a workgroup's row parity is blockIdx & 1 for every unit it walks
-  if (grid <= 0) return WSMG_EINVAL;
   hipLaunchKernelGGL(convt_k4s2_kernel, dim3((unsigned)grid), dim3(256), CT_LDS, s, a);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;

@@ -5,7 +5,8 @@ and the code reads plain attributes of it.  Tests and tools flip a switch with `
 set the variable before the import); `sw.reload()` re-reads the environment.  Defaults are what every reported number uses.
 Switches of experiments that were measured and dropped (round 3: WSMG_WGRAD_STREAM, WSMG_WGRAD_REDUCE_STREAM, WSMG_CONV_CAT,
 WSMG_RNN_EXCL, WSMG_WGRAD_DBG_SKIP, WSMG_LSTM_DW_CONTIG, ...) are gone together with their code; DESIGN.md section 7 keeps the
-measurements.
+measurements.  The library-side switches — the tunes that steer which conv kernel takes a layer, read once by the library itself — have
+their table at the top of csrc/wsmg_conv_route.hip.
 
     name                 environment variable        default  meaning
 """
