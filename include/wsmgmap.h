@@ -930,6 +930,31 @@ int wsmg_gae_returns(const float* rewards, float* value_preds, const float* mask
                      float gamma_tau, int use_gae, int T, int N, float* returns, float* adv, float* adv_norm, double* stats,
                      float eps, wsmg_stream_t stream);
 
+/* Rewards normalised by the running standard deviation of the discounted return, with the statistics on the device: baselines'
+ * `VecNormalize` return path, restated (not a dependency, no golden; the reference has none).  ONE launch of one workgroup.
+ * state: float64 [3 + N] = {mean, var, count, ret[N]} (a fresh normaliser: 0, 1, count0, zeros).  rewards [T][N], masks [T+1][N],
+ * rewards_norm [T][N], of which rows [first_row, T) are written.  For s = first_row .. T-1 in order, every operation float64 and
+ * rounded on its own, rewards / masks widened from float32, gamma / clip / eps widened from the float32 they arrive as:
+ *   ret[n]  = ret[n] * gamma + rewards[s][n]
+ *   bmean   = sum_n ret[n] / N;   bM2 = sum_n (ret[n] - bmean)^2;   delta = bmean - mean;   tot = count + N
+ *   mean   += delta * N / tot;   var = (var * count + bM2 + delta^2 * count * N / tot) / tot;   count = tot
+ *   rewards_norm[s][n] = float32(clamp(rewards[s][n] / sqrt(var + eps), -clip, +clip))      (rounded once; NaN stays NaN)
+ *   ret[n] *= masks[s+1][n]
+ * update == 0: only the rewards_norm line, with the stored var; state is not written.  The two sums over n are taken in a fixed
+ * order without atomics: two launches from one state give the same bits.  rewards, masks, state and rewards_norm must not overlap.
+ * WSMG_EINVAL, before anything is enqueued: T < 1, N < 1, N > 1024, T N >= 2^24, first_row outside [0, T], or a NULL pointer.
+ * first_row == T: nothing to do, nothing is launched. */
+int wsmg_reward_normalize(const float* rewards, const float* masks, double* state, float gamma, float clip, float eps, int T,
+                          int N, int first_row, int update, float* rewards_norm, wsmg_stream_t stream);
+/* wsmg_reward_normalize over rows [first_row, T) (gamma: norm_gamma, eps: norm_eps), then wsmg_gae_returns over rewards_norm[0 .. T)
+ * (rows below first_row: an earlier call's) with the remaining arguments, in ONE launch: rewards_norm and state are the bits of the
+ * first alone, returns / adv / adv_norm / stats / value_preds[T] the bits of the second on that rewards_norm.  adv, adv_norm, stats
+ * may be NULL as there.  WSMG_EINVAL, before anything is enqueued: what either of the two refuses. */
+int wsmg_gae_returns_normalized(const float* rewards, const float* masks, double* state, float norm_gamma, float clip,
+                                float norm_eps, int first_row, int update, float* rewards_norm, float* value_preds,
+                                const float* next_value, float gamma, float gamma_tau, int use_gae, int T, int N, float* returns,
+                                float* adv, float* adv_norm, double* stats, float eps, wsmg_stream_t stream);
+
 /* A PPO minibatch in one launch (habitat-baselines' `RolloutStorage.recurrent_generator`, restated; no reference counterpart): the
  * columns `ind` of a list of stored tensors,  dst_f[r][j][:] = src_f[r][ind[j]][:]  for every field f, r < rows_f, j < n  — per
  * field what `src[:rows].index_select(1, ind)` gives.  src_f is [>= rows][N][row_bytes], dst_f [rows][n][row_bytes]; bytes are
