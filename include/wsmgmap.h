@@ -203,8 +203,10 @@ int wsmg_attn_fwd(const float* q, const float* k, const float* v, const uint8_t*
 
 /* backward: given dout [B][C] and dattn [B][I] (NULL = zeros; the contrastive monitor differentiates
  * the weights themselves, policy.py:80-84) write dq [B][C], dk [B][I][C], dv [B][I][C]. */
-/* wsmg_attn_bwd*: passing dk == dv selects the keys-are-values form (k == v): ONE gradient tensor
- * dk[i] = dl[i] q + attn[i] dout is written (used when the key projection is folded into the query). */
+/* wsmg_attn_bwd*: with dk == dv (one buffer) ONE gradient tensor dk[i] = dl[i] q + attn[i] dout is written.  k == v
+ * AND dk == dv, as pointers, selects the keys-are-values kernels (used when the key projection is folded into the
+ * query; wsmg_attn_fwd* selects its one-pass form on k == v); with k != v and dk == dv the generic kernel writes the
+ * one tensor itself. */
 int wsmg_attn_bwd(const float* q, const float* k, const float* v, const float* attn, const float* dout,
                   const float* dattn, float scale, int B, int I, int C, float* dq, float* dk, float* dv,
                   wsmg_stream_t stream);

@@ -10,7 +10,8 @@ Section, kernels it pins, and the test that held them before:
                     test_attention_with_folded_key_projection (I = 37; bf16 at 2e-2 of the tensor maximum)
 2. direct calls     the same kernels through wsmg_attn_fwd[_bf16] / wsmg_attn_bwd[_bf16] into NaN-guarded buffers, with dattn = NULL,
                     with dout = 0 and with both; two launches bit-identical — nothing entered the dattn == NULL branch on purpose
-3. the two forms    one tensor (k == v, dk == dv: the dispatch is by pointer equality) against two tensors of equal values
+3. the two forms    one tensor (k == v, dk == dv: the dispatch is by pointer equality) against two tensors of equal values; two tensors
+                    with ONE gradient buffer (k != v, dk == dv: the generic backward's own one-tensor branch)
 4. shared sets      attn_fwd_kernel / attn_bwd_kernel with a row index (ops.attention_shared, wsmg_attn_shared_*), dlogits itself,
                     masks that are no prefix, unused sets — test_gpu_kernels.py::test_attention_over_shared_sets (prefix masks)
 5. refusals         I = 2561, I = 0, C != 256, a NULL row index: WSMG_EINVAL, nothing written
@@ -246,6 +247,36 @@ def test_one_tensor_and_two_equal_tensors_meet_the_same_reference(I, dtype):
             close(f"two.{name}.{n}", two[n], want2[n], b2[n], ("generic", n))
         close(f"one.{name}.dx", one["dx"].float(), ref["grads"]["both"]["dx"], b1["dx"], ("same", "dx"))
         close(f"two.{name}.dk+dv", two["dk"].double() + two["dv"].double(), ref["grads"]["both"]["dx"], b2["dk"] + b2["dv"])
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=DT_IDS)
+@pytest.mark.parametrize("I", [9, 257])
+def test_two_equal_tensors_with_one_gradient_buffer(I, dtype):
+    """k != v as pointers (equal values) with dk == dv: the launcher wants k == v AND dk == dv for the keys-are-values kernels, so this
+    call stays on the generic ones, whose backward then writes the ONE tensor dk[i] = dl[i] q + attn[i] dout into the buffer — the float64
+    dx, under the bar of the two-tensor form's dk + dv."""
+    bf16 = dtype == torch.bfloat16
+    for kind, mask in (("plain", "none"), ("lane_tagged", "prefix_I-1"), ("grid", "full_row")):
+        inp = ac.inputs("same", I, kind, mask, bf16)
+        ref = ac.reference(inp)
+        two_inp = dict(inp, form="generic", v=inp["k"].clone())
+        b2 = ac.bars(two_inp, ac.reference(two_inp))
+        B, U = inp["B"], inp["U"]
+        q, g, ga, m = inp["q"].cuda(), inp["dout"].cuda(), inp["dattn"].cuda(), dev_mask(inp)
+        k = inp["k"].to(dtype).cuda()
+        v = k.clone()
+        assert k.data_ptr() != v.data_ptr()
+        out, attn, dq = Guarded((B, ac.C), torch.float32), Guarded((B, I), torch.float32), Guarded((B, ac.C), torch.float32)
+        dx = Guarded((U, I, ac.C), dtype)
+        call("wsmg_attn_fwd" + sfx(dtype), P(q), P(k), P(v), P(m), ac.SCALE, B, I, ac.C, P(out.t), P(attn.t), S())
+        call("wsmg_attn_bwd" + sfx(dtype), P(q), P(k), P(v), P(attn.t), P(g), P(ga), ac.SCALE, B, I, ac.C, P(dq.t), P(dx.t), P(dx.t), S())
+        name = "two_one_buffer." + case_id(inp)
+        for n, t in (("out", out), ("attn", attn), ("dq", dq), ("dx", dx)):
+            assert t.guards_intact(), (name, n)
+        close(f"{name}.out", out.t, ref["out"], b2["out"], ("generic", "out"))
+        close(f"{name}.attn", attn.t, ref["attn"], b2["attn"], ("generic", "attn"))
+        close(f"{name}.dq", dq.t, ref["grads"]["both"]["dq"], b2["dq"], ("generic", "dq"))
+        close(f"{name}.dx", dx.t.float(), ref["grads"]["both"]["dx"], b2["dk"] + b2["dv"])
 
 
 # ============================================================================= 4. shared sets

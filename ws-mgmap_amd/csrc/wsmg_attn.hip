@@ -8,33 +8,13 @@
 // (token-major [I][256], one 1-KiB wave-wide float4 load per token), keeps the logits in LDS and
 // reduces with wavefront shuffles.  The matrix cores are used where the path has a real
 // contraction — the key projection (Conv1d k=1), which runs on the conv engine's MFMA GEMM.
-#include "wsmg_common.h"
+#include "wsmg_attn_common.h"
+#include "wsmg_lanes.h"
 
 namespace {
 
-constexpr int AC = 256;       // channels (hidden_size/2)
 constexpr int AWAVES = 4;
-constexpr int AMAX_I = 2560;  // logits kept in LDS (10 KiB); 2304 = the 48 x 48 encoded map of the E=196 geometry
 constexpr int SAME_WAVES = 16;  // waves per row of the keys-are-values kernels (B = 512 rows alone give only 2 workgroups per CU)
-
-__device__ inline float block_reduce_max(float v, float* sh, int wave, int lane) {
-  v = wave_max(v);
-  if (lane == 0) sh[wave] = v;
-  __syncthreads();
-  float r = sh[0];
-  for (int w = 1; w < AWAVES; ++w) r = fmaxf(r, sh[w]);
-  __syncthreads();
-  return r;
-}
-__device__ inline float block_reduce_sum(float v, float* sh, int wave, int lane) {
-  v = wave_sum(v);
-  if (lane == 0) sh[wave] = v;
-  __syncthreads();
-  float r = sh[0];
-  for (int w = 1; w < AWAVES; ++w) r += sh[w];
-  __syncthreads();
-  return r;
-}
 
 template <class T>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(const float* __restrict__ q, const T* __restrict__ k,
@@ -59,8 +39,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const float* __restrict__
   for (int i0 = wave * 4; i0 < I; i0 += AWAVES * 4) {
     f32x4 kv[4];
     float d[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) kv[u] = (i0 + u < I) ? ld4(kb + (size_t)(i0 + u) * AC) : f32x4{0.f, 0.f, 0.f, 0.f};
+    load_tokens(kb, i0, I, kv);
 #pragma unroll
     for (int u = 0; u < 4; ++u) d[u] = wave_sum(qv[0] * kv[u][0] + qv[1] * kv[u][1] + qv[2] * kv[u][2] + qv[3] * kv[u][3]);
     if (lane == 0) {
@@ -79,14 +58,14 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const float* __restrict__
   // phase 2: softmax over the tokens
   float mx = -INFINITY;
   for (int i = tid; i < I; i += 256) mx = fmaxf(mx, lg[i]);
-  mx = block_reduce_max(mx, red, wave, lane);
+  mx = block_max(mx, red);
   float sm = 0.f;
   for (int i = tid; i < I; i += 256) {
     float e = expf(lg[i] - mx);
     lg[i] = e;
     sm += e;
   }
-  sm = block_reduce_sum(sm, red, wave, lane);
+  sm = block_sum(sm, red);
   const float inv = 1.f / sm;
   for (int i = tid; i < I; i += 256) {
     float a = lg[i] * inv;
@@ -98,8 +77,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const float* __restrict__
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   for (int i0 = wave * 4; i0 < I; i0 += AWAVES * 4) {
     f32x4 vv[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) vv[u] = (i0 + u < I) ? ld4(vb + (size_t)(i0 + u) * AC) : f32x4{0.f, 0.f, 0.f, 0.f};
+    load_tokens(vb, i0, I, vv);
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const float a = (i0 + u < I) ? lg[i0 + u] : 0.f;
@@ -107,16 +85,16 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const float* __restrict__
       for (int j = 0; j < 4; ++j) acc[j] += a * vv[u][j];
     }
   }
-  reinterpret_cast<f32x4*>(&part[wave][0])[lane] = acc;
+  put_row(part, wave, lane, acc);
   __syncthreads();
-  float o = part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid];
-  out[(size_t)b * AC + tid] = o;
+  out[(size_t)b * AC + tid] = sum_rows<AWAVES>(part, tid);
 }
 
 // backward: da = dout.v + dattn; s = sum attn*da; dl = attn*(da-s)*scale;
 //           dq = sum_i dl[i] k[i]; dk[i] = dl[i] q; dv[i] = attn[i] dout
-// dk == dv (same buffer) selects the keys-are-values form used when the key projection is folded into the
-// query: one gradient tensor dk[i] = dl[i] q + attn[i] dout is written instead of two.
+// dk == dv (one buffer, whatever k and v are) makes this kernel write ONE gradient tensor dk[i] = dl[i] q + attn[i] dout instead of
+// two: the gradient of a token tensor that was passed as keys and as values.  The launcher sends k == v with dk == dv to the
+// keys-are-values kernel below, so that branch runs here only for two token tensors with one gradient buffer.
 template <class T>
 __global__ __launch_bounds__(256) void attn_bwd_kernel(const float* __restrict__ q, const T* __restrict__ k,
                                                        const T* __restrict__ v,
@@ -151,8 +129,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const float* __restrict__
   for (int i0 = wave * 4; i0 < I; i0 += AWAVES * 4) {
     f32x4 vv[4];
     float d[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) vv[u] = (i0 + u < I) ? ld4(vb + (size_t)(i0 + u) * AC) : f32x4{0.f, 0.f, 0.f, 0.f};
+    load_tokens(vb, i0, I, vv);
 #pragma unroll
     for (int u = 0; u < 4; ++u) d[u] = wave_sum(gv[0] * vv[u][0] + gv[1] * vv[u][1] + gv[2] * vv[u][2] + gv[3] * vv[u][3]);
 #pragma unroll
@@ -172,7 +149,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const float* __restrict__
   __syncthreads();
   float s = 0.f;
   for (int i = tid; i < I; i += 256) s += ab[i] * da[i];
-  s = block_reduce_sum(s, red, wave, lane);
+  s = block_sum(s, red);
   for (int i = tid; i < I; i += 256) {
     const float dl = ab[i] * (da[i] - s) * scale;
     da[i] = dl;
@@ -182,8 +159,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const float* __restrict__
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   for (int i0 = wave * 4; i0 < I; i0 += AWAVES * 4) {
     f32x4 kv[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) kv[u] = (i0 + u < I) ? ld4(kb + (size_t)(i0 + u) * AC) : f32x4{0.f, 0.f, 0.f, 0.f};
+    load_tokens(kb, i0, I, kv);
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int i = i0 + u;
@@ -203,9 +179,9 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const float* __restrict__
       if (!shared) st4(dkb + (size_t)i * AC, o);
     }
   }
-  reinterpret_cast<f32x4*>(&part[wave][0])[lane] = acc;
+  put_row(part, wave, lane, acc);
   __syncthreads();
-  dq[(size_t)b * AC + tid] = part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid];
+  dq[(size_t)b * AC + tid] = sum_rows<AWAVES>(part, tid);
 }
 
 
@@ -220,43 +196,21 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const float* __restrict__
 //              dq = scale * (sum_i a_i da_i x_i - s * sum_i a_i x_i)   -> both sums accumulate in the read pass;
 //              dx_i = a_i (da_i - s) scale * q + a_i * dout            -> needs no x at all (write-only pass).
 // Eight tokens per trip and wave; their eight partial dot products are reduced together with a halving
-// butterfly (v_permlane32/16_swap, DPP): 10 lane exchanges per 8 tokens instead of 48.
-template <int C, int D, int NV>
-__device__ __forceinline__ void halve8(float (&v)[NV], int lane) {
-  if constexpr (D == 32 || D == 16) {
-#pragma unroll
-    for (int i = 0; i < C / 2; ++i) {
-      const int lo = __float_as_int(v[i]), hi = __float_as_int(v[i + C / 2]);
-      auto r = (D == 32) ? __builtin_amdgcn_permlane32_swap(lo, hi, false, false)
-                         : __builtin_amdgcn_permlane16_swap(lo, hi, false, false);
-      v[i] = __int_as_float(r[0]) + __int_as_float(r[1]);
-    }
-  } else {   // D == 8: DPP row rotate by 8
-    const bool up = (lane & D) != 0;
-#pragma unroll
-    for (int i = 0; i < C / 2; ++i) {
-      const float keep = up ? v[i + C / 2] : v[i];
-      const float send = up ? v[i] : v[i + C / 2];
-      const int x = __float_as_int(send);
-      v[i] = keep + __int_as_float(__builtin_amdgcn_update_dpp(x, x, 0x128, 0xF, 0xF, false));
-    }
-  }
-}
+// butterfly (wsmg_lanes.h: v_permlane32/16_swap, DPP): 10 lane exchanges per 8 tokens instead of 48.
+
 // dot products of 8 token rows with one vector, all 8 results in every lane: d[u] = sum_c g[c] x_u[c]
 __device__ __forceinline__ void dots8(const f32x4 (&xv)[8], const f32x4 g, int lane, float (&d)[8]) {
   float p[8];
 #pragma unroll
   for (int u = 0; u < 8; ++u) p[u] = g[0] * xv[u][0] + g[1] * xv[u][1] + g[2] * xv[u][2] + g[3] * xv[u][3];
-  halve8<8, 32>(p, lane);
-  halve8<4, 16>(p, lane);
-  halve8<2, 8>(p, lane);
+  halve<8, 32>(p, lane);
+  halve<4, 16>(p, lane);
+  halve<2, 8>(p, lane);
   float r = p[0];   // token ((lane>>5)&1)*4 + ((lane>>4)&1)*2 + ((lane>>3)&1), summed over lanes that differ in bits 3..5
   {
-    int x = __float_as_int(r);
-    r += __int_as_float(__builtin_amdgcn_update_dpp(x, x, 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
-    x = __float_as_int(r);
-    r += __int_as_float(__builtin_amdgcn_update_dpp(x, x, 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
-    x = __float_as_int(r);
+    r += lane_xor<1>(r);
+    r += lane_xor<2>(r);
+    const int x = __float_as_int(r);
     r += __int_as_float(__builtin_amdgcn_update_dpp(x, x, 0x141, 0xF, 0xF, false));  // row_half_mirror: lane i <-> 7 - i
   }
 #pragma unroll
@@ -279,16 +233,12 @@ __global__ __launch_bounds__(NW * 64) void attn_same_fwd_kernel(const float* __r
   // the next trip's eight token rows are requested before this trip is reduced (the loop is latency-bound otherwise:
   // 8 waves per CU, one 8-load batch in flight per wave)
   f32x4 xv[8], xn[8];
-#pragma unroll
-  for (int u = 0; u < 8; ++u) xn[u] = (wave * 8 + u < I) ? ld4(xb + (size_t)(wave * 8 + u) * AC) : f32x4{0.f, 0.f, 0.f, 0.f};
+  load_tokens(xb, wave * 8, I, xn);
   for (int i0 = wave * 8; i0 < I; i0 += NW * 8) {
 #pragma unroll
     for (int u = 0; u < 8; ++u) xv[u] = xn[u];
     const int i1 = i0 + NW * 8;
-    if (i1 < I) {
-#pragma unroll
-      for (int u = 0; u < 8; ++u) xn[u] = (i1 + u < I) ? ld4(xb + (size_t)(i1 + u) * AC) : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
+    if (i1 < I) load_tokens(xb, i1, I, xn);
     float d[8];
     dots8(xv, qv, lane, d);
     float mx = m;
@@ -320,7 +270,7 @@ __global__ __launch_bounds__(NW * 64) void attn_same_fwd_kernel(const float* __r
     m = mx;
   }
   if (lane == 0) { wm[wave] = m; wsum[wave] = ssum; }
-  reinterpret_cast<f32x4*>(&part[wave][0])[lane] = acc;
+  put_row(part, wave, lane, acc);
   __syncthreads();
   float M = wm[0];
 #pragma unroll
@@ -359,16 +309,12 @@ __global__ __launch_bounds__(NW * 64) void attn_same_bwd_kernel(const float* __r
   float s = 0.f;
   f32x4 A = {0.f, 0.f, 0.f, 0.f}, O = {0.f, 0.f, 0.f, 0.f};
   f32x4 xv[8], xn[8];   // (next trip prefetched, as in the forward kernel)
-#pragma unroll
-  for (int u = 0; u < 8; ++u) xn[u] = (wave * 8 + u < I) ? ld4(xb + (size_t)(wave * 8 + u) * AC) : f32x4{0.f, 0.f, 0.f, 0.f};
+  load_tokens(xb, wave * 8, I, xn);
   for (int i0 = wave * 8; i0 < I; i0 += NW * 8) {
 #pragma unroll
     for (int u = 0; u < 8; ++u) xv[u] = xn[u];
     const int i1 = i0 + NW * 8;
-    if (i1 < I) {
-#pragma unroll
-      for (int u = 0; u < 8; ++u) xn[u] = (i1 + u < I) ? ld4(xb + (size_t)(i1 + u) * AC) : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
+    if (i1 < I) load_tokens(xb, i1, I, xn);
     // the per-token scalars of this trip: lane u < 8 fetches token i0 + u, then broadcast
     float a_l = 0.f, g_l = 0.f;
     if (lane < 8 && i0 + lane < I) { a_l = ab[i0 + lane]; g_l = dab ? dab[i0 + lane] : 0.f; }
@@ -388,13 +334,13 @@ __global__ __launch_bounds__(NW * 64) void attn_same_bwd_kernel(const float* __r
     if (lane < 8 && i0 + lane < I) da[i0 + lane] = mine;
   }
   if (lane == 0) wsum[wave] = s;
-  reinterpret_cast<f32x4*>(&pa[wave][0])[lane] = A;
-  reinterpret_cast<f32x4*>(&po[wave][0])[lane] = O;
+  put_row(pa, wave, lane, A);
+  put_row(po, wave, lane, O);
   __syncthreads();
   s = 0.f;
-  float sa = 0.f, so = 0.f;
 #pragma unroll
-  for (int w = 0; w < NW; ++w) { s += wsum[w]; sa += pa[w][tid & (AC - 1)]; so += po[w][tid & (AC - 1)]; }
+  for (int w = 0; w < NW; ++w) s += wsum[w];
+  const float sa = sum_rows<NW>(pa, tid & (AC - 1)), so = sum_rows<NW>(po, tid & (AC - 1));
   if (tid < AC) dq[(size_t)b * AC + tid] = scale * (sa - s * so);
   // write pass: dx_i = dl_i * q + a_i * dout
   for (int i0 = wave * 8; i0 < I; i0 += NW * 8) {
@@ -417,113 +363,78 @@ __global__ __launch_bounds__(NW * 64) void attn_same_bwd_kernel(const float* __r
   }
 }
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+// ---- launchers.  row_index == NULL: a key / value set per row, and k == v (with dk == dv in the backward pass) as POINTERS selects
+// the keys-are-values kernels.  row_index != NULL, the shared-set form: B query rows attend over U << B key / value sets (one per
+// unique instruction; row b uses set row_index[b]), always on the generic kernels.  That form replaces the reference's per-row copies
+// of the instruction keys / values (mg_map_policy.py:229-232 on tensors that repeat every instruction T times) — nothing is gathered,
+// dk / dv are not written, and dK / dV of a set are formed by the caller from dlogits.
+bool attn_args_ok(int B, int I, int C) { return C == AC && B > 0 && I > 0 && I <= AMAX_I; }
 
-// float32 -> e4m3 (round to nearest even, saturating at +-448), 4 values per thread
-__global__ __launch_bounds__(256) void quantize_e4m3_kernel(const float* __restrict__ x, int64_t n4, float inv_scale,
-                                                            unsigned* __restrict__ y) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n4) return;
-  f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) v[j] = fminf(fmaxf(v[j] * inv_scale, -448.f), 448.f);
-  int w = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], 0, false);
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], w, true);
-  y[i] = (unsigned)w;
+template <class T>
+int attn_fwd(const float* q, const T* k, const T* v, const uint8_t* mask, const int64_t* row_index, float scale, int B, int I, int C,
+             float* out, float* attn, wsmg_stream_t stream) {
+  if (!attn_args_ok(B, I, C)) return WSMG_EINVAL;
+  if (k == v && !row_index)   // keys are values: one-pass form
+    hipLaunchKernelGGL((attn_same_fwd_kernel<T, SAME_WAVES>), dim3(B), dim3(SAME_WAVES * 64), 0, wsmg_s(stream), q, k, mask, scale, I, out, attn);
+  else
+    hipLaunchKernelGGL(attn_fwd_kernel<T>, dim3(B), dim3(256), 0, wsmg_s(stream), q, k, v, mask, scale, I, out, attn, row_index);
+  WSMG_RETURN_LAUNCH();
+}
+
+template <class T>
+int attn_bwd(const float* q, const T* k, const T* v, const float* attn, const float* dout, const float* dattn, const int64_t* row_index,
+             float scale, int B, int I, int C, float* dq, T* dk, T* dv, float* dlogits, wsmg_stream_t stream) {
+  if (!attn_args_ok(B, I, C)) return WSMG_EINVAL;
+  if (k == v && dk == dv && !row_index)   // keys are values: one read pass + one write pass
+    hipLaunchKernelGGL((attn_same_bwd_kernel<T, SAME_WAVES>), dim3(B), dim3(SAME_WAVES * 64), 0, wsmg_s(stream), q, k, attn, dout, dattn, scale, I, dq, dk,
+                       dlogits);
+  else
+    hipLaunchKernelGGL(attn_bwd_kernel<T>, dim3(B), dim3(256), 0, wsmg_s(stream), q, k, v, attn, dout, dattn, scale, I, dq, dk, dv, row_index,
+                       dlogits);
+  WSMG_RETURN_LAUNCH();
 }
 }  // namespace
 
 extern "C" int wsmg_attn_fwd(const float* q, const float* k, const float* v, const uint8_t* mask, float scale, int B,
                              int I, int C, float* out, float* attn, wsmg_stream_t stream) {
-  if (C != AC || B <= 0 || I <= 0 || I > AMAX_I) return WSMG_EINVAL;
-  if (k == v) {   // keys are values: one-pass form
-    hipLaunchKernelGGL((attn_same_fwd_kernel<float, SAME_WAVES>), dim3(B), dim3(SAME_WAVES * 64), 0, wsmg_s(stream), q, k, mask, scale, I, out, attn);
-    WSMG_RETURN_LAUNCH();
-  }
-  hipLaunchKernelGGL(attn_fwd_kernel<float>, dim3(B), dim3(256), 0, wsmg_s(stream), q, k, v, mask, scale, I, out, attn, (const int64_t*)nullptr);
-  WSMG_RETURN_LAUNCH();
+  return attn_fwd<float>(q, k, v, mask, nullptr, scale, B, I, C, out, attn, stream);
 }
-
 extern "C" int wsmg_attn_fwd_bf16(const float* q, const void* k, const void* v, const uint8_t* mask, float scale, int B,
                                   int I, int C, float* out, float* attn, wsmg_stream_t stream) {
-  if (C != AC || B <= 0 || I <= 0 || I > AMAX_I) return WSMG_EINVAL;
-  if (k == v) {
-    hipLaunchKernelGGL((attn_same_fwd_kernel<bf16_t, SAME_WAVES>), dim3(B), dim3(SAME_WAVES * 64), 0, wsmg_s(stream), q, (const bf16_t*)k, mask, scale, I, out, attn);
-    WSMG_RETURN_LAUNCH();
-  }
-  hipLaunchKernelGGL(attn_fwd_kernel<bf16_t>, dim3(B), dim3(256), 0, wsmg_s(stream), q, (const bf16_t*)k,
-                     (const bf16_t*)v, mask, scale, I, out, attn, (const int64_t*)nullptr);
-  WSMG_RETURN_LAUNCH();
+  return attn_fwd<bf16_t>(q, (const bf16_t*)k, (const bf16_t*)v, mask, nullptr, scale, B, I, C, out, attn, stream);
 }
-
 extern "C" int wsmg_attn_bwd(const float* q, const float* k, const float* v, const float* attn, const float* dout,
                              const float* dattn, float scale, int B, int I, int C, float* dq, float* dk, float* dv,
                              wsmg_stream_t stream) {
-  if (C != AC || B <= 0 || I <= 0 || I > AMAX_I) return WSMG_EINVAL;
-  if (k == v && dk == dv) {   // keys are values: one read pass + one write pass
-    hipLaunchKernelGGL((attn_same_bwd_kernel<float, SAME_WAVES>), dim3(B), dim3(SAME_WAVES * 64), 0, wsmg_s(stream), q, k, attn, dout, dattn, scale, I, dq, dk,
-                       (float*)nullptr);
-    WSMG_RETURN_LAUNCH();
-  }
-  hipLaunchKernelGGL(attn_bwd_kernel<float>, dim3(B), dim3(256), 0, wsmg_s(stream), q, k, v, attn, dout, dattn, scale,
-                     I, dq, dk, dv, (const int64_t*)nullptr, (float*)nullptr);
-  WSMG_RETURN_LAUNCH();
+  return attn_bwd<float>(q, k, v, attn, dout, dattn, nullptr, scale, B, I, C, dq, dk, dv, nullptr, stream);
 }
-
 extern "C" int wsmg_attn_bwd_bf16(const float* q, const void* k, const void* v, const float* attn, const float* dout,
                                   const float* dattn, float scale, int B, int I, int C, float* dq, void* dk, void* dv,
                                   wsmg_stream_t stream) {
-  if (C != AC || B <= 0 || I <= 0 || I > AMAX_I) return WSMG_EINVAL;
-  if (k == v && dk == dv) {
-    hipLaunchKernelGGL((attn_same_bwd_kernel<bf16_t, SAME_WAVES>), dim3(B), dim3(SAME_WAVES * 64), 0, wsmg_s(stream), q, (const bf16_t*)k, attn, dout, dattn, scale, I,
-                       dq, (bf16_t*)dk, (float*)nullptr);
-    WSMG_RETURN_LAUNCH();
-  }
-  hipLaunchKernelGGL(attn_bwd_kernel<bf16_t>, dim3(B), dim3(256), 0, wsmg_s(stream), q, (const bf16_t*)k,
-                     (const bf16_t*)v, attn, dout, dattn, scale, I, dq, (bf16_t*)dk, (bf16_t*)dv, (const int64_t*)nullptr, (float*)nullptr);
-  WSMG_RETURN_LAUNCH();
+  return attn_bwd<bf16_t>(q, (const bf16_t*)k, (const bf16_t*)v, attn, dout, dattn, nullptr, scale, B, I, C, dq, (bf16_t*)dk, (bf16_t*)dv,
+                          nullptr, stream);
 }
-
-extern "C" int wsmg_quantize_e4m3(const float* x, int64_t n, float inv_scale, uint8_t* y, wsmg_stream_t stream) {
-  if (n <= 0 || (n & 3) != 0) return WSMG_EINVAL;
-  const int64_t n4 = n / 4;
-  hipLaunchKernelGGL(quantize_e4m3_kernel, dim3((unsigned)wsmg_cdiv(n4, 256)), dim3(256), 0, wsmg_s(stream), x, n4, inv_scale,
-                     reinterpret_cast<unsigned*>(y));
-  WSMG_RETURN_LAUNCH();
-}
-
-// ---- shared-set form: B query rows attend over U << B key/value sets (one per unique instruction; row b uses set
-// row_index[b]).  Replaces the reference's per-row copies of the instruction keys / values (mg_map_policy.py:229-232 on
-// tensors that repeat every instruction T times) — nothing is gathered, and dK / dV of a set are formed by the caller.
 extern "C" int wsmg_attn_shared_fwd(const float* q, const float* k_sets, const float* v_sets, const uint8_t* mask_sets,
                                     const int64_t* row_index, float scale, int B, int I, int C, float* out, float* attn,
                                     wsmg_stream_t stream) {
-  if (C != AC || B <= 0 || I <= 0 || I > AMAX_I || !row_index) return WSMG_EINVAL;
-  hipLaunchKernelGGL(attn_fwd_kernel<float>, dim3(B), dim3(256), 0, wsmg_s(stream), q, k_sets, v_sets, mask_sets, scale, I, out,
-                     attn, row_index);
-  WSMG_RETURN_LAUNCH();
+  return row_index ? attn_fwd<float>(q, k_sets, v_sets, mask_sets, row_index, scale, B, I, C, out, attn, stream) : WSMG_EINVAL;
 }
 extern "C" int wsmg_attn_shared_fwd_bf16(const float* q, const void* k_sets, const void* v_sets, const uint8_t* mask_sets,
                                          const int64_t* row_index, float scale, int B, int I, int C, float* out, float* attn,
                                          wsmg_stream_t stream) {
-  if (C != AC || B <= 0 || I <= 0 || I > AMAX_I || !row_index) return WSMG_EINVAL;
-  hipLaunchKernelGGL(attn_fwd_kernel<bf16_t>, dim3(B), dim3(256), 0, wsmg_s(stream), q, (const bf16_t*)k_sets,
-                     (const bf16_t*)v_sets, mask_sets, scale, I, out, attn, row_index);
-  WSMG_RETURN_LAUNCH();
+  return row_index ? attn_fwd<bf16_t>(q, (const bf16_t*)k_sets, (const bf16_t*)v_sets, mask_sets, row_index, scale, B, I, C, out, attn, stream)
+                   : WSMG_EINVAL;
 }
 extern "C" int wsmg_attn_shared_bwd(const float* q, const float* k_sets, const float* v_sets, const float* attn,
                                     const float* dout, const float* dattn, const int64_t* row_index, float scale, int B, int I,
                                     int C, float* dq, float* dlogits, wsmg_stream_t stream) {
-  if (C != AC || B <= 0 || I <= 0 || I > AMAX_I || !row_index || !dlogits) return WSMG_EINVAL;
-  hipLaunchKernelGGL(attn_bwd_kernel<float>, dim3(B), dim3(256), 0, wsmg_s(stream), q, k_sets, v_sets, attn, dout, dattn, scale, I,
-                     dq, (float*)nullptr, (float*)nullptr, row_index, dlogits);
-  WSMG_RETURN_LAUNCH();
+  return row_index && dlogits ? attn_bwd<float>(q, k_sets, v_sets, attn, dout, dattn, row_index, scale, B, I, C, dq, nullptr, nullptr, dlogits, stream)
+                              : WSMG_EINVAL;
 }
 extern "C" int wsmg_attn_shared_bwd_bf16(const float* q, const void* k_sets, const void* v_sets, const float* attn,
                                          const float* dout, const float* dattn, const int64_t* row_index, float scale, int B,
                                          int I, int C, float* dq, float* dlogits, wsmg_stream_t stream) {
-  if (C != AC || B <= 0 || I <= 0 || I > AMAX_I || !row_index || !dlogits) return WSMG_EINVAL;
-  hipLaunchKernelGGL(attn_bwd_kernel<bf16_t>, dim3(B), dim3(256), 0, wsmg_s(stream), q, (const bf16_t*)k_sets,
-                     (const bf16_t*)v_sets, attn, dout, dattn, scale, I, dq, (bf16_t*)nullptr, (bf16_t*)nullptr, row_index, dlogits);
-  WSMG_RETURN_LAUNCH();
+  return row_index && dlogits ? attn_bwd<bf16_t>(q, (const bf16_t*)k_sets, (const bf16_t*)v_sets, attn, dout, dattn, row_index, scale, B, I, C, dq,
+                                                 nullptr, nullptr, dlogits, stream)
+                              : WSMG_EINVAL;
 }

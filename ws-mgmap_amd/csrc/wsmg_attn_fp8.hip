@@ -20,18 +20,11 @@
 //     gradient of the de-quantised tokens; dq = d q_f W_k^T and dW_k = q^T d q_f are the same MFMA kernel / one GEMM.
 #include <stdlib.h>
 
-#include "wsmg_common.h"
+#include "wsmg_attn_common.h"
 
 namespace {
 
-constexpr int AC = 256;
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f32x4 cvt4_e4m3(unsigned w) {
-  auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false);
-  auto hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
-  return f32x4{lo[0], lo[1], hi[0], hi[1]};
-}
 
 // ----------------------------------------------------------------------------- fold: out[B][256] = in[B][256] @ W  (or W^T)
 // W [256][256] row-major (Conv1d weight [C_out][C_in]).  transpose = 0: out[b][j] = sum_o in[b][o] W[o][j]   (q_f = q W_k);
@@ -66,7 +59,7 @@ __global__ __launch_bounds__(256) void attn_fp8_fold_kernel(const float* __restr
 }
 
 // ----------------------------------------------------------------------------- forward, split over the token axis
-constexpr int F8_CHUNK = 224;         // tokens per workgroup at most (56 KB of dynamic LDS: a whole row when the batch fills the chip)
+constexpr int F8_CHUNK = F8_MAX_L;    // tokens per workgroup at most (a whole row when the batch fills the chip)
 constexpr int F8_PART = AC + 2;       // partial record: 256 weighted sums, local max, local sum
 
 struct Fp8FwdArgs {
@@ -88,7 +81,7 @@ __device__ __forceinline__ float dot16(const uint8_t* tok, const float (&qv)[16]
   float d = 0.f;
 #pragma unroll
   for (int w4 = 0; w4 < 4; ++w4) {
-    const f32x4 v = cvt4_e4m3(raw[w4]);
+    const f32x4 v = e4m3_dec4(raw[w4]);
 #pragma unroll
     for (int j = 0; j < 4; ++j) d = fmaf(qv[4 * w4 + j], v[j], d);
   }
@@ -152,13 +145,13 @@ __global__ __launch_bounds__(256) void attn_fp8_fwd_kernel(Fp8FwdArgs a) {
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   for (int i = wave; i < nt; i += 4) {
     const float w = lg[i];
-    const f32x4 xv = cvt4_e4m3(reinterpret_cast<const unsigned*>(xs + (size_t)i * AC)[lane]);
+    const f32x4 xv = e4m3_dec4(reinterpret_cast<const unsigned*>(xs + (size_t)i * AC)[lane]);
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[j] = fmaf(w, xv[j], acc[j]);
   }
-  reinterpret_cast<f32x4*>(&psum[wave][0])[lane] = acc;
+  put_row(psum, wave, lane, acc);
   __syncthreads();
-  const float mine = psum[0][tid] + psum[1][tid] + psum[2][tid] + psum[3][tid];
+  const float mine = sum_rows<4>(psum, tid);
   if (a.ns == 1) {   // the whole row is here: normalise and leave
     const float inv1 = 1.f / sm;
     a.out[(size_t)b * AC + tid] = mine * inv1 * xsc;
@@ -207,7 +200,6 @@ __global__ __launch_bounds__(256) void attn_fp8_fwd_kernel(Fp8FwdArgs a) {
 // [1,256] x [256,256] product per row, W_k (256 KB) read through L2 — as two float32 fmaf chains per output column (threads j and
 // 256 + j take the two halves of the reduction); (3) the tokens land in LDS, the logits, the softmax and the weighted sum are
 // attn_fp8_fwd_kernel's (whole row, ns = 1), with eight waves instead of four.  No second launch, no workspace, no ticket.
-constexpr int ROW_MAX_L = 224;        // 56 KB of dynamic LDS for the row's bytes
 struct Fp8RowArgs {
   const float* q;         // [B][256]
   const float* w;         // [256][256] Conv1d weight [C_out][C_in]: q_f[j] = sum_o q[o] w[o][j]
@@ -223,7 +215,7 @@ struct Fp8RowArgs {
 
 __global__ __launch_bounds__(512) void attn_fp8_row_kernel(Fp8RowArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t xs[];   // L * 256 token bytes
-  __shared__ float lg[ROW_MAX_L];
+  __shared__ float lg[F8_MAX_L];
   __shared__ __attribute__((aligned(16))) float qs[AC];
   __shared__ __attribute__((aligned(16))) float qfs[2][AC];
   __shared__ __attribute__((aligned(16))) float psum[8][AC];
@@ -234,7 +226,7 @@ __global__ __launch_bounds__(512) void attn_fp8_row_kernel(Fp8RowArgs a) {
   const int L = a.L;
   const int len = a.lengths ? a.lengths[b] : L;
   // (1) the row's bytes: up to 7 x 16 bytes per thread, in flight while the fold runs
-  constexpr int TRIPS = ROW_MAX_L * (AC / 16) / 512;
+  constexpr int TRIPS = F8_MAX_L * (AC / 16) / 512;
   const u32x4* src = reinterpret_cast<const u32x4*>(a.x + (size_t)b * L * AC);
   const int npiece = L * (AC / 16);
   u32x4 tok[TRIPS];
@@ -304,11 +296,11 @@ __global__ __launch_bounds__(512) void attn_fp8_row_kernel(Fp8RowArgs a) {
   f32x4 acc4 = {0.f, 0.f, 0.f, 0.f};
   for (int i = wave; i < L; i += 8) {
     const float w = lg[i];
-    const f32x4 xv = cvt4_e4m3(reinterpret_cast<const unsigned*>(xs + (size_t)i * AC)[lane]);
+    const f32x4 xv = e4m3_dec4(reinterpret_cast<const unsigned*>(xs + (size_t)i * AC)[lane]);
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc4[j] = fmaf(w, xv[j], acc4[j]);
   }
-  reinterpret_cast<f32x4*>(&psum[wave][0])[lane] = acc4;
+  put_row(psum, wave, lane, acc4);
   __syncthreads();
   const float inv1 = 1.f / sm;
   if (tid < AC) {
@@ -319,7 +311,6 @@ __global__ __launch_bounds__(512) void attn_fp8_row_kernel(Fp8RowArgs a) {
 }
 
 // ----------------------------------------------------------------------------- backward (one workgroup per row)
-constexpr int F8_MAX_L = 224;   // 56 KB of LDS for the row's bytes
 struct Fp8BwdArgs {
   const float* qf;       // [B][256]
   const uint8_t* x;      // [B][L][256]
@@ -374,7 +365,7 @@ __global__ __launch_bounds__(256) void attn_fp8_bwd_kernel(Fp8BwdArgs a) {
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   for (int i = wave; i < a.L; i += 4) {
     const float g = dl[i];
-    const f32x4 xv = cvt4_e4m3(reinterpret_cast<const unsigned*>(xs + (size_t)i * AC)[lane]);
+    const f32x4 xv = e4m3_dec4(reinterpret_cast<const unsigned*>(xs + (size_t)i * AC)[lane]);
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[j] = fmaf(g, xv[j], acc[j]);
     if (a.dx) {
@@ -385,23 +376,24 @@ __global__ __launch_bounds__(256) void attn_fp8_bwd_kernel(Fp8BwdArgs a) {
       reinterpret_cast<f32x4*>(a.dx + ((size_t)b * a.L + i) * AC)[lane] = o;
     }
   }
-  reinterpret_cast<f32x4*>(&psum[wave][0])[lane] = acc;
+  put_row(psum, wave, lane, acc);
   __syncthreads();
-  a.dqf[(size_t)b * AC + tid] = (psum[0][tid] + psum[1][tid] + psum[2][tid] + psum[3][tid]) * xsc;
+  a.dqf[(size_t)b * AC + tid] = sum_rows<4>(psum, tid) * xsc;
 }
 
-// float32 -> e4m3 (round to nearest even, saturating at +-448), 4 values per thread; inverse scale from device memory
+// float32 -> e4m3 codes (e4m3_enc4), 4 values per thread: the caller's inverse scale, or the scale read from device memory
+__global__ __launch_bounds__(256) void quantize_e4m3_kernel(const float* __restrict__ x, int64_t n4, float inv_scale,
+                                                            unsigned* __restrict__ y) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n4) return;
+  y[i] = e4m3_enc4(reinterpret_cast<const f32x4*>(x)[i], inv_scale);
+}
 __global__ __launch_bounds__(256) void quantize_e4m3_dev_kernel(const float* __restrict__ x, int64_t n4, const float* __restrict__ scale,
                                                                 unsigned* __restrict__ y) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n4) return;
-  const float inv_scale = (float)(1.0 / (double)*scale);   // as the host quantiser: float32(1 / scale) from a float64 quotient
-  f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) v[j] = fminf(fmaxf(v[j] * inv_scale, -448.f), 448.f);
-  int w = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], 0, false);
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], w, true);
-  y[i] = (unsigned)w;
+  const float inv_scale = e4m3_inv_scale(*scale);
+  y[i] = e4m3_enc4(reinterpret_cast<const f32x4*>(x)[i], inv_scale);
 }
 
 }  // namespace
@@ -445,12 +437,12 @@ extern "C" int wsmg_attn_fp8_fwd(const float* q_folded, const uint8_t* x_e4m3, c
 
 extern "C" int wsmg_attn_fp8_row_fwd(const float* q, const float* w_k, const uint8_t* x_e4m3, const float* x_scale, const int* lengths,
                                      float scale, int B, int L, int C, float* q_folded, float* out, float* attn, wsmg_stream_t stream) {
-  if (C != AC || B <= 0 || L <= 0 || L > ROW_MAX_L || !q || !w_k || !x_e4m3 || !x_scale || !out || !attn) return WSMG_EINVAL;
+  if (C != AC || B <= 0 || L <= 0 || L > F8_MAX_L || !q || !w_k || !x_e4m3 || !x_scale || !out || !attn) return WSMG_EINVAL;
   Fp8RowArgs a{q, w_k, x_e4m3, x_scale, lengths, scale, L, q_folded, out, attn};
   static bool attr = false;
   if (!attr) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fp8_row_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       ROW_MAX_L * AC);
+                                       F8_MAX_L * AC);
     if (e != hipSuccess) return (int)e;
     attr = true;
   }
@@ -464,6 +456,14 @@ extern "C" int wsmg_attn_fp8_bwd(const float* q_folded, const uint8_t* x_e4m3, c
   if (C != AC || B <= 0 || L <= 0 || L > F8_MAX_L) return WSMG_EINVAL;
   Fp8BwdArgs a{q_folded, x_e4m3, x_scale, attn, dout, dattn, scale, L, dq_folded, dx};
   hipLaunchKernelGGL(attn_fp8_bwd_kernel, dim3((unsigned)B), dim3(256), (size_t)L * AC, wsmg_s(stream), a);
+  WSMG_RETURN_LAUNCH();
+}
+
+extern "C" int wsmg_quantize_e4m3(const float* x, int64_t n, float inv_scale, uint8_t* y, wsmg_stream_t stream) {
+  if (n <= 0 || (n & 3) != 0) return WSMG_EINVAL;
+  const int64_t n4 = n / 4;
+  hipLaunchKernelGGL(quantize_e4m3_kernel, dim3((unsigned)wsmg_cdiv(n4, 256)), dim3(256), 0, wsmg_s(stream), x, n4, inv_scale,
+                     reinterpret_cast<unsigned*>(y));
   WSMG_RETURN_LAUNCH();
 }
 

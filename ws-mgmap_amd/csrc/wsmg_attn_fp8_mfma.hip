@@ -19,12 +19,10 @@
 // exactly e4m3 numbers the result equals the reference's float32 `_attn` up to summation order — golden g5f.
 #include <stdio.h>
 
+#include "wsmg_attn_common.h"
 #include "wsmg_conv_tile.h"
 
 namespace {
-
-constexpr int AC = 256;          // channels
-constexpr int LMAX = 224;        // tokens per set at most (a multiple of 32; the reference pads instructions to 200)
 
 struct F8mArgs {
   const uint8_t* q;      // [B][256] e4m3
@@ -42,12 +40,8 @@ struct F8mArgs {
   float* attn;           // [B][L]
 };
 
-__device__ __forceinline__ float e4m3_to_f32(uint8_t c) {
-  return __builtin_amdgcn_cvt_f32_fp8((int)c, 0);
-}
-
 __global__ __launch_bounds__(256) void attn_fp8_mfma_fwd_kernel(F8mArgs a) {
-  __shared__ __attribute__((aligned(16))) float S[32][LMAX + 4];
+  __shared__ __attribute__((aligned(16))) float S[32][F8_MAX_L + 4];
   __shared__ __attribute__((aligned(16))) uint8_t V8[2][32][AC + 16];      // two chunks of 32 tokens x 256 value bytes (+16: rows 4 banks apart)
   __shared__ int rows[32];
   const int u = blockIdx.x, tile = blockIdx.y;
@@ -172,7 +166,7 @@ __global__ __launch_bounds__(256) void attn_fp8_mfma_fwd_kernel(F8mArgs a) {
         const int ch = 64 * wave + 32 * t + r;
         bf16x8 vb;
 #pragma unroll
-        for (int s = 0; s < 8; ++s) vb[s] = (short)f2bf_bits(e4m3_to_f32(V8[c & 1][16 * kk + 8 * h + s][ch]));   // exact: e4m3 has 4 significant bits
+        for (int s = 0; s < 8; ++s) vb[s] = e4m3_dec_bf(V8[c & 1][16 * kk + 8 * h + s][ch]);   // exact: e4m3 has 4 significant bits
         o[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(phi, vb, o[t], 0, 0, 0);
         o[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(plo, vb, o[t], 0, 0, 0);
       }
@@ -241,6 +235,10 @@ __global__ __launch_bounds__(256) void attn_fp8_amax_kernel(PrepArgs a) {
     if (v > 0.f || v != v) atomicMax(a.amax + threadIdx.x, v != v ? 0x7fc00000u : __float_as_uint(v));
   }
 }
+// a tensor's scale: the caller's (fixed > 0), or from its |x| maximum (NaN stays NaN)
+__device__ __forceinline__ float scale_of(float am, float fixed) {
+  return fixed > 0.f ? fixed : (am != am ? am : fmaxf(am * (1.0f / 448.0f), 1e-30f));
+}
 // prep 2: the three quantisations (scale = max(amax * float32(1 / 448), 1e-30) — the value `(x.abs().amax() / 448.0).clamp_min(1e-30)`
 // has in torch, which multiplies by the reciprocal of a scalar divisor — or the caller's; codes as wsmg_quantize_e4m3_dev makes them) and,
 // in one extra workgroup, the grouping of the rows by instruction set.
@@ -264,7 +262,7 @@ __global__ __launch_bounds__(256) void attn_fp8_quant_group_kernel(PrepArgs a, i
     for (int b = tid; b < a.B; b += 256) a.order[atomicAdd(&cnt[set_of(b)], 1)] = b;
     if (tid < 3) {
       const float am = __uint_as_float(a.amax[tid]);
-      a.scales[tid] = a.fixed[tid] > 0.f ? a.fixed[tid] : (am != am ? am : fmaxf(am * (1.0f / 448.0f), 1e-30f));
+      a.scales[tid] = scale_of(am, a.fixed[tid]);
     }
     return;
   }
@@ -274,14 +272,8 @@ __global__ __launch_bounds__(256) void attn_fp8_quant_group_kernel(PrepArgs a, i
   const int t = i < a.n4[0] ? 0 : i < a.n4[0] + a.n4[1] ? 1 : 2;
   const int64_t k = i - (t == 0 ? 0 : t == 1 ? a.n4[0] : a.n4[0] + a.n4[1]);
   const float am = __uint_as_float(a.amax[t]);
-  const float sc = a.fixed[t] > 0.f ? a.fixed[t] : (am != am ? am : fmaxf(am * (1.0f / 448.0f), 1e-30f));
-  const float inv_scale = (float)(1.0 / (double)sc);
-  f32x4 v = reinterpret_cast<const f32x4*>(a.x[t])[k];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) v[j] = fminf(fmaxf(v[j] * inv_scale, -448.f), 448.f);
-  int w = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], 0, false);
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], w, true);
-  reinterpret_cast<unsigned*>(a.codes[t])[k] = (unsigned)w;
+  const float sc = scale_of(am, a.fixed[t]);
+  reinterpret_cast<unsigned*>(a.codes[t])[k] = e4m3_enc4(reinterpret_cast<const f32x4*>(a.x[t])[k], e4m3_inv_scale(sc));
 }
 
 // ---- round 5: the whole operator in ONE launch (it was |x| maxima + quantise / group + this kernel = 36 us at
@@ -314,32 +306,6 @@ struct F8fArgs {
   float* trace;            // diagnostic build (`tracing` in the launcher): microseconds since the start of workgroup 0 at its phase boundaries
 };
 
-__device__ __forceinline__ long quant8(const float* p, float inv_scale) {
-  const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
-  float x[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-#pragma unroll
-  for (int j = 0; j < 8; ++j) x[j] = fminf(fmaxf(x[j] * inv_scale, -448.f), 448.f);
-  int w0 = __builtin_amdgcn_cvt_pk_fp8_f32(x[0], x[1], 0, false);
-  w0 = __builtin_amdgcn_cvt_pk_fp8_f32(x[2], x[3], w0, true);
-  int w1 = __builtin_amdgcn_cvt_pk_fp8_f32(x[4], x[5], 0, false);
-  w1 = __builtin_amdgcn_cvt_pk_fp8_f32(x[6], x[7], w1, true);
-  return (long)(((unsigned long)(unsigned)w1 << 32) | (unsigned long)(unsigned)w0);
-}
-__device__ __forceinline__ float scale_of(float am, float fixed) {
-  return fixed > 0.f ? fixed : (am != am ? am : fmaxf(am * (1.0f / 448.0f), 1e-30f));
-}
-
-// quantiser's expression on 8 values already in registers (the codes wsmg_attn_fp8_prep writes)
-__device__ __forceinline__ long quant8r(const f32x4 a, const f32x4 b, float inv_scale) {
-  float x[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-#pragma unroll
-  for (int j = 0; j < 8; ++j) x[j] = fminf(fmaxf(x[j] * inv_scale, -448.f), 448.f);
-  int w0 = __builtin_amdgcn_cvt_pk_fp8_f32(x[0], x[1], 0, false);
-  w0 = __builtin_amdgcn_cvt_pk_fp8_f32(x[2], x[3], w0, true);
-  int w1 = __builtin_amdgcn_cvt_pk_fp8_f32(x[4], x[5], 0, false);
-  w1 = __builtin_amdgcn_cvt_pk_fp8_f32(x[6], x[7], w1, true);
-  return (long)(((unsigned long)(unsigned)w1 << 32) | (unsigned long)(unsigned)w0);
-}
 
 // Order inside an attention workgroup (second form of this kernel; the first — maxima, barrier, then every operand loaded and
 // quantised where it was needed — took 32 us at B = 64, as long as the three launches it replaced: the value chunks alone were five
@@ -348,13 +314,13 @@ __device__ __forceinline__ long quant8r(const f32x4 a, const f32x4 b, float inv_
 // wave per SIMD has 512), then the maxima pass and the grid barrier run while those loads are in flight; after the barrier the
 // registers are quantised (queries to MFMA operands, values to the LDS image of all chunks at once) and only the keys are loaded
 // behind it.  The arithmetic per element is unchanged.
-constexpr int NCHMAX = LMAX / 32;      // 7 value chunks of 32 tokens at most
+constexpr int NCHMAX = F8_MAX_L / 32;      // 7 value chunks of 32 tokens at most
 
 __global__ __launch_bounds__(256) void attn_fp8_mfma_fused_kernel(F8fArgs a) {
   // (dynamic: 29 KB of logits + 60 KB of value codes are more than the 64 KB a kernel may declare statically without an attribute)
   extern __shared__ __attribute__((aligned(16))) unsigned char fused_lds[];
-  float (*S)[LMAX + 4] = reinterpret_cast<float (*)[LMAX + 4]>(fused_lds);
-  uint8_t (*V8)[32][AC + 16] = reinterpret_cast<uint8_t (*)[32][AC + 16]>(fused_lds + 32 * (LMAX + 4) * 4);
+  float (*S)[F8_MAX_L + 4] = reinterpret_cast<float (*)[F8_MAX_L + 4]>(fused_lds);
+  uint8_t (*V8)[32][AC + 16] = reinterpret_cast<uint8_t (*)[32][AC + 16]>(fused_lds + 32 * (F8_MAX_L + 4) * 4);
   __shared__ int rows[32];
   __shared__ int wtot[4];
   __shared__ float wm[4][3];
@@ -508,13 +474,13 @@ __global__ __launch_bounds__(256) void attn_fp8_mfma_fused_kernel(F8fArgs a) {
   if (!active) return;
   stamp(3);
   const float sq = sc3[0], sk = sc3[1], sv = sc3[2];
-  const float iq = (float)(1.0 / (double)sq), ik = (float)(1.0 / (double)sk), iv = (float)(1.0 / (double)sv);
+  const float iq = e4m3_inv_scale(sq), ik = e4m3_inv_scale(sk), iv = e4m3_inv_scale(sv);
   const int len = a.lengths ? a.lengths[u] : a.L;
 
   // ---- quantise what is in registers: the queries to MFMA operands, the values to the LDS image of all chunks
   long qa[16];
 #pragma unroll
-  for (int ks = 0; ks < 16; ++ks) qa[ks] = my_row < 0 ? 0l : quant8r(qraw[ks][0], qraw[ks][1], iq);
+  for (int ks = 0; ks < 16; ++ks) qa[ks] = my_row < 0 ? 0l : e4m3_enc8(qraw[ks][0], qraw[ks][1], iq);
 #pragma unroll
   for (int c = 0; c < NCHMAX; ++c) {
     if (c < nchunk) {
@@ -525,7 +491,7 @@ __global__ __launch_bounds__(256) void attn_fp8_mfma_fused_kernel(F8fArgs a) {
         const int l = 32 * c + tk;
         u32x4 val = {0u, 0u, 0u, 0u};
         if (l < a.L) {
-          const long lo = quant8r(vraw[c][half][0], vraw[c][half][1], iv), hi = quant8r(vraw[c][half][2], vraw[c][half][3], iv);
+          const long lo = e4m3_enc8(vraw[c][half][0], vraw[c][half][1], iv), hi = e4m3_enc8(vraw[c][half][2], vraw[c][half][3], iv);
           val[0] = (unsigned)(lo & 0xffffffffl); val[1] = (unsigned)((unsigned long)lo >> 32);
           val[2] = (unsigned)(hi & 0xffffffffl); val[3] = (unsigned)((unsigned long)hi >> 32);
         }
@@ -546,7 +512,7 @@ __global__ __launch_bounds__(256) void attn_fp8_mfma_fused_kernel(F8fArgs a) {
       for (int g = 0; g < 16; ++g) acc4[c][g] = 0.f;
     long kb[16];
 #pragma unroll
-    for (int ks = 0; ks < 16; ++ks) kb[ks] = tok < a.L ? quant8(kp + 16 * ks, ik) : 0l;
+    for (int ks = 0; ks < 16; ++ks) kb[ks] = tok < a.L ? e4m3_enc8(kp + 16 * ks, ik) : 0l;
 #pragma unroll
     for (int ks = 0; ks < 16; ++ks) acc4[ks >> 2] = __builtin_amdgcn_mfma_f32_32x32x16_fp8_fp8(qa[ks], kb[ks], acc4[ks >> 2], 0, 0, 0);
     f32x16 acc;
@@ -614,7 +580,7 @@ __global__ __launch_bounds__(256) void attn_fp8_mfma_fused_kernel(F8fArgs a) {
         const int ch = 64 * wave + 32 * t + r;
         bf16x8 vb;
 #pragma unroll
-        for (int s_ = 0; s_ < 8; ++s_) vb[s_] = (short)f2bf_bits(e4m3_to_f32(V8[c][16 * kk + 8 * h + s_][ch]));
+        for (int s_ = 0; s_ < 8; ++s_) vb[s_] = e4m3_dec_bf(V8[c][16 * kk + 8 * h + s_][ch]);
         o[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(phi, vb, o[t], 0, 0, 0);
         o[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(plo, vb, o[t], 0, 0, 0);
       }
@@ -664,7 +630,7 @@ extern "C" int wsmg_attn_fp8_mfma_fwd(const uint8_t* q_codes, const float* q_sca
                                       const int* set_start, float scale, int B, int U, int L, int C, float* out, float* attn,
                                       wsmg_stream_t stream) {
   if (!q_codes || !q_scale || !k_codes || !k_scale || !v_codes || !v_scale || !row_ids || !set_start || !out || !attn) return WSMG_EINVAL;
-  if (B <= 0 || U <= 0 || L <= 0 || L > LMAX || C != AC) return WSMG_EINVAL;
+  if (B <= 0 || U <= 0 || L <= 0 || L > F8_MAX_L || C != AC) return WSMG_EINVAL;
   F8mArgs a{q_codes, k_codes, v_codes, q_scale, k_scale, v_scale, lengths, row_ids, set_start, scale, B, U, L, out, attn};
   hipLaunchKernelGGL(attn_fp8_mfma_fwd_kernel, dim3((unsigned)U, (unsigned)wsmg_cdiv(B, 32)), dim3(256), 0, wsmg_s(stream), a);
   WSMG_RETURN_LAUNCH();
@@ -679,7 +645,7 @@ extern "C" int wsmg_attn_fp8_mfma_fused(const float* q, const float* k_sets, con
                                         unsigned* workspace, unsigned arrivals_before, int epoch, float* scales_out, float* out, float* attn,
                                         wsmg_stream_t stream) {
   if (!q || !k_sets || !v_sets || !inverse || !workspace || !out || !attn) return WSMG_EINVAL;
-  if (B <= 0 || U <= 0 || U > 1024 || L <= 0 || L > LMAX || C != AC) return WSMG_EINVAL;
+  if (B <= 0 || U <= 0 || U > 1024 || L <= 0 || L > F8_MAX_L || C != AC) return WSMG_EINVAL;
   const int tiles = (int)wsmg_cdiv(B, 32);
   const int64_t nmain = (int64_t)U * tiles;
   const int need = !(q_scale > 0.f && k_scale > 0.f && v_scale > 0.f);
@@ -705,7 +671,7 @@ extern "C" int wsmg_attn_fp8_mfma_fused(const float* q, const float* k_sets, con
   constexpr bool tracing = false;   // diagnostic build: true = phase stamps on stderr (synchronises)
   if (tracing && !trace_dev && hipMalloc((void**)&trace_dev, 16 * sizeof(float)) != hipSuccess) trace_dev = nullptr;
   a.trace = tracing ? trace_dev : nullptr;
-  constexpr int FUSED_LDS = 32 * (LMAX + 4) * 4 + NCHMAX * 32 * (AC + 16);
+  constexpr int FUSED_LDS = 32 * (F8_MAX_L + 4) * 4 + NCHMAX * 32 * (AC + 16);
   static bool attr = false;
   if (!attr) {
     hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fp8_mfma_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, FUSED_LDS);
@@ -726,7 +692,7 @@ extern "C" int wsmg_attn_fp8_mfma_fused(const float* q, const float* k_sets, con
 /* workgroups wsmg_attn_fp8_mfma_fused launches for this shape when it has to take the maxima itself (= the arrivals one launch adds
  * to its workspace's counter); 0 when it would refuse the shape */
 extern "C" int wsmg_attn_fp8_mfma_fused_arrivals(int B, int U, int L, int C) {
-  if (B <= 0 || U <= 0 || U > 1024 || L <= 0 || L > LMAX || C != AC) return 0;
+  if (B <= 0 || U <= 0 || U > 1024 || L <= 0 || L > F8_MAX_L || C != AC) return 0;
   const int64_t nmain = (int64_t)U * wsmg_cdiv(B, 32);
   if (nmain > fused_main_limit()) return 0;
   const int64_t tot4 = ((int64_t)B * C + 2ll * U * L * C) / 4;

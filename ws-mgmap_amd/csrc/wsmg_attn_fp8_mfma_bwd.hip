@@ -18,12 +18,10 @@
 //                partial blocks.  A set no row uses gets zeros; tokens at or past lengths[u] have p = 0 exactly, hence dl = 0 and zero
 //                gradient rows; rows past the end of a partial chunk are staged as zeros.
 // No [B][L][256] or [U][B][L] tensor exists.
+#include "wsmg_attn_common.h"
 #include "wsmg_conv_tile.h"
 
 namespace {
-
-constexpr int AC = 256;          // channels
-constexpr int LMAX = 224;        // tokens per set at most (the forward's limit)
 
 struct F8bArgs {
   const uint8_t* q;        // [B][256] e4m3
@@ -46,9 +44,6 @@ struct F8bArgs {
   float* dl;               // [B][L] scratch: d logits
 };
 
-__device__ __forceinline__ short e4m3_to_bf(uint8_t c) {      // exact: e4m3 has 4 significant bits
-  return (short)f2bf_bits(__builtin_amdgcn_cvt_f32_fp8((int)c, 0));
-}
 __device__ __forceinline__ void split8(const float (&x)[8], bf16x8& hi, bf16x8& lo) {
 #pragma unroll
   for (int s = 0; s < 8; ++s) {
@@ -57,25 +52,10 @@ __device__ __forceinline__ void split8(const float (&x)[8], bf16x8& hi, bf16x8& 
     lo[s] = (short)f2bf_bits(x[s] - bf2f(h));
   }
 }
-// 8 consecutive e4m3 bytes -> 8 bf16 numbers
-__device__ __forceinline__ bf16x8 codes8_to_bf(long w) {
-  const int w0 = (int)(w & 0xffffffffl), w1 = (int)((unsigned long)w >> 32);
-  bf16x8 o;
-  o[0] = (short)f2bf_bits(__builtin_amdgcn_cvt_f32_fp8(w0, 0));
-  o[1] = (short)f2bf_bits(__builtin_amdgcn_cvt_f32_fp8(w0, 1));
-  o[2] = (short)f2bf_bits(__builtin_amdgcn_cvt_f32_fp8(w0, 2));
-  o[3] = (short)f2bf_bits(__builtin_amdgcn_cvt_f32_fp8(w0, 3));
-  o[4] = (short)f2bf_bits(__builtin_amdgcn_cvt_f32_fp8(w1, 0));
-  o[5] = (short)f2bf_bits(__builtin_amdgcn_cvt_f32_fp8(w1, 1));
-  o[6] = (short)f2bf_bits(__builtin_amdgcn_cvt_f32_fp8(w1, 2));
-  o[7] = (short)f2bf_bits(__builtin_amdgcn_cvt_f32_fp8(w1, 3));
-  return o;
-}
-
 // MFMA 32x32x16 operand layout, as the forward uses it: A lane (r, h) = row r, k = 8 h .. 8 h + 7; B lane (r, h) = column r, k likewise;
 // D lane (r = column, h), register g -> row (g & 3) + 8 (g >> 2) + 4 h.
 __global__ __launch_bounds__(256) void attn_fp8_mfma_bwd_rows_kernel(F8bArgs a) {
-  __shared__ __attribute__((aligned(16))) float S[32][LMAX + 4];
+  __shared__ __attribute__((aligned(16))) float S[32][F8_MAX_L + 4];
   __shared__ __attribute__((aligned(16))) uint8_t K8[2][32][AC + 16];      // two chunks of 32 tokens x 256 key bytes
   __shared__ int rows[32];
   const int u = blockIdx.x, tile = blockIdx.y;
@@ -115,7 +95,7 @@ __global__ __launch_bounds__(256) void attn_fp8_mfma_bwd_rows_kernel(F8bArgs a) 
       for (int g = 0; g < 16; ++g) { acc_hi[g] = 0.f; acc_lo[g] = 0.f; }
 #pragma unroll
       for (int ks = 0; ks < 16; ++ks) {
-        const bf16x8 vb = codes8_to_bf(vb8[ks]);
+        const bf16x8 vb = e4m3_dec8_bf(vb8[ks]);
         acc_hi = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ahi[ks], vb, acc_hi, 0, 0, 0);
         acc_lo = __builtin_amdgcn_mfma_f32_32x32x16_bf16(alo[ks], vb, acc_lo, 0, 0, 0);
       }
@@ -194,7 +174,7 @@ __global__ __launch_bounds__(256) void attn_fp8_mfma_bwd_rows_kernel(F8bArgs a) 
         const int ch = 64 * wave + 32 * t + r;
         bf16x8 kb;
 #pragma unroll
-        for (int s = 0; s < 8; ++s) kb[s] = e4m3_to_bf(K8[c & 1][16 * kk + 8 * h + s][ch]);
+        for (int s = 0; s < 8; ++s) kb[s] = e4m3_dec_bf(K8[c & 1][16 * kk + 8 * h + s][ch]);
         o[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dhi, kb, o[t], 0, 0, 0);
         o[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dlo, kb, o[t], 0, 0, 0);
       }
@@ -276,7 +256,7 @@ __global__ __launch_bounds__(256) void attn_fp8_mfma_bwd_sets_kernel(F8bArgs a) 
         const int ch = 64 * wave + 32 * t + r;
         bf16x8 qb, ghi, glo;
 #pragma unroll
-        for (int s = 0; s < 8; ++s) qb[s] = e4m3_to_bf(Q8[16 * kk + 8 * h + s][ch]);
+        for (int s = 0; s < 8; ++s) qb[s] = e4m3_dec_bf(Q8[16 * kk + 8 * h + s][ch]);
         dk[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dhi, qb, dk[t], 0, 0, 0);
         dk[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dlo, qb, dk[t], 0, 0, 0);
 #pragma unroll
@@ -342,7 +322,7 @@ extern "C" int wsmg_attn_fp8_mfma_bwd(const uint8_t* q_codes, const float* q_sca
   if (!q_codes || !q_scale || !k_codes || !k_scale || !v_codes || !v_scale || !row_ids || !set_start || !inverse || !attn)
     return WSMG_EINVAL;
   if (!dq || !dk || !dv || !dl_scratch) return WSMG_EINVAL;
-  if (B <= 0 || U <= 0 || U > 1024 || L <= 0 || L > LMAX || C != AC) return WSMG_EINVAL;
+  if (B <= 0 || U <= 0 || U > 1024 || L <= 0 || L > F8_MAX_L || C != AC) return WSMG_EINVAL;
   F8bArgs a{q_codes, k_codes, v_codes, q_scale, k_scale, v_scale, row_ids, set_start, inverse, attn, dout, dattn, scale, B, U, L,
             dq, dk, dv, dl_scratch};
   hipLaunchKernelGGL(attn_fp8_mfma_bwd_rows_kernel, dim3((unsigned)U, (unsigned)wsmg_cdiv(B, 32)), dim3(256), 0, wsmg_s(stream), a);

@@ -98,6 +98,14 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
   __syncthreads();
   return red[0] + red[1] + red[2] + red[3];
 }
+// the maximum over the same workgroup, the float block_sum's way (same red, same waits)
+__device__ __forceinline__ float block_max(float v, float* red) {
+  v = wave_max(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return fmaxf(fmaxf(fmaxf(red[0], red[1]), red[2]), red[3]);
+}
 __device__ __forceinline__ double block_sum_d(double v, double* red) {
   v = wave_sum_d(v);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
