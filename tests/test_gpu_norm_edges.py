@@ -4,23 +4,24 @@ own of test_gpu_kernels.py::test_bn_act_train / test_bn_act_bf16, not widened fo
 measured error over its bar; the module prints the worst ratio per section, type and output at its end (profiles/norm_edges.txt).
 
 Section, what it pins, and what held it before:
-a. reduction edges   col_reduce_kernel<1 | 2>, bn_stats_finalize_kernel, bn_bwd_finalize_kernel, the apply kernels, forward + backward
+a. reduction edges   col_reduce_kernel<1 | 2>, bn_stats_finalize_kernel, sum_finalize_kernel<true>, the apply kernels, forward + backward
                      at 2 ... rpi + 1 ... 8 rpi + 1 rows, at 63 ... 257 blocks (both loops of reduce_partials), at the cap of 1024
                      blocks, one row past it and two rounds past it; C = 256 everywhere, C = 32 and 512 at 65 / 193 blocks and the cap
                      — test_bn_act_train / test_bn_act_bf16: at most 59 blocks, C <= 256
 b. mode matrix       {f32, bf16} x {residual} x {ReLU} at every C of chan_ok, train forward + backward; eval forward, its untouched
                      running statistics and its refused backward — bf16 without ReLU and residual without ReLU had no test
 c. strided dy        wsmg_bn_act_bwd_ld[_bf16]: dy a channel slice of a wider tensor read in place (ops.core._rows_of), the
-                     misaligned slice through its copy, the refusals of the entry point itself — whole-policy tests only
+                     misaligned slice through its copy, the refusals of the entry point itself — whole-policy tests only;
+                     wsmg_bn_act_bwd[_bf16] (the same with ld = C, no longer on the ops route) directly
 d. dx_lo             wsmg_bn_act_bwd_ld_bf16_lo through ops.GradLoSink — whole-policy tests only
 e. slabs             wsmg_bn_act_fwd_bf16_pre at 1 ... 257 slabs (the model uses 8 and 64), wsmg_bn_stats_finalize +
                      wsmg_bn_bwd_apply_bf16 directly, in place too — the classifier tail's C = 32 only
-f. channel sums      wsmg_channel_sum[_bf16] (col_reduce_kernel<0>, sum_finalize_kernel) at every C — no direct test
+f. channel sums      wsmg_channel_sum[_bf16] (col_reduce_kernel<0>, sum_finalize_kernel<false>) at every C — no direct test
 g. refusals          unsupported C, rows = 0: WSMG_EINVAL; a workspace one byte short: WSMG_ENOMEM; nothing written
 h. GroupNorm         group_norm_nhwc_bf16_kernel<float | bf16> at groups of 1, 3, 5 ... elements, fewer than 256, no multiple of 256,
                      C / G no power of two, H W = 1 — G = 16 on the backbone's shapes and one G = 1 case
 
-NOT reached on purpose: the cap of 4096 blocks of stream_grid / stream_grid8 (the apply kernels' grid).  It needs 16.7 M float32 /
+NOT reached on purpose: the cap of 4096 blocks of stream_grid (the apply kernels' grid).  It needs 16.7 M float32 /
 33.5 M bf16 elements, and it only changes the stride of a grid-stride loop that every case here already walks four or more times per
 thread.  The largest case is 32 775 x 512 = 16.8 M elements (section a, "beyond" at C = 512)."""
 import ctypes
@@ -213,9 +214,10 @@ def test_bn_backward_copies_a_misaligned_slice(ops, monkeypatch, res):
     B, H, W = nc.STRIDED_SHAPE
     c = dict(nc.bn_case(C, B * H * W, True, res, True), shape=(B, H, W))
     called, real = [], _abi.call
-    monkeypatch.setattr(_abi, "call", lambda name, *a: (called.append(name), real(name, *a))[1])
+    monkeypatch.setattr(_abi, "call", lambda name, *a: (called.append((name, a[1] if len(a) > 1 else None)), real(name, *a))[1])
     out = run_bn(ops, c, True, res, True, wide=(Ctot, c0), copy_expected=True)
-    assert "wsmg_bn_act_bwd_bf16" in called and "wsmg_bn_act_bwd_ld_bf16" not in called, called
+    strides = [ld for name, ld in called if name == "wsmg_bn_act_bwd_ld_bf16"]     # the one backward entry point, told the copy's stride
+    assert strides == [C] and not any(name.startswith("wsmg_bn_act_bwd") and name != "wsmg_bn_act_bwd_ld_bf16" for name, _ in called), called
     check_bn(f"c.misaligned.{'res_relu' if res else 'relu'}.bf16", "c", c, True, res, out)
 
 
@@ -318,6 +320,29 @@ def test_bn_stats_finalize_and_backward_apply_direct(C):
     assert lib().wsmg_bn_bwd_apply_bf16(P(inplace), *args, P(inplace), S()) == 0
     torch.cuda.synchronize()
     assert torch.equal(inplace, dx), "dx == dy must give the out-of-place result"
+
+
+@pytest.mark.parametrize("bf16", [False, True], ids=DT_IDS)
+def test_bn_backward_without_a_stride_direct(ops, bf16):
+    """wsmg_bn_act_bwd[_bf16], which ops.bn_act no longer calls (it hands wsmg_bn_act_bwd_ld its stride, C for a contiguous dy): the
+    entry point itself after wsmg_bn_act_fwd[_bf16], residual + ReLU, against the reference and bars of the ops route (check_bn)."""
+    C = 64
+    B, H, W = nc.MODE_SHAPES[C]
+    rows = B * H * W
+    c = dict(nc.bn_case(C, rows, bf16, True, True), shape=(B, H, W))
+    dt = torch.bfloat16 if bf16 else torch.float32
+    x, r, dy = c["x"].to(dt).cuda(), c["res"].to(dt).cuda(), c["dy"].to(dt).cuda()
+    gamma, beta, rm, rv = c["gamma"].cuda(), c["beta"].cuda(), c["rm"].cuda(), c["rv"].cuda()
+    y, dx, dres = (torch.full((rows, C), NAN, dtype=dt, device="cuda") for _ in range(3))
+    mean, invstd, dg, db = _nan(C), _nan(C), _nan(C), _nan(C)
+    need = int(lib().wsmg_channel_reduce_workspace_bytes(rows, C))
+    ws = torch.empty(need // 8, dtype=torch.float64, device="cuda")
+    assert getattr(lib(), "wsmg_bn_act_fwd" + sfx(bf16))(P(x), P(r), P(gamma), P(beta), P(rm), P(rv), nc.MOMENTUM, nc.EPS, 1, 1, rows, C, P(y),
+                                                         P(mean), P(invstd), P(ws), need, S()) == 0
+    assert getattr(lib(), "wsmg_bn_act_bwd" + sfx(bf16))(P(dy), P(x), P(y), P(gamma), P(beta), P(mean), P(invstd), 1, rows, C, P(dx), P(dres),
+                                                         P(dg), P(db), P(ws), need, S()) == 0
+    torch.cuda.synchronize()
+    check_bn(f"c.direct.C{C}.{DT_IDS[bf16]}", "c", c, bf16, True, dict(y=y, dx=dx, dgamma=dg, dbeta=db, dres=dres, rm=rm, rv=rv))
 
 
 # ----------------------------------------------------------------------------- f. channel sums

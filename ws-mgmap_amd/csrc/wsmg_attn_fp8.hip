@@ -24,8 +24,6 @@
 
 namespace {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 // ----------------------------------------------------------------------------- fold: out[B][256] = in[B][256] @ W  (or W^T)
 // W [256][256] row-major (Conv1d weight [C_out][C_in]).  transpose = 0: out[b][j] = sum_o in[b][o] W[o][j]   (q_f = q W_k);
 // transpose = 1: out[b][o] = sum_j in[b][j] W[o][j]   (dq = d q_f W_k^T).  One workgroup = 16 rows x 64 columns, one wave =

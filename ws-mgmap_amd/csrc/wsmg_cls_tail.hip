@@ -34,13 +34,7 @@ constexpr int PITCH = 80;       // LDS tile pitch (bytes): 64 + 16
 constexpr int TILE = 32 * PITCH;
 constexpr int WAVES = 8;
 
-__device__ __forceinline__ void unpack8(const u32x4 v, float (&o)[8]) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    o[2 * j] = __uint_as_float(v[j] << 16);
-    o[2 * j + 1] = __uint_as_float(v[j] & 0xffff0000u);
-  }
-}
+// eight float32 as one bf16 MFMA operand (16 bytes of bf16 as eight float32, the other way: wsmg_common.h's chans_f32<8>)
 __device__ __forceinline__ bf16x8 pack8(const float (&v)[8]) {
   bf16x8 o;
 #pragma unroll
@@ -92,7 +86,7 @@ __device__ __forceinline__ void act_frags(const u32x4 (&raw)[2], const float (*c
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks) {
     float v[8];
-    unpack8(raw[ks], v);
+    chans_f32<8>(raw[ks], v);
     const int k0 = 16 * ks + 8 * h;
     const f32x4 s0 = *reinterpret_cast<const f32x4*>(&cst[0][k0]), s1 = *reinterpret_cast<const f32x4*>(&cst[0][k0 + 4]);
     const f32x4 t0 = *reinterpret_cast<const f32x4*>(&cst[1][k0]), t1 = *reinterpret_cast<const f32x4*>(&cst[1][k0 + 4]);

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "wsmgmap.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -36,6 +38,46 @@ __device__ __forceinline__ void st4(bf16_t* p, f32x4 v) {
     u[j] = __builtin_bit_cast(unsigned short, b);
   }
   *reinterpret_cast<u16x4*>(p) = u;
+}
+
+// N consecutive channels of a row: N = 4 (float32, or bf16 through ld4 / st4) or N = 8 (bf16 only, one 16-byte access).  chans_t is
+// what the load returns (a kernel that keeps several loads in flight holds them in this form), chans_f32 its N float32 values; the
+// store rounds each value to T once.
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));   // four 32-bit words
+template <int N> using chans_t = typename std::conditional<N == 8, u32x4, f32x4>::type;
+template <int N, class T>
+__device__ __forceinline__ chans_t<N> ld_chans_raw(const T* p) {
+  if constexpr (N == 8) return *reinterpret_cast<const u32x4*>(p);
+  else return ld4(p);
+}
+template <int N>
+__device__ __forceinline__ void chans_f32(chans_t<N> d, float (&o)[N]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if constexpr (N == 8) {
+      o[2 * j] = __uint_as_float(d[j] << 16);
+      o[2 * j + 1] = __uint_as_float(d[j] & 0xffff0000u);
+    } else {
+      o[j] = d[j];
+    }
+  }
+}
+template <int N, class T>
+__device__ __forceinline__ void ld_chans(const T* p, float (&o)[N]) { chans_f32<N>(ld_chans_raw<N>(p), o); }
+template <int N, class T>
+__device__ __forceinline__ void st_chans(T* p, const float (&g)[N]) {
+  if constexpr (N == 8) {
+    u32x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const bf16_t lo = (bf16_t)g[2 * j], hi = (bf16_t)g[2 * j + 1];
+      o[j] = (unsigned)__builtin_bit_cast(unsigned short, lo) | ((unsigned)__builtin_bit_cast(unsigned short, hi) << 16);
+    }
+    *reinterpret_cast<u32x4*>(p) = o;
+  } else {
+    const f32x4 o = {g[0], g[1], g[2], g[3]};
+    st4(p, o);
+  }
 }
 
 // after a kernel launch: report launch-time errors through the C ABI's int return

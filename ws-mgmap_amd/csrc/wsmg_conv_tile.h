@@ -6,7 +6,6 @@
 
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef short bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ unsigned short f2bf_bits(float f) {   // round to nearest even
   bf16_t b = (bf16_t)f;

@@ -13,8 +13,6 @@ namespace {
 #define GRID_STRIDE(i, n) \
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
 
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-
 template <class T>
 __global__ void relu_fwd_kernel(const T* x, T* y, int64_t n4) {
   GRID_STRIDE(i, n4) {
@@ -176,40 +174,13 @@ __global__ void upsample_fwd_kernel(const T* x, T* y, int B, int H, int W, int C
   }
 }
 
-// N consecutive channels of a pixel as loaded — 16 bytes for 4 float32 or 8 bf16, 8 bytes for 4 bf16 — and what the backward
-// below does with them: load, g += w * channels, store
-template <int N> using chans_t = typename std::conditional<N == 8, u32x4_t, f32x4>::type;
-template <int N, class T>
-__device__ __forceinline__ chans_t<N> ld_chans(const T* p) {
-  if constexpr (N == 8) return *reinterpret_cast<const u32x4_t*>(p);
-  else return ld4(p);
-}
+// g += w * (N consecutive channels of a pixel as loaded: wsmg_common.h's chans_t)
 template <int N>
 __device__ __forceinline__ void fma_chans(float (&g)[N], float w, chans_t<N> d) {
+  float v[N];
+  chans_f32<N>(d, v);
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    if constexpr (N == 8) {
-      g[2 * j] += w * __uint_as_float(d[j] << 16);
-      g[2 * j + 1] += w * __uint_as_float(d[j] & 0xffff0000u);
-    } else {
-      g[j] += w * d[j];
-    }
-  }
-}
-template <int N, class T>
-__device__ __forceinline__ void st_chans(T* p, const float (&g)[N]) {
-  if constexpr (N == 8) {
-    u32x4_t o;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const bf16_t lo = (bf16_t)g[2 * j], hi = (bf16_t)g[2 * j + 1];
-      o[j] = (unsigned)__builtin_bit_cast(unsigned short, lo) | ((unsigned)__builtin_bit_cast(unsigned short, hi) << 16);
-    }
-    *reinterpret_cast<u32x4_t*>(p) = o;
-  } else {
-    const f32x4 o = {g[0], g[1], g[2], g[3]};
-    st4(p, o);
-  }
+  for (int j = 0; j < N; ++j) g[j] += w * v[j];
 }
 
 // The upsample's backward as a gather, N = 4 or 8 channels per thread (8: bf16 only, one 16-byte access): dx[iy][ix] = the sum over the
@@ -262,7 +233,7 @@ __global__ __launch_bounds__(256) void upsample_bwdn_kernel(const T* __restrict_
       chans_t<N> d[6];
 #pragma unroll
       for (int e = 0; e < 6; ++e)
-        if (e < nx) d[e] = ld_chans<N>(base + ((size_t)oys[a] * OW + oxs[e]) * ld_dy);
+        if (e < nx) d[e] = ld_chans_raw<N>(base + ((size_t)oys[a] * OW + oxs[e]) * ld_dy);
 #pragma unroll
       for (int e = 0; e < 6; ++e) {
         if (e >= nx) break;
@@ -303,7 +274,7 @@ __global__ void avgpool_bwd_kernel(const T* dy, T* dx, int B, int H, int W, int 
 
 // ---- channel concatenation of two NHWC tensors (the UNet skip connections, map_encoder.py:104,110, and
 // mg_map_policy.py:99): out[p] = a[p] ++ b[p], one 16-byte chunk per thread, the pixel index computed once per chunk
-__global__ void cat_channels_kernel(const u32x4_t* __restrict__ a, const u32x4_t* __restrict__ b, u32x4_t* __restrict__ y,
+__global__ void cat_channels_kernel(const u32x4* __restrict__ a, const u32x4* __restrict__ b, u32x4* __restrict__ y,
                                     int64_t rows, int ca, int cb) {
   const int cy = ca + cb;
   const int64_t n = rows * cy;
@@ -317,7 +288,7 @@ __global__ void cat_channels_kernel(const u32x4_t* __restrict__ a, const u32x4_t
 // Rollout route of the UNet decoders (unet_encoder.py:95-109, map_encoder.py:103-110): cat([upsample2x(a), b], channels) in one
 // pass, bf16 — the upsampled tensor is never written (and read back by the concatenation); 8 channels per thread, the
 // interpolation arithmetic of upsample_fwd_kernel.
-__global__ void upsample_cat_bf16_kernel(const bf16_t* __restrict__ a, const u32x4_t* __restrict__ b, u32x4_t* __restrict__ y, int B,
+__global__ void upsample_cat_bf16_kernel(const bf16_t* __restrict__ a, const u32x4* __restrict__ b, u32x4* __restrict__ y, int B,
                                          int H, int W, int ca8, int cb8) {
   const int OH = 2 * H, OW = 2 * W, cy = ca8 + cb8, C = ca8 * 8;
   const float sh = OH > 1 ? (float)(H - 1) / (float)(OH - 1) : 0.f;
@@ -338,7 +309,7 @@ __global__ void upsample_cat_bf16_kernel(const bf16_t* __restrict__ a, const u32
     up_src(oy, H, sh, y0, y1, hy0, hy1);
     up_src(ox, W, sw, x0, x1, wx0, wx1);
     const bf16_t* xb = a + (size_t)bb * H * W * C + c * 8;
-    u32x4_t o;
+    u32x4 o;
 #pragma unroll
     for (int hlf = 0; hlf < 2; ++hlf) {
       const f32x4 v00 = ld4(xb + ((size_t)y0 * W + x0) * C + 4 * hlf), v01 = ld4(xb + ((size_t)y0 * W + x1) * C + 4 * hlf);
@@ -374,36 +345,36 @@ __device__ __forceinline__ unsigned add3_2(unsigned a, unsigned b, unsigned c) {
   const bf16_t l = (bf16_t)lo, h = (bf16_t)hi;
   return (unsigned)__builtin_bit_cast(unsigned short, l) | ((unsigned)__builtin_bit_cast(unsigned short, h) << 16);
 }
-__global__ void add3_bf16_kernel(const u32x4_t* __restrict__ a, const u32x4_t* __restrict__ b, const u32x4_t* __restrict__ c,
-                                 u32x4_t* __restrict__ y, int64_t n8) {
+__global__ void add3_bf16_kernel(const u32x4* __restrict__ a, const u32x4* __restrict__ b, const u32x4* __restrict__ c,
+                                 u32x4* __restrict__ y, int64_t n8) {
   GRID_STRIDE(i, n8) {
-    const u32x4_t u = a[i], v = b[i], w = c[i];
-    u32x4_t o = {add3_2(u[0], v[0], w[0]), add3_2(u[1], v[1], w[1]), add3_2(u[2], v[2], w[2]), add3_2(u[3], v[3], w[3])};
+    const u32x4 u = a[i], v = b[i], w = c[i];
+    u32x4 o = {add3_2(u[0], v[0], w[0]), add3_2(u[1], v[1], w[1]), add3_2(u[2], v[2], w[2]), add3_2(u[3], v[3], w[3])};
     y[i] = o;
   }
 }
-__global__ void relu_fwd8_kernel(const u32x4_t* __restrict__ x, u32x4_t* __restrict__ y, int64_t n8) {
+__global__ void relu_fwd8_kernel(const u32x4* __restrict__ x, u32x4* __restrict__ y, int64_t n8) {
   GRID_STRIDE(i, n8) {
-    const u32x4_t v = x[i];
-    u32x4_t o = {relu2(v[0]), relu2(v[1]), relu2(v[2]), relu2(v[3])};
+    const u32x4 v = x[i];
+    u32x4 o = {relu2(v[0]), relu2(v[1]), relu2(v[2]), relu2(v[3])};
     y[i] = o;
   }
 }
-__global__ void relu_bwd8_kernel(const u32x4_t* __restrict__ dy, const u32x4_t* __restrict__ y, u32x4_t* __restrict__ dx, int64_t n8) {
+__global__ void relu_bwd8_kernel(const u32x4* __restrict__ dy, const u32x4* __restrict__ y, u32x4* __restrict__ dx, int64_t n8) {
   GRID_STRIDE(i, n8) {
-    const u32x4_t g = dy[i], v = y[i];
-    u32x4_t o = {mask2(g[0], v[0]), mask2(g[1], v[1]), mask2(g[2], v[2]), mask2(g[3], v[3])};
+    const u32x4 g = dy[i], v = y[i];
+    u32x4 o = {mask2(g[0], v[0]), mask2(g[1], v[1]), mask2(g[2], v[2]), mask2(g[3], v[3])};
     dx[i] = o;
   }
 }
 
 // the same with a row stride on dy (rows of C8 16-byte pieces, `ld8` pieces apart): a channel slice of a wider gradient read in place
-__global__ void relu_bwd8_rows_kernel(const u32x4_t* __restrict__ dy, int64_t ld8, const u32x4_t* __restrict__ y, u32x4_t* __restrict__ dx,
+__global__ void relu_bwd8_rows_kernel(const u32x4* __restrict__ dy, int64_t ld8, const u32x4* __restrict__ y, u32x4* __restrict__ dx,
                                       int C8, int64_t n8) {
   GRID_STRIDE(i, n8) {
     const int64_t r = i / C8;
-    const u32x4_t g = dy[r * ld8 + (i - r * C8)], v = y[i];
-    u32x4_t o = {mask2(g[0], v[0]), mask2(g[1], v[1]), mask2(g[2], v[2]), mask2(g[3], v[3])};
+    const u32x4 g = dy[r * ld8 + (i - r * C8)], v = y[i];
+    u32x4 o = {mask2(g[0], v[0]), mask2(g[1], v[1]), mask2(g[2], v[2]), mask2(g[3], v[3])};
     dx[i] = o;
   }
 }
@@ -453,7 +424,7 @@ int relu_fwd_t(const T* x, T* y, int64_t n, wsmg_stream_t stream) {
   if (n <= 0 || n % 4) return WSMG_EINVAL;
   if constexpr (std::is_same<T, bf16_t>::value) {
     if (n % 8 == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0) {
-      hipLaunchKernelGGL(relu_fwd8_kernel, dim3(wsmg_sgrid(n / 8)), dim3(256), 0, wsmg_s(stream), (const u32x4_t*)x, (u32x4_t*)y, n / 8);
+      hipLaunchKernelGGL(relu_fwd8_kernel, dim3(wsmg_sgrid(n / 8)), dim3(256), 0, wsmg_s(stream), (const u32x4*)x, (u32x4*)y, n / 8);
       WSMG_RETURN_LAUNCH();
     }
   }
@@ -465,8 +436,8 @@ int relu_bwd_t(const T* dy, const T* y, T* dx, int64_t n, wsmg_stream_t stream) 
   if (n <= 0 || n % 4) return WSMG_EINVAL;
   if constexpr (std::is_same<T, bf16_t>::value) {
     if (n % 8 == 0 && (((uintptr_t)dy | (uintptr_t)y | (uintptr_t)dx) & 15) == 0) {
-      hipLaunchKernelGGL(relu_bwd8_kernel, dim3(wsmg_sgrid(n / 8)), dim3(256), 0, wsmg_s(stream), (const u32x4_t*)dy, (const u32x4_t*)y,
-                         (u32x4_t*)dx, n / 8);
+      hipLaunchKernelGGL(relu_bwd8_kernel, dim3(wsmg_sgrid(n / 8)), dim3(256), 0, wsmg_s(stream), (const u32x4*)dy, (const u32x4*)y,
+                         (u32x4*)dx, n / 8);
       WSMG_RETURN_LAUNCH();
     }
   }
@@ -541,21 +512,21 @@ extern "C" int wsmg_cat_channels(const void* a, const void* b, void* y, int64_t 
   if (rows <= 0 || bytes_a <= 0 || bytes_b <= 0 || (bytes_a & 15) || (bytes_b & 15)) return WSMG_EINVAL;
   if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)y) & 15) return WSMG_EINVAL;
   const int ca = bytes_a / 16, cb = bytes_b / 16;
-  hipLaunchKernelGGL(cat_channels_kernel, dim3(wsmg_sgrid(rows * (ca + cb))), dim3(256), 0, wsmg_s(s), (const u32x4_t*)a, (const u32x4_t*)b,
-                     (u32x4_t*)y, rows, ca, cb);
+  hipLaunchKernelGGL(cat_channels_kernel, dim3(wsmg_sgrid(rows * (ca + cb))), dim3(256), 0, wsmg_s(s), (const u32x4*)a, (const u32x4*)b,
+                     (u32x4*)y, rows, ca, cb);
   WSMG_RETURN_LAUNCH();
 }
 extern "C" int wsmg_upsample2x_cat_bf16(const void* a, const void* b, void* y, int B, int H, int W, int Ca, int Cb, wsmg_stream_t s) {
   if (B <= 0 || H <= 0 || W <= 0 || Ca <= 0 || Cb <= 0 || (Ca & 7) || (Cb & 7)) return WSMG_EINVAL;
   if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)y) & 15) return WSMG_EINVAL;
   hipLaunchKernelGGL(upsample_cat_bf16_kernel, dim3(wsmg_sgrid((int64_t)B * 4 * H * W * (Ca + Cb) / 8)), dim3(256), 0, wsmg_s(s), CB16(a),
-                     (const u32x4_t*)b, (u32x4_t*)y, B, H, W, Ca / 8, Cb / 8);
+                     (const u32x4*)b, (u32x4*)y, B, H, W, Ca / 8, Cb / 8);
   WSMG_RETURN_LAUNCH();
 }
 extern "C" int wsmg_add3_bf16(const void* a, const void* b, const void* c, void* y, int64_t n, wsmg_stream_t s) {
   if (!a || !b || !c || !y || n <= 0 || (n & 7) || (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)y) & 15)) return WSMG_EINVAL;
-  hipLaunchKernelGGL(add3_bf16_kernel, dim3(wsmg_sgrid(n / 8)), dim3(256), 0, wsmg_s(s), (const u32x4_t*)a, (const u32x4_t*)b, (const u32x4_t*)c,
-                     (u32x4_t*)y, n / 8);
+  hipLaunchKernelGGL(add3_bf16_kernel, dim3(wsmg_sgrid(n / 8)), dim3(256), 0, wsmg_s(s), (const u32x4*)a, (const u32x4*)b, (const u32x4*)c,
+                     (u32x4*)y, n / 8);
   WSMG_RETURN_LAUNCH();
 }
 extern "C" int wsmg_relu_fwd(const float* x, float* y, int64_t n, wsmg_stream_t s) { return relu_fwd_t<float>(x, y, n, s); }
@@ -570,8 +541,8 @@ extern "C" int wsmg_relu_bwd(const float* dy, const float* y, float* dx, int64_t
 extern "C" int wsmg_relu_bwd_bf16(const void* dy, const void* y, void* dx, int64_t n, wsmg_stream_t s) { return relu_bwd_t<bf16_t>(CB16(dy), CB16(y), B16(dx), n, s); }
 extern "C" int wsmg_relu_bwd_rows_bf16(const void* dy, int64_t ld_dy, const void* y, void* dx, int64_t rows, int C, wsmg_stream_t s) {
   if (rows <= 0 || C <= 0 || (C & 7) || ld_dy < C || (ld_dy & 7) || (((uintptr_t)dy | (uintptr_t)y | (uintptr_t)dx) & 15)) return WSMG_EINVAL;
-  hipLaunchKernelGGL(relu_bwd8_rows_kernel, dim3(wsmg_sgrid(rows * C / 8)), dim3(256), 0, wsmg_s(s), (const u32x4_t*)dy, ld_dy / 8,
-                     (const u32x4_t*)y, (u32x4_t*)dx, C / 8, rows * C / 8);
+  hipLaunchKernelGGL(relu_bwd8_rows_kernel, dim3(wsmg_sgrid(rows * C / 8)), dim3(256), 0, wsmg_s(s), (const u32x4*)dy, ld_dy / 8,
+                     (const u32x4*)y, (u32x4*)dx, C / 8, rows * C / 8);
   WSMG_RETURN_LAUNCH();
 }
 extern "C" int wsmg_maxpool3x3s2_fwd(const float* x, float* y, int B, int H, int W, int C, int OH, int OW, wsmg_stream_t s) { return maxpool_fwd_t<float>(x, y, B, H, W, C, OH, OW, s); }

@@ -28,8 +28,7 @@
 
 namespace {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));   // a 16-byte unit: one global_load_dwordx4 / store per lane
-
+// the unit below is a u32x4, 16 bytes: one global_load_dwordx4 / store per lane
 constexpr int GATHER_PER = 8;                     // units per thread, all loaded before the first store
 constexpr int GATHER_RUN = 256 * GATHER_PER;      // consecutive destination units of one field per workgroup
 

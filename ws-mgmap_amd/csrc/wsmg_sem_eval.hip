@@ -19,8 +19,6 @@
 
 namespace {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int CH = 32;          // channels of the logits = padded classes
 constexpr int THREADS = 512;
 constexpr int PIX = 2;          // pixels in flight per thread

@@ -73,7 +73,7 @@ class _BnAct(torch.autograd.Function):
         rows, C, relu, has_res, train, sfx = ctx.cfg
         if not train:
             raise _abi.WsmgError("backward through eval-mode BatchNorm is not part of the reference's path")
-        dy, ld = _rows_of(dy, C)
+        dy, ld = _rows_of(dy, C)      # ld > C: a channel slice of a concatenation's gradient, read in place
         dx = torch.empty_like(x)
         dres = torch.empty_like(x) if has_res else None
         dgamma = torch.empty(C, device=x.device, dtype=torch.float32)
@@ -84,12 +84,8 @@ class _BnAct(torch.autograd.Function):
             _abi.call("wsmg_bn_act_bwd_ld_bf16_lo", _p(dy), ld, _p(x), _p(y), _p(gamma), _p(beta), _p(mean), _p(invstd), relu, rows, C,
                       _p(dx), _p(lo), _p(dres), _p(dgamma), _p(dbeta), _p(ws), ws.numel() * 8, _stream())
             ctx.lo_sink.lo = lo
-            return dx, dres, dgamma, dbeta, None, None, None, None, None, None, None, None
-        if ld != C:     # a channel slice of a concatenation's gradient, read in place
-            _abi.call("wsmg_bn_act_bwd_ld" + sfx, _p(dy), ld, _p(x), _p(y), _p(gamma), _p(beta), _p(mean), _p(invstd), relu, rows, C,
-                      _p(dx), _p(dres), _p(dgamma), _p(dbeta), _p(ws), ws.numel() * 8, _stream())
         else:
-            _abi.call("wsmg_bn_act_bwd" + sfx, _p(dy), _p(x), _p(y), _p(gamma), _p(beta), _p(mean), _p(invstd), relu, rows, C,
+            _abi.call("wsmg_bn_act_bwd_ld" + sfx, _p(dy), ld, _p(x), _p(y), _p(gamma), _p(beta), _p(mean), _p(invstd), relu, rows, C,
                       _p(dx), _p(dres), _p(dgamma), _p(dbeta), _p(ws), ws.numel() * 8, _stream())
         return dx, dres, dgamma, dbeta, None, None, None, None, None, None, None, None
 
