@@ -380,6 +380,59 @@ def test_generic_bf16_weight_gradient_forms(cfg):
     assert err <= 2e-5 * scale, err / scale
 
 
+# ----------------------------------------------------------------------------- k8 stem weight gradient: tile groups that find no tile
+# conv_win_wgrad_kernel (csrc/wsmg_conv_win_wgrad.hip): 8 roles x G groups of 5 x 25-pixel tiles, G = min(64, tiles) rounded up to whole
+# rounds of 8, one slab per group.  A group beyond the tile count must still write its slab (zeros): nothing else does.
+# (name, H = W, tiles, groups)
+STEM_FEW = [("b1_100", 100, 20, 24),      # OH = 50: whole blocks, fewer tiles than groups, a tile count that is no multiple of 8
+            ("b1_36", 36, 4, 8)]          # OH = 18: every block hangs over the right and bottom edges (the per-pixel dY test)
+
+
+@pytest.mark.parametrize("cfg", STEM_FEW, ids=[c[0] for c in STEM_FEW])
+def test_stem_window_weight_gradient_with_tile_less_groups(cfg):
+    """64 -> 64, k8 s2 p3, B = 1 through plan / slabs / reduce on a NaN-FILLED workspace, against the float64 weight gradient of the same
+    bf16 operands at the family's bar, 2e-5 max|ref| (test_generic_bf16_weight_gradient_forms); bit-identical over three launches; the
+    atomic form at the same bar."""
+    from wsmgmap import _abi, ops
+    name, H, tiles, groups = cfg
+    B, C, k, s, p = 1, 64, 8, 2, 3
+    dims = cr.dims(B, C, C, k, s, p, H)
+    OH = dims[-1]
+    assert B * -(-OH // 5) * -(-OH // 25) == tiles and tiles < groups
+    r = cr.route(cr.BWD_WEIGHT, dims)
+    assert (r["kind"], r["nsplit"]) == ("WGRAD_STEM_WIN", groups), r
+    assert cr.plan_nsplit(dims) == groups
+    x = torch.relu(T(df.uniform(f"inst.stemw.{name}.x", (B, H, H, C), 4.0))).to(torch.bfloat16)
+    dy = T(df.uniform(f"inst.stemw.{name}.dy", (B, OH, OH, C), 0.4)).clone()
+    dy[:, OH // 2] = 0
+    dy = dy.to(torch.bfloat16)
+    want = torch.nn.grad.conv2d_weight(x.double().permute(0, 3, 1, 2), (C, C, k, k), dy.double().permute(0, 3, 1, 2), stride=s, padding=p)
+    scale = float(want.abs().max())
+    xg, dyg = x.cuda(), dy.cuda()
+    slab = C * k * k * C
+    outs = []
+    for _ in range(3):
+        ws = torch.full((groups * slab,), float("nan"), device="cuda")
+        _abi.call("wsmg_conv2d_bwd_weight_bf16_slabs", ops._p(xg), ops._p(dyg), ops._p(ws), groups, groups * slab, *dims, ops._stream())
+        dw = torch.full((C, C, k, k), float("nan"), device="cuda")
+        _abi.call("wsmg_weight_grad_reduce_oihw", ops._p(ws), groups, C, C, k, k, C, ops._p(dw), ops._stream())
+        torch.cuda.synchronize()
+        outs.append(dw.cpu())
+    left = int(torch.isnan(outs[0]).sum())
+    print(f"{name}: {left} of {outs[0].numel()} elements of dW are NaN (slabs left unwritten)")
+    assert left == 0
+    assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
+    err = float((outs[0].double() - want).abs().max())
+    print(f"{name}: slab form err / scale {err / scale:.3e}")
+    assert err <= 2e-5 * scale, err / scale
+    dwa = torch.zeros(C, k, k, C, device="cuda")
+    _abi.call("wsmg_conv2d_bwd_weight_bf16", ops._p(xg), ops._p(dyg), ops._p(dwa), *dims, ops._stream())
+    torch.cuda.synchronize()
+    err = float((dwa.permute(0, 3, 1, 2).double().cpu() - want).abs().max())
+    print(f"{name}: atomic form err / scale {err / scale:.3e}")
+    assert err <= 2e-5 * scale, err / scale
+
+
 # ----------------------------------------------------------------------------- Adam: vector path, scalar tail, unaligned path
 ADAM_SIZES = [1, 3, 4, 4095, 4096, 4097, 8193]
 

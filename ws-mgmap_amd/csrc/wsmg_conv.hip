@@ -14,7 +14,7 @@
 // ranges (grid.z) and combined with float atomics.
 #include <stdlib.h>
 
-#include "wsmg_conv_tile.h"
+#include "wsmg_wgrad_tile.h"
 
 namespace {
 
@@ -308,19 +308,9 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradArgs a) {
   const int uu = u0 + wave;
   const int tap = uu / cchunks;
   const int ci = (uu - tap * cchunks) * 32 + r;
-  const int taps = a.KH * a.KW;
 #pragma unroll
-  for (int t = 0; t < 2; ++t) {
-#pragma unroll
-    for (int g = 0; g < 16; ++g) {
-      int co = co0 + 32 * t + (g & 3) + 8 * (g >> 2) + 4 * h;
-      if (co < a.Cout) {
-        float* const q = a.dw + (size_t)bz * a.slab + ((size_t)co * taps + tap) * a.Cin + ci;
-        if (a.slab) *q = t == 0 ? acc0[g] : acc1[g];
-        else atomicAdd(q, t == 0 ? acc0[g] : acc1[g]);
-      }
-    }
-  }
+  for (int t = 0; t < 2; ++t)   // (Cout % 32 == 0: a 32-channel tile is whole or past the end)
+    if (co0 + 32 * t < a.Cout) wgrad_flush_tile(t == 0 ? acc0 : acc1, a.dw, a.slab, bz, co0 + 32 * t, a.KH * a.KW, tap, a.Cin, ci, h, true);
 }
 
 // pipeline variant: DB = false everywhere (set from measurements); the DB = true instantiations no dispatcher could select are

@@ -13,7 +13,7 @@
 //       lane) — no transposed copy is ever materialised.
 #include <stdlib.h>
 
-#include "wsmg_conv_tile.h"
+#include "wsmg_wgrad_tile.h"
 #include "wsmg_relu_mask.h"
 
 namespace {
@@ -494,12 +494,9 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_kernel(WgradArgsB a) {
     for (int u = 0; u < WUN; ++u) *reinterpret_cast<u32x4*>(&Xs[(u * WKP + xpx) * X_LD + xseg * 16]) = rx[u];
   };
 
-  // transposing-read lane map (every lane participates: EXEC must be full)
-  const int li = lane & 15, q = li >> 2, p4 = li & 3;
-  const int half16 = (lane >> 4) & 1;  // which 16 of the 32 MFMA rows/cols this 16-lane group owns
-  const int h = lane >> 5;             // k half: pixels 8h .. 8h+7 of a 16-pixel MFMA step
-  const unsigned char* a_base = &Ds[(8 * h + q) * D_LD + (half16 * 16 + p4 * 4) * 2];   // + 64 t: co 32t..32t+31
-  const unsigned char* b_base = &Xs[(wave * TU * WKP + 8 * h + q) * X_LD + (half16 * 16 + p4 * 4) * 2];
+  const TrLane tl(lane);
+  const unsigned char* a_base = &Ds[(8 * tl.h + tl.q4) * D_LD + tl.chan_off];   // + 64 t: co 32t..32t+31
+  const unsigned char* b_base = &Xs[(wave * TU * WKP + 8 * tl.h + tl.q4) * X_LD + tl.chan_off];
 
   // branch-free main loop over a multiple of PF k-steps (pieces past p_end load zeros), see the igemm loop
   gload(rd[0], rx[0]);
@@ -515,16 +512,9 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_kernel(WgradArgsB a) {
       for (int ks = 0; ks < WKP / 16; ++ks) {
         bf16x8 af[TC], bfr[TU];
 #pragma unroll
-        for (int t = 0; t < TC; ++t) {
-          bf16x4 l = tr_read(a_base + 64 * t + (16 * ks) * D_LD), hh = tr_read(a_base + 64 * t + (16 * ks + 4) * D_LD);
-          af[t] = __builtin_shufflevector(l, hh, 0, 1, 2, 3, 4, 5, 6, 7);
-        }
+        for (int t = 0; t < TC; ++t) af[t] = tr_frag(a_base + 64 * t + (16 * ks) * D_LD, D_LD);
 #pragma unroll
-        for (int u = 0; u < TU; ++u) {
-          const unsigned char* bp = b_base + u * WKP * X_LD;
-          bf16x4 l = tr_read(bp + (16 * ks) * X_LD), hh = tr_read(bp + (16 * ks + 4) * X_LD);
-          bfr[u] = __builtin_shufflevector(l, hh, 0, 1, 2, 3, 4, 5, 6, 7);
-        }
+        for (int u = 0; u < TU; ++u) bfr[u] = tr_frag(b_base + (u * WKP + 16 * ks) * X_LD, X_LD);
 #pragma unroll
         for (int u = 0; u < TU; ++u)
 #pragma unroll
@@ -535,26 +525,15 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_kernel(WgradArgsB a) {
       __syncthreads();
     }
   }
-  const int r = lane & 31;
-  const int taps = a.KH * a.KW;
 #pragma unroll
   for (int u = 0; u < TU; ++u) {
     const int uu = u0 + wave * TU + u;
     if (uu >= a.units) continue;
     const int tap = uu / cchunks;
-    const int ci = (uu - tap * cchunks) * 32 + r;
+    const int ci = (uu - tap * cchunks) * 32 + (lane & 31);
 #pragma unroll
-    for (int t = 0; t < TC; ++t) {
-#pragma unroll
-      for (int g = 0; g < 16; ++g) {
-        int co = co0 + 32 * t + (g & 3) + 8 * (g >> 2) + 4 * h;
-        if (co < a.Cout) {
-          float* const q = a.dw + (size_t)bz * a.slab + ((size_t)co * taps + tap) * a.Cin + ci;
-          if (a.slab) *q = acc[t][u][g];      // lanes = consecutive input channels: two 128-byte segments per instruction
-          else atomicAdd(q, acc[t][u][g]);
-        }
-      }
-    }
+    for (int t = 0; t < TC; ++t)   // (Cout % 32 == 0: a 32-channel tile is whole or past the end)
+      if (co0 + 32 * t < a.Cout) wgrad_flush_tile(acc[t][u], a.dw, a.slab, bz, co0 + 32 * t, a.KH * a.KW, tap, a.Cin, ci, tl.h, true);
   }
 }
 

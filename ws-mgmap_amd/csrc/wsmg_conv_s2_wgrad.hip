@@ -21,7 +21,7 @@
 // (3) 8 waves where the layer has four co tiles (enc3).
 #include <stdlib.h>
 
-#include "wsmg_conv_tile.h"
+#include "wsmg_wgrad_tile.h"
 
 namespace {
 
@@ -54,11 +54,8 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void conv_s2_wgrad_kernel
   unsigned char* const xs = lds;
   unsigned char* const ds = lds + X_BYTES;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // workgroup -> (role, group): the roles of a group read the same dY tiles and overlapping input rows at about the same time, so they
-  // share an XCD (its L2): local index i = bid / 8 on XCD bid % 8 -> role i % R, group (bid % 8) + 8 (i / R)
-  constexpr int R = K * NCC;
-  const int xcd = blockIdx.x & 7, li_ = blockIdx.x >> 3;
-  const int role = li_ % R, grp = xcd + 8 * (li_ / R);
+  int role, grp;
+  wgrad_role_group(blockIdx.x, K * NCC, role, grp);
   const int ky = role % K, cc = role / K;
   const int ntiles = a.B * a.tiles_y;
   const __amdgpu_buffer_rsrc_t xr = make_rsrc(a.x, a.x_bytes), dr = make_rsrc(a.dy, a.dy_bytes);
@@ -112,15 +109,11 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void conv_s2_wgrad_kernel
     }
   };
 
-  // ---- transposing-read lane map (as conv_wgrad_bf16_kernel): the lane supplies the address of pixel 8 h + q4 (+ 4 for the second
-  // read) and channels 16 half16 + 4 p4 .. + 3 of its tile; the hardware hands each lane 4 pixels of ITS channel
-  const int li = lane & 15, q4 = li >> 2, p4 = li & 3;
-  const int half16 = (lane >> 4) & 1, h = lane >> 5;
-  const int chan_off = (half16 * 16 + p4 * 4) * 2;
+  const TrLane tl(lane);
   const int cot = wave % NCO, cih = wave / NCO;
-  const int l0 = 8 * h + q4;
-  const unsigned char* const a_base = ds + cot * DPLANE + l0 * 64 + chan_off;
-  const unsigned char* const x_base = xs + cih * XPLANE + chan_off;
+  const int l0 = 8 * tl.h + tl.q4;
+  const unsigned char* const a_base = ds + cot * DPLANE + l0 * 64 + tl.chan_off;
+  const unsigned char* const x_base = xs + cih * XPLANE + tl.chan_off;
   auto xoff = [&](int c, int s2) {   // window entry of pixel 16 c + 8 h + q4 + 4 s2 at tap kx = 0 (padding pixels repeat the last one)
     int p = 16 * c + l0 + 4 * s2;
     p = p < NPXR ? p : NPXR - 1;
@@ -141,14 +134,12 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void conv_s2_wgrad_kernel
     __syncthreads();
     struct Frag { bf16x8 a, b[K]; };
     auto fload = [&](int c, Frag& f) {
-      const bf16x4 l = tr_read(a_base + (16 * c) * 64), hh = tr_read(a_base + (16 * c + 4) * 64);
-      f.a = __builtin_shufflevector(l, hh, 0, 1, 2, 3, 4, 5, 6, 7);
+      f.a = tr_frag(a_base + (16 * c) * 64, 64);
       const int x0 = xoff(c, 0), x1 = xoff(c, 1);
 #pragma unroll
       for (int v = 0; v < K; ++v) {
         const int to = ((v & 1) * PC + (v >> 1)) * 64;   // tap kx = v: parity plane kx & 1, entry shift kx >> 1
-        const bf16x4 l2 = tr_read(x_base + x0 + to), h2 = tr_read(x_base + x1 + to);
-        f.b[v] = __builtin_shufflevector(l2, h2, 0, 1, 2, 3, 4, 5, 6, 7);
+        f.b[v] = tr_frag(x_base + x0 + to, x_base + x1 + to);
       }
     };
     for (; tile < ntiles; tile += a.groups) {
@@ -180,20 +171,10 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void conv_s2_wgrad_kernel
     }
   }
 
-  // ---- one flush per workgroup: lane r = input channel (consecutive lanes -> 128-byte segments of an OHWI row)
-  const int r = lane & 31;
-  const int ci = cc * 64 + 32 * cih + r;
+  // ---- one flush per workgroup
 #pragma unroll
-  for (int v = 0; v < K; ++v) {
-    const int tap = ky * K + v;
-#pragma unroll
-    for (int g = 0; g < 16; ++g) {
-      const int co = 32 * cot + (g & 3) + 8 * (g >> 2) + 4 * h;
-      float* const q = a.dw + (size_t)grp * a.slab + ((size_t)co * (K * K) + tap) * a.Cin + ci;
-      if (a.slab) *q = acc[v][g];
-      else if (grp < ntiles) atomicAdd(q, acc[v][g]);
-    }
-  }
+  for (int v = 0; v < K; ++v)
+    wgrad_flush_tile(acc[v], a.dw, a.slab, grp, 32 * cot, K * K, ky * K + v, a.Cin, cc * 64 + 32 * cih + (lane & 31), tl.h, grp < ntiles);
 }
 
 struct S2wShape { int K, P, H, Cin, Cout, TH, groups; };
@@ -203,18 +184,13 @@ constexpr S2wShape kEnc3{5, 1, 50, 64, 128, 8, 48}, kStem{7, 3, 24, 256, 64, 12,
 
 const S2wShape* s2w_shape(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH, int OW) {
   if (stride != 2 || KH != KW || H != W || OH != OW) return nullptr;
-  if ((size_t)B * H * W * Cin * 2 >= (1ull << 31) || (size_t)B * OH * OW * Cout * 2 >= (1ull << 31)) return nullptr;
+  if (wsmg_check_conv_bf16(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return nullptr;   // (OH, and the 32-bit byte-offset limits)
   for (const S2wShape* s : {&kEnc3, &kStem})
-    if (KH == s->K && pad == s->P && H == s->H && Cin == s->Cin && Cout == s->Cout && OH == (H + 2 * pad - KH) / 2 + 1) return s;
+    if (KH == s->K && pad == s->P && H == s->H && Cin == s->Cin && Cout == s->Cout) return s;
   return nullptr;
 }
 
-int s2w_groups(const S2wShape* s, int B, int OH) {
-  const int ntiles = B * ((OH + s->TH - 1) / s->TH);
-  int groups = s->groups;
-  if (groups > ntiles) groups = ntiles;
-  return (groups + 7) / 8 * 8;   // whole XCD rounds (groups beyond the tile count find no tile and flush zeros)
-}
+int s2w_groups(const S2wShape* s, int B, int OH) { return wgrad_groups(s->groups, B * ((OH + s->TH - 1) / s->TH)); }
 
 template <int K, int P, int TH, int TW, int NCO, int NW, int NCC>
 int launch_s2w(S2wArgs& a, hipStream_t s) {
@@ -222,15 +198,7 @@ int launch_s2w(S2wArgs& a, hipStream_t s) {
   constexpr int NPX = (TH * TW + 15) & ~15;
   constexpr int LDS = 2 * (TH * WC * 64 + 64) + NCO * (NPX * 64 + 64);
   static_assert(LDS <= 160 * 1024, "LDS of one CU");
-  auto kern = conv_s2_wgrad_kernel<K, P, TH, TW, NCO, NW, NCC>;
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)(K * NCC * a.groups)), dim3(NW * 64), LDS, s, a);
-  WSMG_RETURN_LAUNCH();
+  return wsmg_launch_dyn_lds<conv_s2_wgrad_kernel<K, P, TH, TW, NCO, NW, NCC>>(dim3((unsigned)(K * NCC * a.groups)), dim3(NW * 64), LDS, s, a);
 }
 
 }  // namespace

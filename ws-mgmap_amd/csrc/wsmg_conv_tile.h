@@ -74,6 +74,20 @@ inline int wsmg_cu_count() {
   return cus;
 }
 
+// Launch of a kernel whose dynamic LDS exceeds the 64 KB default: the limit is raised once per KERNEL INSTANCE (the kernel is a template
+// argument, so every instance has its own latch), then the launch; returns the launch error
+template <auto kernel, class Args>
+int wsmg_launch_dyn_lds(dim3 grid, dim3 block, int lds_bytes, hipStream_t s, const Args& args) {
+  static bool raised = false;
+  if (!raised) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+    if (e != hipSuccess) return (int)e;
+    raised = true;
+  }
+  hipLaunchKernelGGL(kernel, grid, block, lds_bytes, s, args);
+  WSMG_RETURN_LAUNCH();
+}
+
 // geometry every convolution entry point checks (the bf16 engine adds its 32-bit byte-offset limits: wsmg_check_conv_bf16)
 inline int wsmg_check_conv(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH, int OW) {
   if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || KH <= 0 || KW <= 0) return WSMG_EINVAL;

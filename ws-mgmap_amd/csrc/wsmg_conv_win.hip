@@ -245,15 +245,7 @@ int wsmg_conv_win_fwd_bf16(const void* x, const void* w_ohwi, const float* bias,
   constexpr int TH = 5, TW = 25;
   WinArgs a{(const bf16_t*)x, (const bf16_t*)w_ohwi, bias, (bf16_t*)y, B, H, W, OH, OW, (OH + TH - 1) / TH, (OW + TW - 1) / TW, relu,
             (unsigned)((size_t)B * H * W * 128), (unsigned)(64u * 8 * 8 * 64 * 2), stats, nslab};
-  auto kern = conv_win_fwd_kernel<8, 2, 3, TH, TW>;
   constexpr int LDS = (((TH - 1) * 2 + 8) * 2 * (((TW - 1) * 2 + 8) / 2) + 3 * 64) * 144;
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }
   int ntiles = B * a.tiles_y * a.tiles_x, grid = ntiles < 256 ? ntiles : 256;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), LDS, s, a);
-  WSMG_RETURN_LAUNCH();
+  return wsmg_launch_dyn_lds<conv_win_fwd_kernel<8, 2, 3, TH, TW>>(dim3((unsigned)grid), dim3(256), LDS, s, a);
 }

@@ -351,18 +351,10 @@ __global__ __launch_bounds__(512) void conv_win3_mixed_kernel(Win3Args a) {
 template <int MT, int NPW, int NT, int AUX>
 int launch_win3_aux(Win3Args& a, hipStream_t s) {
   constexpr int LDS = 2 * 128 * NPW * ROWB + NST * NT * ROWB + 1024;
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_win3_kernel<MT, NPW, NT, AUX>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }
   const int64_t M = (int64_t)a.B * a.H * a.W;
   a.mtiles = (int)wsmg_cdiv(M, MT);
   a.ntiles = a.N / NT;
-  hipLaunchKernelGGL((conv_win3_kernel<MT, NPW, NT, AUX>), dim3((unsigned)(a.mtiles * a.ntiles)), dim3(512), LDS, s, a);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return wsmg_launch_dyn_lds<conv_win3_kernel<MT, NPW, NT, AUX>>(dim3((unsigned)(a.mtiles * a.ntiles)), dim3(512), LDS, s, a);
 }
 // which store loop a launch needs: 1 = mask / split output
 inline int aux_form(const Win3Args& a) { return (a.relu_z || a.dst2) ? 1 : 0; }
@@ -391,17 +383,9 @@ bool mixed_plan(Win3Args& a, int64_t M, int MT, int NT) {
 template <int MT, int NPW, int NPW_S, int NT, int AUX>
 int launch_win3_mixed_aux(Win3Args& a, hipStream_t s) {
   constexpr int LDS = 2 * 128 * NPW * ROWB + NST * NT * ROWB + 1024;
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_win3_mixed_kernel<MT, NPW, NPW_S, NT, AUX>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }
   a.ntiles = a.N / NT;
   a.mtiles = 0;
-  hipLaunchKernelGGL((conv_win3_mixed_kernel<MT, NPW, NPW_S, NT, AUX>), dim3((unsigned)(a.nbig + a.nsmall)), dim3(512), LDS, s, a);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return wsmg_launch_dyn_lds<conv_win3_mixed_kernel<MT, NPW, NPW_S, NT, AUX>>(dim3((unsigned)(a.nbig + a.nsmall)), dim3(512), LDS, s, a);
 }
 template <int MT, int NPW, int NPW_S, int NT>
 int launch_win3_mixed(Win3Args& a, hipStream_t s) {

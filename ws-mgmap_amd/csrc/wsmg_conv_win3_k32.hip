@@ -196,13 +196,5 @@ int wsmg_conv_win3_k32_bf16(int bwd, const void* src, const void* wt, const floa
   K32Args a{(const bf16_t*)src, (const bf16_t*)wt, bias, (bf16_t*)dst, B, H, W, N, N / 32, 0, relu, bwd, dst_ld,
             (unsigned)((size_t)B * H * W * 32 * 2), (unsigned)((size_t)N * 9 * 32 * 2), stats, nslab};
   a.mtiles = (int)wsmg_cdiv((int64_t)B * H * W, MT);
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_win3_k32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, K32_LDS);
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }
-  hipLaunchKernelGGL(conv_win3_k32_kernel, dim3((unsigned)grid), dim3(256), K32_LDS, s, a);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return wsmg_launch_dyn_lds<conv_win3_k32_kernel>(dim3((unsigned)grid), dim3(256), K32_LDS, s, a);
 }

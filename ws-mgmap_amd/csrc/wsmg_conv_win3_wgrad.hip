@@ -155,8 +155,10 @@ __global__ __launch_bounds__(512) void conv_win3_wgrad_kernel(W3wArgs a) {
     dma_advance();
   };
 
-  // ---- MFMA roles: wave -> (output-channel tile tco, input-channel tile tci); transposing-read lane map as in
-  // conv_wgrad_bf16_kernel: the lane supplies row 8 h + q4 (+ 4 for the second read) and channels 16 half16 + 4 p4 .. + 3
+  // ---- MFMA roles: wave -> (output-channel tile tco, input-channel tile tci).  The lane map, the fragment assembly and the flush are
+  // wsmg_wgrad_tile.h's TrLane / tr_frag / wgrad_flush_tile in this kernel's OWN spelling: through the helpers its pixel-split variants
+  // measured slower (profiles/wgrad_once.txt, "tried and not kept"); the lane supplies row 8 h + q4 (+ 4 for the second read) and
+  // channels 16 half16 + 4 p4 .. + 3
   const int pair = wave % NPAIR, wk = wave / NPAIR;
   const int tco = pair % WCO, tci = pair / WCO;
   const int li = lane & 15, q4 = li >> 2, p4 = li & 3;
@@ -254,7 +256,7 @@ __global__ __launch_bounds__(512) void conv_win3_wgrad_kernel(W3wArgs a) {
     if (wk != 0) return;
   }
 
-  // ---- one flush per workgroup: lane r = input channel (consecutive lanes -> 128-byte segments of an OHWI row)
+  // ---- one flush per workgroup (no range is empty: plan_w3w), ONE branch round all nine tiles: lane r = input channel
   const int r = lane & 31;
   const int ci = ci0 + 32 * tci + r;
   if (a.slab) {     // deterministic form: plain stores into this image range's slab
@@ -291,9 +293,8 @@ struct W3wShape { int wco, wci, ks, xcap; };
 constexpr W3wShape kShape[5] = {{0, 0, 0, 0}, {4, 2, 48, 104}, {2, 2, 64, 120}, {4, 1, 64, 128}, {1, 1, 256, 368}};
 
 W3wVariant w3w_variant(int B, int H, int W, int Cin, int Cout) {
-  if (B <= 0 || H < 1 || W < 16) return V_NONE;   // W < 16: the pad columns and the last k-step's unused entries cost more than
-                                                  // the window saves (12 x 12: 0.091 vs 0.052 ms)
-  if ((size_t)B * H * W * (size_t)(Cin > Cout ? Cin : Cout) * 2 >= (1ull << 31)) return V_NONE;
+  if (W < 16) return V_NONE;   // the pad columns and the last k-step's unused entries cost more than the window saves (12 x 12: 0.091 vs 0.052 ms)
+  if (wsmg_check_conv_bf16(B, H, W, Cin, Cout, 3, 3, 1, 1, H, W)) return V_NONE;   // (its 32-bit byte-offset limits)
   const unsigned PW = (unsigned)(W + 2);
   const uint64_t nmax = (uint64_t)(H + 4) * PW + 256 + 368;   // (largest k-step + window of the shapes above)
   if (nmax * PW >= (1ull << 32)) return V_NONE;
@@ -322,18 +323,8 @@ int launch_w3w(W3wArgs& a, W3wVariant v, hipStream_t s) {
   constexpr int STAGES = NSTG * (16 * WK * SL * 64 * WCO + XCAP * 64 * WCI) + 1024;
   constexpr int LDS = (WK > 1 && RED_BYTES > STAGES) ? RED_BYTES : STAGES;
   static_assert(LDS <= 160 * 1024, "LDS of one CU");
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_win3_wgrad_kernel<WCO, WCI, WK, SL, XCAP, NLW, NSTG>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }
   plan_w3w(a, v);
-  const int ntile = a.gco * a.gci;
-  hipLaunchKernelGGL((conv_win3_wgrad_kernel<WCO, WCI, WK, SL, XCAP, NLW, NSTG>), dim3((unsigned)(ntile * a.gz)), dim3(512), LDS, s, a);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return wsmg_launch_dyn_lds<conv_win3_wgrad_kernel<WCO, WCI, WK, SL, XCAP, NLW, NSTG>>(dim3((unsigned)(a.gco * a.gci * a.gz)), dim3(512), LDS, s, a);
 }
 
 }  // namespace

@@ -18,7 +18,7 @@
 // (3 padding pixels: their dY rows are zero, their X addresses repeat the last pixel).
 #include <stdlib.h>
 
-#include "wsmg_conv_tile.h"
+#include "wsmg_wgrad_tile.h"
 
 namespace {
 
@@ -49,12 +49,8 @@ __global__ __launch_bounds__(256, 2) void conv_win_wgrad_kernel(WinWgradArgs a) 
   unsigned char* const xs = lds;
   unsigned char* const ds = lds + X_BYTES;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // Workgroup -> (kernel row ky, tile group): consecutive block ids go round the 8 XCDs, and the 8 roles of a group read
-  // the same dY tiles and overlapping input rows (every input row is wanted by 2-3 of them) at about the same time — so
-  // the roles of a group share an XCD (its L2): local index i = bid / 8 on XCD bid % 8 -> role i % 8, group (bid % 8) + 8 (i / 8).
-  // With the roles spread over the XCDs (role = bid % 8) the kernel moved 4.2 GB through the fabric in 0.78 ms and waited on it.
-  const int xcd = blockIdx.x & 7, li_ = blockIdx.x >> 3;
-  const int ky = li_ & 7, grp = xcd + 8 * (li_ >> 3);
+  int ky, grp;   // role = kernel row: every input row is wanted by 2-3 of a group's 8 roles
+  wgrad_role_group(blockIdx.x, K, ky, grp);
   const int tpi = a.tiles_y * a.tiles_x;
   const int ntiles = a.B * tpi;
   const __amdgpu_buffer_rsrc_t xr = make_rsrc(a.x, a.x_bytes), dr = make_rsrc(a.dy, a.dy_bytes);
@@ -118,21 +114,17 @@ __global__ __launch_bounds__(256, 2) void conv_win_wgrad_kernel(WinWgradArgs a) 
     for (int j = 0; j < DPER; ++j) *reinterpret_cast<u32x4*>(ds + (wc0 + 32 * j) * PITCH + pch * 16) = rd[j];
   };
 
-  // ---- transposing-read lane map (as conv_wgrad_bf16_kernel): the lane supplies the address of pixel 8 h + q (+ 4 for
-  // the second read) and channels 16 half16 + 4 p4 .. + 3; the hardware hands each lane 4 pixels of ITS channel
-  const int li = lane & 15, q4 = li >> 2, p4 = li & 3;
-  const int half16 = (lane >> 4) & 1, h = lane >> 5;
-  const int chan_off = (half16 * 16 + p4 * 4) * 2;
+  const TrLane tl(lane);
   // X entry of K index k = 16 c + 8 h + q4 (+ 4): pixel -> (row, ox); padding pixels repeat pixel 124.  Computed per chunk
   // (6 VALU instructions per address beside 8 MFMAs): a table of the 16 offsets cost 16 VGPRs and spilled.
-  const int l0 = 8 * h + q4;
+  const int l0 = 8 * tl.h + tl.q4;
   auto xoff = [&](int c, int s2) {
     int p = 16 * c + l0 + 4 * s2;
     p = p < TH * TW ? p : TH * TW - 1;
     const int jr = (p * 41) >> 10;   // p / 25 for p < 128
-    return jr * XROW + (p - jr * TW) * PITCH + chan_off;
+    return jr * XROW + (p - jr * TW) * PITCH + tl.chan_off;
   };
-  const unsigned char* const a_base = ds + (8 * h + q4) * PITCH + chan_off;
+  const unsigned char* const a_base = ds + l0 * PITCH + tl.chan_off;
   // this wave's taps kx = 2 wave, 2 wave + 1: parity plane kx & 1, entry shift kx >> 1
   const int kx0 = 2 * wave;
   const int tapoff0 = ((kx0 & 1) * PC + (kx0 >> 1)) * PITCH, tapoff1 = (((kx0 + 1) & 1) * PC + ((kx0 + 1) >> 1)) * PITCH;
@@ -145,8 +137,7 @@ __global__ __launch_bounds__(256, 2) void conv_win_wgrad_kernel(WinWgradArgs a) 
 #pragma unroll
       for (int g = 0; g < 16; ++g) acc[t][v][g] = 0.f;
 
-  int tile = grp;
-  if (tile >= ntiles) return;   // (whole workgroup: no tile, nothing to add)
+  int tile = grp;   // (a group beyond the tile count loads zeros, multiplies nothing and flushes: wgrad_flush_tile's `live`)
   gload(tile);
   lstore();
   __syncthreads();
@@ -156,16 +147,12 @@ __global__ __launch_bounds__(256, 2) void conv_win_wgrad_kernel(WinWgradArgs a) 
   struct Frag { bf16x8 a[2], b[4]; };
   auto fload = [&](int c, Frag& f) {
 #pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const bf16x4 l = tr_read(a_base + 64 * t + (16 * c) * PITCH), hh = tr_read(a_base + 64 * t + (16 * c + 4) * PITCH);
-      f.a[t] = __builtin_shufflevector(l, hh, 0, 1, 2, 3, 4, 5, 6, 7);
-    }
+    for (int t = 0; t < 2; ++t) f.a[t] = tr_frag(a_base + 64 * t + (16 * c) * PITCH, PITCH);
     const int x0 = xoff(c, 0), x1 = xoff(c, 1);
 #pragma unroll
     for (int v = 0; v < 4; ++v) {
       const int to = (v >> 1) ? tapoff1 : tapoff0;
-      const bf16x4 l = tr_read(xs + x0 + to + 64 * (v & 1)), hh = tr_read(xs + x1 + to + 64 * (v & 1));
-      f.b[v] = __builtin_shufflevector(l, hh, 0, 1, 2, 3, 4, 5, 6, 7);
+      f.b[v] = tr_frag(xs + x0 + to + 64 * (v & 1), xs + x1 + to + 64 * (v & 1));
     }
   };
   for (; tile < ntiles; tile += a.groups) {
@@ -197,22 +184,12 @@ __global__ __launch_bounds__(256, 2) void conv_win_wgrad_kernel(WinWgradArgs a) 
     __syncthreads();
   }
 
-  // ---- one flush per workgroup: lane r = input channel (consecutive lanes -> 128-byte segments of an OHWI row)
-  const int r = lane & 31;
+  // ---- one flush per workgroup
 #pragma unroll
-  for (int v = 0; v < 4; ++v) {
-    const int tap = ky * K + kx0 + (v >> 1);
-    const int ci = 32 * (v & 1) + r;
+  for (int v = 0; v < 4; ++v)
 #pragma unroll
     for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int g = 0; g < 16; ++g) {
-        const int co = 32 * t + (g & 3) + 8 * (g >> 2) + 4 * h;
-        float* const q = a.dw + (size_t)grp * a.slab + ((size_t)co * (K * K) + tap) * 64 + ci;
-        if (a.slab) *q = acc[t][v][g];
-        else atomicAdd(q, acc[t][v][g]);
-      }
-  }
+      wgrad_flush_tile(acc[t][v], a.dw, a.slab, grp, 32 * t, K * K, ky * K + kx0 + (v >> 1), 64, 32 * (v & 1) + (lane & 31), tl.h, grp < ntiles);
 }
 
 }  // namespace
@@ -222,13 +199,10 @@ __global__ __launch_bounds__(256, 2) void conv_win_wgrad_kernel(WinWgradArgs a) 
 // route of wsmg_conv_bf16.hip sends none here).
 static bool winw_fits(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH, int OW) {
   if (Cin != 64 || Cout != 64 || KH != 8 || KW != 8 || stride != 2 || pad != 3) return false;
-  return !((size_t)B * H * W * 128 >= (1ull << 31) || (size_t)B * OH * OW * 128 >= (1ull << 31));
+  return wsmg_check_conv_bf16(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW) == 0;   // (its 32-bit byte-offset limits)
 }
 static int winw_groups(int B, int OH, int OW) {
-  const int ntiles = B * ((OH + TH - 1) / TH) * ((OW + TW - 1) / TW);
-  int groups = 64;   // 8 roles x 64 groups = 512 workgroups = 2 per CU (78 KB of LDS each)
-  if (groups > ntiles) groups = ntiles;
-  return (groups + 7) / 8 * 8;   // whole XCD rounds (groups beyond the tile count find no tile and only flush zeros)
+  return wgrad_groups(64, B * ((OH + TH - 1) / TH) * ((OW + TW - 1) / TW));   // 8 roles x 64 groups = 512 workgroups = 2 per CU (78 KB of LDS each)
 }
 
 // tile groups (= slabs of the deterministic form) this kernel would use; 0: the layer is not this kernel's
@@ -241,15 +215,6 @@ int wsmg_conv_win_wgrad_bf16(const void* x, const void* dy, float* dw_ohwi, long
   if (!winw_fits(B, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW)) return WSMG_EINVAL;
   WinWgradArgs a{(const bf16_t*)x, (const bf16_t*)dy, dw_ohwi, (int64_t)slab_floats, B, H, W, OH, OW, (OH + TH - 1) / TH, (OW + TW - 1) / TW, 0,
                  (unsigned)((size_t)B * H * W * 128), (unsigned)((size_t)B * OH * OW * 128)};
-  const int groups = winw_groups(B, OH, OW);
-  a.groups = groups;
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_win_wgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       X_BYTES + D_BYTES);
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }
-  hipLaunchKernelGGL(conv_win_wgrad_kernel, dim3((unsigned)(8 * groups)), dim3(256), X_BYTES + D_BYTES, s, a);
-  WSMG_RETURN_LAUNCH();
+  a.groups = winw_groups(B, OH, OW);
+  return wsmg_launch_dyn_lds<conv_win_wgrad_kernel>(dim3((unsigned)(K * a.groups)), dim3(256), X_BYTES + D_BYTES, s, a);
 }

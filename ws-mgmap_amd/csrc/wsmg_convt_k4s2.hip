@@ -197,13 +197,5 @@ int wsmg_convt_k4s2_bf16(const void* src, const void* w_ihwo, void* dst, double*
   if (grid == 0 || (stats && nslab <= 0)) return WSMG_EINVAL;
   CtArgs a{(const bf16_t*)src, (const bf16_t*)w_ihwo, (bf16_t*)dst, B, H, W, (int)wsmg_cdiv((int64_t)B * H * W, CT_MT),
            (unsigned)((size_t)B * H * W * 64 * 2), (unsigned)(32u * 16 * 64 * 2), stats, nslab};
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(convt_k4s2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, CT_LDS);
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }
-  hipLaunchKernelGGL(convt_k4s2_kernel, dim3((unsigned)grid), dim3(256), CT_LDS, s, a);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return wsmg_launch_dyn_lds<convt_k4s2_kernel>(dim3((unsigned)grid), dim3(256), CT_LDS, s, a);
 }
